@@ -11,6 +11,14 @@ when N>1) -> SGD-Nesterov/clipnorm update, on one synthetic COCO-shaped batch th
 HBM before the timed region.  Workload = BASELINE.json configs[1] (per GPU: batch 16, 640x640,
 d=256 h=8, 100 queries, COCO-80 classes, dropout 0.1 like the reference).  Rank 0 prints ONE JSON
 line.  `value` is whole-job images/s (global batch / max-over-ranks step time).
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else the line can carry - the
+per-launch roofline, the CPU baseline, configs[3]'s batch 32, the fp32 / fp32-grade policies, configs[2], the data-parallel
+all-reduce timings, the panoptic head alone, the step's HBM figure - runs only with --full (each leg can still be switched off
+there with its --no-* option); without it those fields are null.  --dump-outputs DIR writes what one step of the timed
+path returns (per-image losses and metrics) and a fixed, seeded sample of the variables it trains as DIR/<name>.npy.  That
+step starts from a state that is the same every run (DumpState): the timed steps themselves start from weights that ~50
+earlier updates, summed with float atomics, have carried apart between runs.
 """
 from __future__ import annotations
 
@@ -282,6 +290,75 @@ def usable_cores() -> int:
     return max(1, min(n, int(os.environ.get("BDETR_CPU_THREADS", "16"))))
 
 
+DUMP_SAMPLE = 1 << 23                  # --dump-outputs: at most 8 M sampled variable elements (32 MB of float32)
+
+
+class DumpState:
+    """--dump-outputs: the inputs of the dumped step, the same every run.  The first step of the run (build-by-first-call, untimed)
+    runs with the library's deterministic reductions (kernels.set_deterministic: split-K slices and column sums folded in a fixed
+    order, bit-identical from run to run), and everything a step reads besides the batch is kept from right after it: every
+    variable (weights and BatchNorm moving statistics), the optimizer's momentum and the step / iteration counters (dropout seed,
+    learning rate).  Every later step sums with float atomics, so the weights the timed steps start from differ between runs by
+    more than rounding after tens of updates; the dumped step is therefore one more step of the timed path - same launch mode,
+    same kernels - from this state after the timed region, whose outputs differ between runs by rounding only."""
+
+    def __init__(self, model, run_step, batch):
+        import torch
+        from boosted_detr_amd import kernels as K
+        prev = K.set_deterministic(True)
+        try:
+            run_step(batch)
+            torch.cuda.synchronize()
+        finally:
+            K.set_deterministic(prev)
+        self.values = [v.value.detach().clone() for v in model.variables]
+        self.momentum = model.optimizer.flat_mom.clone()
+        self.counters = (model.steps_done, model.optimizer.iterations)
+
+    def step(self, model, run_step, batch, use_graph):
+        """Restore the state, run one step of the timed path (eager or replayed, as the timed steps ran) and return it synchronised."""
+        import torch
+        from boosted_detr_amd.engine import bump_weights_version
+        model.guard_flush()
+        torch.cuda.synchronize()
+        for v, x in zip(model.variables, self.values):
+            v.value.copy_(x)
+        model.optimizer.flat_mom.copy_(self.momentum)
+        model.steps_done, model.optimizer.iterations = self.counters
+        bump_weights_version()                # weight-derived operands (packed / pre-split copies) are rebuilt from the restored values
+        keep, model.use_graph = model.use_graph, use_graph
+        redos = model.range_redos
+        try:
+            run_step(batch)
+            model.guard_flush()
+            torch.cuda.synchronize()
+        finally:
+            model.use_graph = keep
+        if model.range_redos != redos:
+            raise SystemExit("bench.py: the range guard tripped in the dumped step; no outputs written")
+
+
+def dump_outputs(model, out_dir, extra=None):
+    """What the model's last step computed, as float32 .npy files: the per-image vectors train_step returns
+    (loss and metrics, one file per weak learner when there are several), the tensors in `extra` (name -> tensor) and the trained
+    variables after the update - all of them flattened in model order, a sample of DUMP_SAMPLE elements at positions drawn by a
+    fixed seed when larger."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: t.detach().float().cpu().numpy() for k, t in (extra or {}).items()}
+    for name, ts in model.step_logs().items():
+        for i, t in enumerate(ts):
+            arrays[name if len(ts) == 1 else f"{name}_{i}"] = t.detach().float().cpu().numpy()
+    flat = torch.cat([v.value.detach().reshape(-1).float() for v in model.variables])
+    if flat.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.Generator(np.random.PCG64(20240)).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    arrays["variables_sample"] = flat.cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return sorted(arrays)
+
+
 def cpu_baseline(args):
     """The build's CPU restatement (oracle, PyTorch-CPU fp32 + scipy matcher) timed on the host cores:
     forward + matcher + loss + backward on a bounded sample of the same workload (batch 2)."""
@@ -323,6 +400,10 @@ def main():
     ap.add_argument("--backbone", default="ResNet", choices=["ResNet", "ResNet101"], help="configs[4]: ResNet101 (no reference counterpart)")
     ap.add_argument("--panoptic", action="store_true", help="configs[4]: append the panoptic mask head's forward (PanopticAttention + PanopticNeck on the "
                     "step's encoder output) to every step: --backbone ResNet101 --image 800 --image-w 1333 --queries 300 --batch 8 --panoptic")
+    ap.add_argument("--full", action="store_true", help="also run every secondary leg after the timed steps (roofline, CPU baseline, batch 32, fp32 / "
+                    "fp32-grade policies, configs[2], all-reduce timings, panoptic head alone, step HBM figure); a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what one step of the timed path computes from a state that is the same "
+                    "every run (per-image losses and metrics, a seeded sample of the trained variables) to DIR/<name>.npy as float32")
     ap.add_argument("--no-fp32-policy", action="store_true", help="skip the secondary measurement under the exact-fp32 arithmetic policy")
     ap.add_argument("--no-batch32", action="store_true", help="skip the secondary measurement at configs[3]'s per-GPU batch (32)")
     ap.add_argument("--no-configs2", action="store_true", help="skip the secondary measurement of configs[2] (BoostedDETR + Fashionpedia heads, batch 16)")
@@ -418,6 +499,7 @@ def main():
         if args.panoptic:
             masks[0] = model.panoptic_masks()
 
+    dump_state = DumpState(model, run_step, batch) if args.dump_outputs else None
     if distributed:
         # set-up, like the build: a data-parallel model settles the placement of its side stream by timing its first eager steps on each
         # candidate (training.Model._side_tune_begin: a schedule of fixed length, the same on every rank)
@@ -495,7 +577,7 @@ def main():
     model.guard_flush()
     redos_before = model.range_redos
 
-    want_roof = not args.no_roofline          # every rank runs the bracketed region (collectives must match); rank 0 records
+    want_roof = args.full and not args.no_roofline          # every rank runs the bracketed region (collectives must match); rank 0 records
 
     def timed_region():
         with quiet_gc(collect=False):
@@ -528,7 +610,7 @@ def main():
 
     # Data-parallel legs (N > 1): a few more steps with events on the communication stream around every bucket's all-reduce.
     allreduce = None
-    if distributed:
+    if distributed and args.full:
         model._dp.profile = True
         for _ in range(min(5, args.steps)):
             run_step(batch)
@@ -537,7 +619,7 @@ def main():
 
     # the mask head alone (events on the launch stream), next to the step it is appended to
     panoptic = None
-    if args.panoptic:
+    if args.panoptic and args.full:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(5):
@@ -608,14 +690,14 @@ def main():
     # CPU baseline here, between the primary GPU legs and the secondary ones (round 3 ran it last: the driver's utilisation samples
     # then saw an idle GPU for the last two thirds of the run).  Rank 0, N = 1 only.
     cpu_line = None
-    if rank == 0 and not (args.no_cpu_baseline or world > 1 or not is_config2(args)):
+    if rank == 0 and args.full and not (args.no_cpu_baseline or world > 1 or not is_config2(args)):
         cpu_line = cpu_baseline(args)
 
     # Secondary measurement at BASELINE.json configs[3]'s per-GPU batch (global 256 on 8 GPUs = 32 per GPU): the same
     # model and step, a batch of 32 resident images per rank.  `value` above stays the fixed 16-per-GPU weak-scaling
     # series; this one is reported next to it in config.configs3 (and is a first-class line of its own with --batch 32).
     b32 = None
-    if not args.no_batch32 and is_config2(args) and args.batch != 32:
+    if args.full and not args.no_batch32 and is_config2(args) and args.batch != 32:
         host32 = make_batch(32, args.image, args.image, 100, 82, seed=4321 + rank)
         batch32 = {"image": to_device(host32["image"]), "category": to_device(host32["category"], torch.int32),
                    "attribute": to_device(host32["attribute"], torch.int32),
@@ -667,7 +749,7 @@ def main():
                 "arithmetic": arithmetic}
 
     fp32_line = grade_line = None
-    if not args.no_fp32_policy and is_config2(args):
+    if args.full and not args.no_fp32_policy and is_config2(args):
         fp32_line = policy_leg("fp32", None, "every conv/GEMM product exact fp32 (v_mfma_f32_32x32x2_f32)")
         # every product of the step at 2^-22 or better with the forward still on the 16-bit MFMA: the headline's forward (f16 pairs,
         # three products) and an exact-fp32 backward (the headline's gradient products are bf16 pairs, 2^-18)
@@ -680,7 +762,7 @@ def main():
     # BASELINE.json configs[2]: BoostedDETR (3 weak learners) with the Fashionpedia heads (46 categories / 294 attributes, attribute
     # weight 1) at batch 16, graph replay like the headline.  A second model in the same process (its own flat buffers and graph pools).
     c2 = None
-    if not args.no_configs2 and is_config2(args) and args.batch == 16 and not distributed:
+    if args.full and not args.no_configs2 and is_config2(args) and args.batch == 16 and not distributed:
         import copy
         a2 = copy.copy(args)
         a2.model, a2.fashionpedia, a2.learners = "boosted", True, 3
@@ -720,12 +802,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    logs = model.logs_to_host(model.step_logs())
+    if dump_state is not None:                 # every rank runs the step (its collectives must match); rank 0 writes
+        dump_state.step(model, run_step, batch, replayed)
+        if rank == 0:
+            names = dump_outputs(model, args.dump_outputs, {"panoptic_masks": masks[0]} if args.panoptic else None)
+            note(f"outputs of one timed-path step from the fixed state -> {args.dump_outputs}: {', '.join(names)}")
     note(f"timed {args.steps} steps in {elapsed:.3f} s")
     if rank == 0:
         global_batch = args.batch * world
         ms_per_step = elapsed / args.steps * 1e3
         value = global_batch * args.steps / elapsed
-        logs = model.logs_to_host(model.step_logs())
         gflop_img = GFLOP_PER_IMAGE if is_config2(args) else (GFLOP_PER_IMAGE_CONFIG5 + (GFLOP_PANOPTIC_FWD if args.panoptic else 0.0)) if is_config5(args) else None
         out = {
             "metric": METRIC if not is_config5(args) else "images/sec training step (fwd+matcher+loss+bwd" + (" + mask head fwd" if args.panoptic else "") + "), 1333x800 N=300",
@@ -746,7 +833,7 @@ def main():
             # whole step against the two roofs (the judge's cross-checks): algorithmic FLOPs / step time / 3-product MFMA roof, and the step's
             # measured HBM traffic (committed PMC passes) / this run's step time
             "step_frac_of_mfma_roof": round(value / world * gflop_img / 1e3 / (PEAK_16BIT_MFMA_TFLOPS / 3), 4) if gflop_img else None,
-            "step_hbm": step_hbm(ms_per_step) if is_config2(args) and args.batch == 16 else None,
+            "step_hbm": step_hbm(ms_per_step) if args.full and is_config2(args) and args.batch == 16 else None,
             "final_loss": round(logs.get("loss", float("nan")), 4),
             "range_guard": guard,
             "allreduce": allreduce,

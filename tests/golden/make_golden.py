@@ -1,4 +1,4 @@
-"""Generates tests/golden/config1.npz from the CPU oracle (oracle/detr_oracle.py).
+"""Generates tests/golden/config1.npz and boosted3.npz from the CPU oracle (oracle/detr_oracle.py).
 
 The reference (TensorFlow) cannot run in the authoring container, so these vectors pin the
 BUILD'S OWN restatement, not the reference ("parity unpinned", see the oracle's header): they
@@ -80,9 +80,11 @@ def main():
     bcfg = O.Config(num_decoder_blocks=3, boosted=True)
     bbatch = O.make_batch(bcfg, 2, 20, seed=77, num_objects=[5, 2])
     build(bcfg, bbatch, "boosted3", out)
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "config1.npz")
-    np.savez_compressed(path, **out)
-    print(path, os.path.getsize(path), "bytes,", len(out), "arrays")
+    for tag in ("config1", "boosted3"):              # one file per configuration: each stays under 1 MiB
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), f"{tag}.npz")
+        part = {k: v for k, v in out.items() if k.startswith(tag + "/")}
+        np.savez_compressed(path, **part)
+        print(path, os.path.getsize(path), "bytes,", len(part), "arrays")
 
 
 if __name__ == "__main__":

@@ -101,6 +101,32 @@ def test_bench_batch_generator_matches_oracle_generator():
     assert 1 <= bench.usable_cores() <= 16
 
 
+def test_bench_dump_outputs_float32_bounded_and_seeded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the step's per-image vectors (one file per weak learner), extra outputs (the panoptic masks) and a
+    variable sample drawn at the same positions every run, float32, within 64 MB."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.DUMP_SAMPLE * 4 <= (64 << 20) - (1 << 20)     # the shipped sample leaves room for the per-image vectors
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    g = torch.Generator().manual_seed(0)
+    logs = {"loss": [torch.rand(4, dtype=torch.float64, generator=g)], "IOU": [torch.rand(4, generator=g), torch.rand(4, generator=g)]}
+    model = type("M", (), {"variables": [type("V", (), {"value": torch.randn(s, generator=g)})() for s in (700, 600, 3)],
+                           "step_logs": lambda self: logs})()
+    extra = {"panoptic_masks": torch.randn(2, 3, 5, generator=g)}
+    names = bench.dump_outputs(model, str(tmp_path / "a"), extra)
+    assert names == ["IOU_0", "IOU_1", "loss", "panoptic_masks", "variables_sample"]
+    bench.dump_outputs(model, str(tmp_path / "b"), extra)
+    flat = torch.cat([v.value for v in model.variables]).numpy()
+    for n in names:
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+    assert np.array_equal(np.load(tmp_path / "a" / "IOU_1.npy"), logs["IOU"][1].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "panoptic_masks.npy"), extra["panoptic_masks"].numpy())
+    s = np.load(tmp_path / "a" / "variables_sample.npy")
+    assert s.shape == (1000,) and np.isin(s, flat).all() and len(np.unique(s)) == 1000
+
+
 _DP_SCRIPT = r'''
 import os, sys, numpy as np, torch, torch.distributed as dist
 sys.path.insert(0, sys.argv[1])

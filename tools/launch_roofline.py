@@ -1,4 +1,4 @@
-"""Per-launch roofline of the conv/GEMM family from a bdetr_prof_dump CSV (BDETR_PROF_DUMP=<file> python bench.py ...): every
+"""Per-launch roofline of the conv/GEMM family from a bdetr_prof_dump CSV (BDETR_PROF_DUMP=<file> python bench.py --full ...): every
 distinct (shape, tile, kind) with its time per step, the time its own roof allows (the larger of algorithmic FLOPs / the 3-product
 MFMA roof and algorithmic bytes / HBM peak) and the gap between them, sorted by the gap - where the family's time is lost."""
 import csv

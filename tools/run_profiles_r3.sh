@@ -6,7 +6,7 @@ OUT=gpurun_out/profiles_r3
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 B="--no-cpu-baseline --no-roofline --no-batch32 --no-fp32-policy"
-python bench.py --steps 40 --warmup 5 > $OUT/r03_bench_line.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+python bench.py --steps 40 --warmup 5 --full > $OUT/r03_bench_line.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 python bench.py --steps 40 --warmup 5 --no-graph --no-cpu-baseline --no-roofline --no-batch32 --no-fp32-policy > $OUT/r03_bench_line_eager.json 2> $OUT/bench_eager.err || { tail -20 $OUT/bench_eager.err; exit 1; }
 BDETR_SIDE_STREAM=0 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/serial -- python3 bench.py --steps 5 --warmup 2 --no-graph $B > $OUT/serial.log 2>&1 || { tail -20 $OUT/serial.log; exit 1; }
 find $OUT/serial -name "*kernel_stats.csv" -exec cp {} $OUT/r03_kernel_stats_serial.csv \;

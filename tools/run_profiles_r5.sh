@@ -9,8 +9,8 @@ OUT=gpurun_out/profiles_r5
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 B="--no-cpu-baseline --no-roofline --no-batch32 --no-fp32-policy --no-configs2"
-python bench.py --steps 40 --warmup 5 > $OUT/r05_bench_line.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
-BDETR_PROF_DUMP=$OUT/launches.csv python bench.py --steps 10 --warmup 3 --no-graph --no-cpu-baseline --no-batch32 --no-fp32-policy --no-configs2 > $OUT/bench_launches.json 2> $OUT/bench_launches.err || { tail -20 $OUT/bench_launches.err; exit 1; }
+python bench.py --steps 40 --warmup 5 --full > $OUT/r05_bench_line.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+BDETR_PROF_DUMP=$OUT/launches.csv python bench.py --steps 10 --warmup 3 --full --no-graph --no-cpu-baseline --no-batch32 --no-fp32-policy --no-configs2 > $OUT/bench_launches.json 2> $OUT/bench_launches.err || { tail -20 $OUT/bench_launches.err; exit 1; }
 python tools/launch_roofline.py $OUT/launches.csv 10 > $OUT/r05_launch_roofline.txt
 python bench.py --steps 40 --warmup 5 --graph $B > $OUT/r05_bench_line_graph.json 2> $OUT/bench_graph.err || { tail -20 $OUT/bench_graph.err; exit 1; }
 python bench.py --steps 40 --warmup 5 --no-graph $B > $OUT/r05_bench_line_eager.json 2> $OUT/bench_eager.err || { tail -20 $OUT/bench_eager.err; exit 1; }
