@@ -164,6 +164,13 @@ SIGNATURES = {
     "bdetr_layernorm_act_fwd": (I, [P, L, I, I, P, P, F, F, P, I, P]),
     "bdetr_copy_cols": (I, [P, L, I, I, P, I, I, P]),
     "bdetr_nhwc_to_nchw": (I, [P, I, I, I, I, P, P]),
+    "bdetr_layernorm_act_bwd_chunks": (I, [L]),
+    "bdetr_layernorm_act_bwd": (I, [P, L, I, I, P, P, F, F, P, I, P, P, P, P, P, P]),
+    "bdetr_resize_bilinear_nhwc_bwd": (I, [P, I, I, I, I, P, I, I, P]),
+    "bdetr_nchw_to_nhwc": (I, [P, I, I, I, P, I, P]),
+    "bdetr_conv_weight_pack": (I, [P, P, I, I, I, I, I, I, I, P, P, P]),
+    "bdetr_conv_weight_unpack": (I, [P, P, I, I, I, I, I, I, P, P, P]),
+    "bdetr_mask_loss": (I, [P, P, P, P, I, I, I, I, F, F, F, F, P, P, P, P]),
     "bdetr_softmax_lastdim_fwd": (I, [P, P, L, I, P]),
     "bdetr_softmax_lastdim_bwd": (I, [P, P, P, L, I, P]),
     "bdetr_sigmoid_fwd": (I, [P, P, L, P]),

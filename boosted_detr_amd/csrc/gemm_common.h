@@ -24,6 +24,7 @@ struct GemmParams {
     int vec_store;                      // C rows are 16-byte aligned and J % 4 == 0: LDS-transposed float4 stores
     int rowmap;                         // scatter C rows through a strided-pixel map (conv s>1 bwd-data)
     int rm_OW, rm_OHOW, rm_H, rm_W, rm_stride;
+    int rm_off;                         // + this many pixels: the tap (r, s) of an R, S <= stride conv, r * W + s (0 for 1x1)
     // grouped launch (dense operands only): blockIdx.z selects one of up to 4 independent problems that
     // share J, R and the epilogue flags but have their own pointers and row count (Q/K/V projections)
     int ngroups;
@@ -163,7 +164,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[BM / WM / 32][BN / W
         if (!g.rowmap) return i;
         int n = i / g.rm_OHOW; int rem = i - n * g.rm_OHOW;
         int oh = rem / g.rm_OW; int ow = rem - oh * g.rm_OW;
-        return ((int64_t)n * g.rm_H + (int64_t)oh * g.rm_stride) * g.rm_W + (int64_t)ow * g.rm_stride;
+        return ((int64_t)n * g.rm_H + (int64_t)oh * g.rm_stride) * g.rm_W + (int64_t)ow * g.rm_stride + g.rm_off;
     };
     gemm_bias_act_stats<BM, BN, WM, WN>(acc, g, tile_i, i0, j0, bias_pre);
 

@@ -963,7 +963,25 @@ extern "C" int bdetr_conv2d_bwd_data(const float* dy, const float* w, float* dx,
         DenseOp b{w, d->C, 0, 0, d->K, d->C};
         return launch_any<DenseLoader<4>, true, DenseLoader<4>, false>(a, b, g, 1, st, use_split(true));
     }
-    BDETR_CHECK_ARG(d->stride == 1, "bdetr_conv2d_bwd_data: stride>1 only for 1x1 convs");
+    if (d->stride > 1 && d->pad == 0 && d->R <= d->stride && d->S <= d->stride) {
+        // taps that never overlap (the panoptic head's 3x3 stride-4 ConvOut): every (output pixel, tap) owns one input pixel, so
+        // dx = R*S dense products dy[M,K] x w[:, r, s, :] scattered to the pixels (oh*stride + r, ow*stride + s); the pixels no
+        // window reads (ih % stride >= R, or beyond the last window) keep the zero fill
+        if (!accumulate) {
+            if (int e = bdetr_zero_bytes(dx, sizeof(float) * (size_t)d->N * d->H * d->W * d->C, st)) return e;
+        }
+        g.I = M; g.J = d->C; g.R = d->K;
+        g.rowmap = 1; g.rm_OW = d->OW; g.rm_OHOW = d->OH * d->OW; g.rm_H = d->H; g.rm_W = d->W; g.rm_stride = d->stride;
+        DenseOp a{dy, d->K, 0, 0, M, d->K};
+        for (int r = 0; r < d->R; ++r)
+            for (int s = 0; s < d->S; ++s) {
+                g.rm_off = r * d->W + s;
+                DenseOp b{w + (int64_t)(r * d->S + s) * d->C, (int64_t)d->R * d->S * d->C, 0, 0, d->K, d->C};
+                if (int e = launch_any<DenseLoader<4>, true, DenseLoader<4>, false>(a, b, g, 1, st, use_split(true))) return e;
+            }
+        return 0;
+    }
+    BDETR_CHECK_ARG(d->stride == 1, "bdetr_conv2d_bwd_data: stride>1 only for 1x1 convs or taps that do not overlap (R, S <= stride, pad 0)");
     // dx[n,ih,iw,c] = sum_{r,s,k} dy[n, ih+pad-r, iw+pad-s, k] * w[k][r][s][c]
     //              = patch gather over dy with pad' = R-1-pad and flipped taps
     const int Mx = d->N * d->H * d->W;

@@ -241,7 +241,7 @@ __device__ __forceinline__ void direct_epilogue(f32x16 (&acc)[BM / WM / 32][BN /
         const __amdgpu_buffer_rsrc_t rsC = make_rsrc(g.c);
         const int i = i0 + wm * WTM + (lane % WTM);
         const int n = i / g.rm_OHOW, rem = i - n * g.rm_OHOW, oh = rem / g.rm_OW, ow = rem - oh * g.rm_OW;
-        const unsigned rmap = i < g.I ? (unsigned)((n * g.rm_H + oh * g.rm_stride) * g.rm_W + ow * g.rm_stride) * ldc4 : OOB;
+        const unsigned rmap = i < g.I ? (unsigned)((n * g.rm_H + oh * g.rm_stride) * g.rm_W + ow * g.rm_stride + g.rm_off) * ldc4 : OOB;
         const bool accum = g.mode == ST_ACCUM;
 #pragma unroll
         for (int a = 0; a < TM; ++a)

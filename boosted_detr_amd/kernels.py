@@ -1008,7 +1008,7 @@ def set_loss(d: LossDesc, cat_pred, att_pred, box_pred, cat_ids, att_hot, bbox, 
 
 
 # --------------------------------------------------------------------------------------
-# panoptic head pieces (forward only) - csrc/panoptic.hip
+# panoptic head pieces (forward) - csrc/panoptic.hip
 # --------------------------------------------------------------------------------------
 def pad4(c: int) -> int:
     return (c + 3) // 4 * 4
@@ -1033,10 +1033,12 @@ def layernorm_act(x, C_true: int, gamma, beta, eps: float, slope: float = 1.0, l
     return out
 
 
-def copy_cols(src, C_true: int, dst, col0: int):
+def copy_cols(src, C_true: int, dst, col0: int, src_col0: int = 0):
+    """dst[..., col0 + c] = src[..., src_col0 + c] for c < C_true (src_col0: the concatenation's backward slices a gradient apart)."""
     _chk(src, dst)
     rows = src.numel() // src.shape[-1]
-    check(_lib.lib().bdetr_copy_cols(_p(src), rows, C_true, src.shape[-1], _p(dst), dst.shape[-1], col0, _stream()), "copy_cols")
+    assert src_col0 + C_true <= src.shape[-1] and dst.numel() // dst.shape[-1] == rows
+    check(_lib.lib().bdetr_copy_cols(_p(src) + 4 * src_col0, rows, C_true, src.shape[-1], _p(dst), dst.shape[-1], col0, _stream()), "copy_cols")
     return dst
 
 
@@ -1046,3 +1048,86 @@ def nhwc_to_nchw(x, C_true: int):
     out = empty(B, C_true, H * W, like=x)
     check(_lib.lib().bdetr_nhwc_to_nchw(_p(x), B, H * W, C_true, ld, _p(out), _stream()), "nhwc_to_nchw")
     return out
+
+
+# --------------------------------------------------------------------------------------
+# panoptic head training - csrc/panoptic.hip (backward pieces, weight pack, mask loss)
+# --------------------------------------------------------------------------------------
+def layernorm_act_bwd(x, C_true: int, gamma, beta, eps: float, slope: float, dout, dgamma=None, dbeta=None):
+    """Adjoint of ``layernorm_act(x, C_true, gamma, beta, eps, slope)``: dx shaped like x (padding columns 0), dgamma / dbeta [C_true]
+    (written, not added)."""
+    _chk(x, gamma, beta, dout, dgamma, dbeta)
+    L = _lib.lib()
+    ld, ldo = x.shape[-1], dout.shape[-1]
+    rows = x.numel() // ld
+    assert dout.numel() // ldo == rows, (x.shape, dout.shape)
+    nblk = L.bdetr_layernorm_act_bwd_chunks(rows)
+    parts = empty(2, nblk, C_true, like=x)
+    dx = torch.empty_like(x)
+    dgamma = empty(C_true, like=x) if dgamma is None else dgamma
+    dbeta = empty(C_true, like=x) if dbeta is None else dbeta
+    check(L.bdetr_layernorm_act_bwd(_p(x), rows, C_true, ld, _p(gamma), _p(beta), eps, slope, _p(dout), ldo, _p(dx), _p(parts[0]), _p(parts[1]),
+                                    _p(dgamma), _p(dbeta), _stream()), "layernorm_act_bwd")
+    return dx, dgamma, dbeta
+
+
+def resize_bilinear_bwd(dout, h: int, w: int):
+    """Adjoint of ``resize_bilinear(x [B,h,w,C], H, W)``."""
+    _chk(dout)
+    B, H, W, Cc = dout.shape
+    din = empty(B, h, w, Cc, like=dout)
+    check(_lib.lib().bdetr_resize_bilinear_nhwc_bwd(_p(dout), B, H, W, Cc, _p(din), h, w, _stream()), "resize_bilinear_bwd")
+    return din
+
+
+def nchw_to_nhwc(x, H: int, W: int, ld_out: int):
+    """x [B, C, H*W] -> [B, H, W, ld_out] (columns C.. ld_out-1 zero): the adjoint of ``nhwc_to_nchw``."""
+    _chk(x)
+    B, Cc, P = x.shape
+    assert P == H * W
+    out = empty(B, H, W, ld_out, like=x)
+    check(_lib.lib().bdetr_nchw_to_nhwc(_p(x), B, P, Cc, _p(out), ld_out, _stream()), "nchw_to_nhwc")
+    return out
+
+
+def conv_weight_pack(kernel, bias, transpose: bool):
+    """Keras-layout kernel (HWIO [R,S,Cin,K]; transpose: Conv2DTranspose [R,S,K,Cin]) + bias [K] -> zero-padded OHWI
+    [pad4(K), R, S, pad4(Cin)] (taps flipped for transpose) and bias [pad4(K)]."""
+    _chk(kernel, bias)
+    R, S = kernel.shape[0], kernel.shape[1]
+    Kc, Cin = (kernel.shape[2], kernel.shape[3]) if transpose else (kernel.shape[3], kernel.shape[2])
+    Kp, Cp = pad4(Kc), pad4(Cin)
+    w = empty(Kp, R, S, Cp, like=kernel)
+    b = empty(Kp, like=kernel)
+    check(_lib.lib().bdetr_conv_weight_pack(_p(kernel), _p(bias), R, S, Cin, Kc, int(transpose), Cp, Kp, _p(w), _p(b), _stream()), "conv_weight_pack")
+    return w, b
+
+
+def conv_weight_unpack(dw, db, keras_shape, transpose: bool, dkernel=None, dbias=None):
+    """Adjoint of ``conv_weight_pack``: the true-channel part of the padded dw / db into Keras-layout dkernel / dbias (either may be None)."""
+    _chk(dw, db, dkernel, dbias)
+    R, S = keras_shape[0], keras_shape[1]
+    Kc, Cin = (keras_shape[2], keras_shape[3]) if transpose else (keras_shape[3], keras_shape[2])
+    if dkernel is None and dbias is None:
+        return None, None
+    check(_lib.lib().bdetr_conv_weight_unpack(_p(dw), _p(db), R, S, Cin, Kc, int(transpose), dw.shape[-1], _p(dkernel), _p(dbias), _stream()),
+          "conv_weight_unpack")
+    return dkernel, dbias
+
+
+MASK_FOCAL_ALPHA, MASK_FOCAL_GAMMA = 0.25, 2.0
+
+
+def mask_loss(logits, masks, match, num_objects, mask_weight=1.0, loss_scale=1.0, want_grads=True):
+    """logits [B,N,P], masks [B,M,P], match int32 [B,M], num_objects int32 [B] -> (loss [B], dlogits [B,N,P] | None)."""
+    _chk(logits, masks)
+    _chk(match, num_objects, dtype=torch.int32)
+    B, N, P = logits.shape
+    M = masks.shape[1]
+    assert masks.shape == (B, M, P) and match.shape == (B, M), (logits.shape, masks.shape, match.shape)
+    row_loss = empty(B, N, like=logits)
+    loss = empty(B, like=logits)
+    dlogits = torch.empty_like(logits) if want_grads else None
+    check(_lib.lib().bdetr_mask_loss(_p(logits), _p(masks), _p(match), _p(num_objects), B, M, N, P, MASK_FOCAL_ALPHA, MASK_FOCAL_GAMMA,
+                                     float(mask_weight), float(loss_scale), _p(row_loss), _p(loss), _p(dlogits), _stream()), "mask_loss")
+    return loss, dlogits

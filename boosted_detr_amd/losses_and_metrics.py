@@ -9,6 +9,7 @@ writes the sparse gradient - no host synchronisation anywhere.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -117,3 +118,41 @@ class MatchingMetric(Layer):
     def __init__(self, name="MatchingMetric", **kwargs):
         super().__init__(name=name, **kwargs)
         self.built = True
+
+
+class MaskLoss(Layer):
+    """Mask loss of the panoptic head (DETR(train_panoptic_head=True)).  The reference defines none (its model.py:4 leaves the
+    head out), so this is the DETR paper's: sigmoid focal loss (alpha .25, gamma 2; TFA sigmoid_focal_crossentropy from logits,
+    averaged over the pixels) + DICE, per matched (object m -> query n) pair of the last decoder layer's assignment
+    (``MatchingLoss.last_match``; masks are not part of the matching cost), summed over the objects and divided by
+    max(num_objects, 1), times ``mask_weight``.
+
+    ``call(masks_pred [B,N,P], masks [B,M,P] (or [B,M,h,w]), match int32 [B,M], num_objects int32 [B])`` -> loss [B].  When a
+    Tape is recording, the kernel's gradient (``loss_scale`` x dloss/dlogits, zero rows for unmatched queries) is registered."""
+
+    def __init__(self, mask_weight=1.0, name="MaskLoss", **kwargs):
+        super().__init__(name=name, **kwargs)
+        self.mask_weight = float(mask_weight)
+        self.loss_scale = 1.0
+        self.built = True
+
+    @staticmethod
+    def check_targets(masks, B: int, M: int, P: int) -> torch.Tensor:
+        if masks is None:
+            raise ValueError(f"train_panoptic_head needs inputs['masks'] ([B, M, h, w] or [B, M, h*w] with B={B}, M={M}, h*w={P})")
+        shape = tuple(masks.shape)
+        if not (len(shape) in (3, 4) and shape[:2] == (B, M) and math.prod(shape[2:]) == P):
+            raise ValueError(f"inputs['masks'] has shape {shape}; expected [B, M, h, w] or [B, M, h*w] with B={B}, M={M}, h*w={P}")
+        return masks
+
+    def call(self, masks_pred, masks, match, num_objects, training=False):
+        B, N, P = masks_pred.shape
+        tape = current_tape()
+        loss, dlogits = K.mask_loss(masks_pred, masks.reshape(B, -1, P), match, num_objects, self.mask_weight, self.loss_scale,
+                                    want_grads=tape is not None)
+        if tape is not None:
+            tape.record([loss], [masks_pred], lambda g: (dlogits,))
+        return loss
+
+    def __call__(self, masks_pred, masks, match, num_objects, training=False, **kw):
+        return self.call(masks_pred, masks, match, num_objects, training=training)

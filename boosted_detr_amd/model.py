@@ -24,6 +24,16 @@ def _prepare_targets(model, inputs):
     return [category, attribute, bbox, num_objects]
 
 
+def _prepare_masks(inputs, B: int, M: int) -> torch.Tensor:
+    """inputs["masks"]: float targets in [0, 1] on the head's 23 x 23 output grid, [B, M, 23, 23] or [B, M, 529], row m aligned with
+    bbox row m (rows m >= num_objects[b] are ignored)."""
+    from .panoptic_neck import MASK_GRID
+    masks = losses_and_metrics.MaskLoss.check_targets(inputs.get("masks"), B, M, MASK_GRID * MASK_GRID)
+    if not isinstance(masks, torch.Tensor):
+        masks = np.asarray(masks, np.float32)
+    return to_device(masks).reshape(B, M, MASK_GRID * MASK_GRID).contiguous()
+
+
 def _image(inputs):
     img = inputs["image"]
     return to_device(img if isinstance(img, torch.Tensor) else np.asarray(img, np.float32))
@@ -35,7 +45,9 @@ class DETR(Model):
                  classification_only=False, attribute_weight=1.0, name="DETR", **kwargs):
         seed = int(kwargs.pop("seed", 0))
         backbone_name = kwargs.pop("backbone_name", "ResNet")      # reference default is EfficientNet (out of scope)
-        with_panoptic_head = bool(kwargs.pop("with_panoptic_head", False))
+        train_panoptic_head = bool(kwargs.pop("train_panoptic_head", False))
+        with_panoptic_head = bool(kwargs.pop("with_panoptic_head", False)) or train_panoptic_head
+        mask_weight = float(kwargs.pop("mask_weight", 1.0))
         super().__init__(name=name, seed=seed)                      # pad_value / oov_value etc. are swallowed like the reference's **kwargs
         category_weight = box_weight = exist_weight = None
         if classification_only:
@@ -72,15 +84,22 @@ class DETR(Model):
         self.loss_fn = losses_and_metrics.MatchingLoss(category_weight=category_weight, box_weight=box_weight,
                                                        attribute_weight=attribute_weight, exist_weight=exist_weight, name="MatchingLoss")
         # BASELINE.json configs[4]'s mask head.  The reference constructs neither layer (model.py:4 has the import commented out;
-        # num_panoptic_heads / panoptic_dim are accepted and unused), so the head is opt-in, forward-only and frozen: it runs on the
-        # features the last call left behind (`panoptic_masks`), outside the training step's tape and arithmetic policy.
-        self.PanopticAttention = self.PanopticNeck = None
+        # num_panoptic_heads / panoptic_dim are accepted and unused), so the head is opt-in.  with_panoptic_head alone: forward-only
+        # and frozen, it runs on the features the last call left behind (`panoptic_masks`), outside the training step's tape and
+        # arithmetic policy.  train_panoptic_head (implies with_panoptic_head): the head runs inside call(training=True) on the
+        # image encoding after the decoder loop, on the tape, and MaskLoss (weight mask_weight) joins the loss vector.
+        self.train_panoptic_head = train_panoptic_head
+        self.mask_weight = mask_weight
+        self.PanopticAttention = self.PanopticNeck = self.MaskLoss = None
         if with_panoptic_head:
             from . import panoptic_neck
             self.PanopticAttention = transformers.PanopticAttention(num_attention_heads=num_panoptic_heads, hidden_dim=panoptic_dim, seed=seed)
             self.PanopticNeck = panoptic_neck.PanopticNeck(seed=seed)
-            self.PanopticAttention.trainable = False
-            self.PanopticNeck.trainable = False
+            if train_panoptic_head:
+                self.MaskLoss = losses_and_metrics.MaskLoss(mask_weight=mask_weight, name="MaskLoss")
+            else:
+                self.PanopticAttention.trainable = False
+                self.PanopticNeck.trainable = False
         self._panoptic_inputs = None
 
     def panoptic_masks(self):
@@ -104,6 +123,8 @@ class DETR(Model):
         image = _image(inputs)
         if training:
             y_true = _prepare_targets(self, inputs)
+            if self.train_panoptic_head:
+                masks = _prepare_masks(inputs, image.shape[0], y_true[2].shape[1])
 
         encoder_features = self.EncoderBackbone([image], training=training)
         encoder_features = self.BackboneNeck([encoder_features], training=training)
@@ -127,8 +148,15 @@ class DETR(Model):
 
         if self.PanopticAttention is not None:
             self._panoptic_inputs = (image_encoding, decoder_features, positional_encoding.value)
+        mask_loss = None
+        if training and self.train_panoptic_head:
+            masks_pred = self.PanopticNeck([self.PanopticAttention([image_encoding, decoder_features, positional_encoding.value], training=training)],
+                                           training=training)
+            self.MaskLoss.mask_weight, self.MaskLoss.loss_scale = self.mask_weight, self.loss_fn.loss_scale
+            mask_loss = self.MaskLoss(masks_pred, masks, self.loss_fn.last_match, y_true[3], training=training)
+            self._loss_roots.append(mask_loss)
         if training:
-            self._register(loss_terms, metrics_i)
+            self._register(loss_terms, metrics_i, mask_loss)
             return y_pred_i
 
         cat_preds = self.CategoryPredictionHead([decoder_features], training=training)
@@ -137,17 +165,22 @@ class DETR(Model):
         category, attributes = self.InverseTokenization([cat_preds, attribute_preds], training=training)
         return category, attributes, box_coord_preds
 
-    def _register(self, loss_terms, metrics_i):
+    def _register(self, loss_terms, metrics_i, mask_loss=None):
         """model.py:206-221.  Per-learner loss vectors are kept as a list (summed on the host when
-        logged) instead of being added on the device: the sum is never needed by the gradient."""
+        logged) instead of being added on the device: the sum is never needed by the gradient.
+        The panoptic head's mask loss (train_panoptic_head) is one more loss term and the Mask_Loss metric."""
         for k, name in enumerate(["loss", "Category_Loss", "Attribute_Loss", "Box_Loss", "Existence_Loss"]):
             terms = [t[k] for t in loss_terms]
             if name == "loss":
                 for t in terms:
                     self.add_loss(t)
+                if mask_loss is not None:
+                    self.add_loss(mask_loss)
             else:
                 self.add_metric(terms, name)
         self.add_metric([metrics_i[0]], "IOU")
+        if mask_loss is not None:
+            self.add_metric([mask_loss], "Mask_Loss")
 
     def citation(self):
         print("DETR-like model for object detection and fine-grained classification, after 'End-to-end Object Detection "

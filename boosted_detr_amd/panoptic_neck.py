@@ -1,22 +1,124 @@
-"""Panoptic head, forward only (drop-in for /root/reference/ModelComponents/panoptic_neck.py:8-186; its attention
-input comes from transformers.PanopticAttention, transformers.py:460-559).
+"""Panoptic head (drop-in for /root/reference/ModelComponents/panoptic_neck.py:8-186; its attention input comes from
+transformers.PanopticAttention, transformers.py:460-559).
 
-The reference never wires these layers into a model (the import is commented out, model.py:4) and never trains them,
-so there is no loss or gradient to reproduce: this is BASELINE.json configs[4]'s "mask head" as a throughput path.
+The reference never wires these layers into a model (the import is commented out, model.py:4) and never trains them.  Here
+the head runs frozen and forward-only by default (``DETR.panoptic_masks``); with ``DETR(train_panoptic_head=True)`` it runs
+inside the training step on the Tape and learns from ``MaskLoss`` (losses_and_metrics.py).
 Channel counts shrink / grow by 2/3 and 3/2 (100 -> 66 -> 44 -> 29 ...), so tensors carry their TRUE channel count
 next to a storage width padded to a multiple of 4 (zeros): ``(tensor [B,H,W,ld], C)``.  Convolutions run on the MFMA
-implicit-GEMM kernels with zero-padded weights; Conv2DTranspose(k=2, stride 1, valid) is the full-padding convolution
-with the taps flipped and the in/out axes of the Keras kernel swapped."""
+implicit-GEMM kernels with zero-padded weights, packed from the Keras-layout variables on the device at every forward
+(a pure copy; no host round trip inside a step); Conv2DTranspose(k=2, stride 1, valid) is the full-padding convolution
+with the taps flipped and the in/out axes of the Keras kernel swapped.
+
+Every op below records its backward on the current Tape (when one is recording).  Parameter gradients go through
+``ops.GradSink`` (the conv weight gradients inside ``side_task``), activation gradients return through the Tape."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
 from . import kernels as K
-from .engine import WEIGHTS_VERSION, Layer, to_device
+from .engine import Layer, current_tape, side_task
+from .ops import GradSink, _own, _rec
 
 LN_EPS = 1e-3            # tf.keras.layers.LayerNormalization default
 LEAKY = 0.01             # ReLU(negative_slope=.01)
+MASK_GRID = 23           # output grid: Resizing(96, 96) -> ... -> ConvOut(k=3, s=4): 94 -> 23
+
+
+def _view(x: torch.Tensor, shape) -> torch.Tensor:
+    """x.view(shape) linked to x on the Tape (the Tape keys on tensor identity)."""
+    y = x.view(shape)
+    _rec([y], [x], lambda g: (g.reshape(x.shape),))
+    return y
+
+
+def conv_packed(x: torch.Tensor, kernel, bias, transpose: bool, stride: int, pad: int) -> torch.Tensor:
+    """Conv2D (HWIO kernel) / Conv2DTranspose (as a pad-1 conv with flipped taps) of a channel-padded NHWC tensor."""
+    w, b = K.conv_weight_pack(kernel.value, bias.value, transpose)
+    N, H, W, ld = x.shape
+    assert w.shape[-1] == ld, (w.shape, x.shape)
+    geom = K.ConvGeom(N, H, W, ld, w.shape[0], w.shape[1], w.shape[2], stride, pad)
+    y, _ = K.conv2d_fwd(x, w, b, geom, K.ACT_NONE)
+    if current_tape() is None:
+        return y
+
+    def backward(g):
+        g = g.contiguous()
+        if kernel.needs_grad or bias.needs_grad:
+            def param_grads(g=g):
+                dw = K.conv2d_bwd_weight(x, g, geom)
+                db = K.colsum(g.view(-1, g.shape[-1]))
+                sk = GradSink(kernel) if kernel.needs_grad else None
+                sb = GradSink(bias) if bias.needs_grad else None
+                K.conv_weight_unpack(dw, db, kernel.keras_shape, transpose, sk.buf if sk else None, sb.buf if sb else None)
+                for sink in (sk, sb):
+                    if sink is not None:
+                        sink.commit()
+            side_task(param_grads, x, g, w)
+        return (_own(K.conv2d_bwd_data(g, w, geom)),)
+
+    _rec([y], [x], backward)
+    return y
+
+
+def layernorm_act(y: torch.Tensor, C: int, gamma, beta, slope: float) -> torch.Tensor:
+    out = K.layernorm_act(y, C, gamma.value, beta.value, LN_EPS, slope)
+    if current_tape() is None:
+        return out
+
+    def backward(g):
+        sg, sb = GradSink(gamma), GradSink(beta)
+        dy, _, _ = K.layernorm_act_bwd(y, C, gamma.value, beta.value, LN_EPS, slope, g.contiguous(), dgamma=sg.buf, dbeta=sb.buf)
+        sg.commit()
+        sb.commit()
+        return (_own(dy),)
+
+    _rec([out], [y], backward)
+    return out
+
+
+def resize_bilinear(x: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    y = K.resize_bilinear(x, H, W)
+    _rec([y], [x], lambda g: (_own(K.resize_bilinear_bwd(g.contiguous(), x.shape[1], x.shape[2])),))
+    return y
+
+
+def concat(parts):
+    """Concatenate (tensor, C) pairs along the TRUE channels into one padded tensor; the backward slices the columns back out."""
+    C = sum(c for _, c in parts)
+    t0 = parts[0][0]
+    out = torch.empty(tuple(t0.shape[:-1]) + (K.pad4(C),), dtype=torch.float32, device=t0.device)
+    if K.pad4(C) != C:
+        K.zero_(out)
+    col = 0
+    for t, c in parts:
+        assert t.shape[:-1] == t0.shape[:-1], (t.shape, t0.shape)
+        K.copy_cols(t, c, out, col)
+        col += c
+    if current_tape() is None:
+        return out, C
+
+    def backward(g):
+        g = g.contiguous()
+        gins, col = [], 0
+        for t, c in parts:
+            d = K.empty(*t.shape, like=g)
+            if t.shape[-1] != c:
+                K.zero_(d)
+            gins.append(_own(K.copy_cols(g, c, d, 0, src_col0=col)))
+            col += c
+        return tuple(gins)
+
+    _rec([out], [t for t, _ in parts], backward)
+    return out, C
+
+
+def nhwc_to_nchw(y: torch.Tensor, C: int) -> torch.Tensor:
+    N, H, W, ld = y.shape
+    out = K.nhwc_to_nchw(y, C)
+    _rec([out], [y], lambda g: (_own(K.nchw_to_nhwc(g.contiguous(), H, W, ld)),))
+    return out
 
 
 class _ConvLNBlock(Layer):
@@ -52,25 +154,6 @@ class _ConvLNBlock(Layer):
             self.convs.append((kernel, bias, gamma, beta, f, g))
             f = g
         self.out_channels = f
-        self._packed = None
-
-    def _weights(self):
-        """OHWI kernels with both channel axes zero-padded to multiples of 4 (rebuilt when the weights change)."""
-        if self._packed is None or self._packed[0] != WEIGHTS_VERSION[0]:
-            packed = []
-            for kernel, bias, gamma, beta, f, g in self.convs:
-                k = kernel.numpy()
-                if self.transpose:
-                    k = np.transpose(k[::-1, ::-1], (2, 0, 1, 3))      # [kh,kw,out,in] flipped -> [out,kh,kw,in]
-                else:
-                    k = np.transpose(k, (3, 0, 1, 2))                    # HWIO -> OHWI
-                w = np.zeros((K.pad4(g), 2, 2, K.pad4(f)), np.float32)
-                w[:g, :, :, :f] = k
-                b = np.zeros(K.pad4(g), np.float32)
-                b[:g] = bias.numpy()
-                packed.append((to_device(w), to_device(b)))
-            self._packed = (WEIGHTS_VERSION[0], packed)
-        return self._packed[1]
 
     def __call__(self, inputs, training=False, **kw):
         x, C = inputs[0]
@@ -82,11 +165,9 @@ class _ConvLNBlock(Layer):
 
     def call(self, inputs, training=False):
         x, C = inputs[0]
-        for (kernel, bias, gamma, beta, f, g), (w, b) in zip(self.convs, self._weights()):
-            N, H, W, ld = x.shape
-            geom = K.ConvGeom(N, H, W, ld, K.pad4(g), 2, 2, 1, 1 if self.transpose else 0)
-            y, _ = K.conv2d_fwd(x, w, b, geom, K.ACT_NONE)
-            x = K.layernorm_act(y, g, gamma.value, beta.value, LN_EPS, LEAKY)
+        for kernel, bias, gamma, beta, f, g in self.convs:
+            y = conv_packed(x, kernel, bias, self.transpose, 1, 1 if self.transpose else 0)
+            x = layernorm_act(y, g, gamma, beta, LEAKY)
         return x, self.out_channels
 
 
@@ -116,41 +197,17 @@ class PanopticNeck(Layer):
         self.UpscaleBlock_0, self.UpscaleBlock_1 = mk(UpscaleBlock, 3, "UpscaleBlock_0"), mk(UpscaleBlock, 2, "UpscaleBlock_1")
         self.UpscaleBlock_2, self.UpscaleBlock_3 = mk(UpscaleBlock, 1, "UpscaleBlock_2"), mk(UpscaleBlock, 2, "UpscaleBlock_3")
         self.DownscaleBlock_4 = mk(DownscaleBlock, 1, "DownscaleBlock_4")
-        self._conv_out = None
 
-    @staticmethod
-    def _concat(parts):
-        """Concatenate (tensor, C) pairs along the TRUE channels into one padded tensor."""
-        C = sum(c for _, c in parts)
-        t0 = parts[0][0]
-        out = torch.empty(tuple(t0.shape[:-1]) + (K.pad4(C),), dtype=torch.float32, device=t0.device)
-        if K.pad4(C) != C:
-            K.zero_(out)
-        col = 0
-        for t, c in parts:
-            assert t.shape[:-1] == t0.shape[:-1], (t.shape, t0.shape)
-            K.copy_cols(t, c, out, col)
-            col += c
-        return out, C
-
-    def _conv_out_weights(self, cin: int):
-        if self._conv_out is None or self._conv_out[0] != WEIGHTS_VERSION[0]:
-            k = np.transpose(self.ConvOut_kernel.numpy(), (3, 0, 1, 2))
-            w = np.zeros((K.pad4(self.num_obj), 3, 3, K.pad4(cin)), np.float32)
-            w[:self.num_obj, :, :, :cin] = k
-            b = np.zeros(K.pad4(self.num_obj), np.float32)
-            b[:self.num_obj] = self.ConvOut_bias.numpy()
-            self._conv_out = (WEIGHTS_VERSION[0], to_device(w), to_device(b))
-        return self._conv_out[1], self._conv_out[2]
+    _concat = staticmethod(concat)
 
     def call(self, inputs, training=False):
         features = inputs[0]                                   # [B, rows, cols, num_obj, dim]
         B, r, c = features.shape[:3]
         C = int(np.prod(features.shape[3:]))
-        x = features.reshape(B, r, c, C)                       # ReshapeInput
+        x = _view(features.contiguous(), (B, r, c, C))         # ReshapeInput
         if K.pad4(C) != C:
-            x, _ = self._concat([(x.contiguous(), C)])
-        orig = (K.resize_bilinear(x.contiguous(), 96, 96), C)  # Resize
+            x, _ = self._concat([(x, C)])
+        orig = (resize_bilinear(x, 96, 96), C)                 # Resize
         d0 = self.DownscaleBlock_0([orig])
         d1 = self.DownscaleBlock_1([d0])
         d2 = self.DownscaleBlock_2([d1])
@@ -169,8 +226,5 @@ class PanopticNeck(Layer):
             self.ConvOut_kernel = self.add_weight("kernel", (3, 3, cin, self.num_obj), "glorot_uniform")
             self.ConvOut_bias = self.add_weight("bias", (self.num_obj,), "zeros")
             self.name = keep
-        w, b = self._conv_out_weights(cin)
-        N, H, W, ld = feats.shape
-        geom = K.ConvGeom(N, H, W, ld, K.pad4(self.num_obj), 3, 3, 4, 0)
-        y, _ = K.conv2d_fwd(feats, w, b, geom, K.ACT_NONE)     # ConvOut: k=3, strides=4, valid
-        return K.nhwc_to_nchw(y, self.num_obj)                 # TransposeOut + FlattenDim: [B, num_obj, OH*OW]
+        y = conv_packed(feats, self.ConvOut_kernel, self.ConvOut_bias, False, 4, 0)     # ConvOut: k=3, strides=4, valid
+        return nhwc_to_nchw(y, self.num_obj)                   # TransposeOut + FlattenDim: [B, num_obj, OH*OW]

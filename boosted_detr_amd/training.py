@@ -667,7 +667,8 @@ class Model(Layer):
         fresh capture (after two eager steps) - never a replay that keeps training frozen layers or updates a retired buffer."""
         from . import transformers
         lf = getattr(self, "loss_fn", None)
-        loss = tuple(getattr(lf, k, None) for k in ("category_weight", "attribute_weight", "box_weight", "exist_weight", "loss_scale"))
+        loss = tuple(getattr(lf, k, None) for k in ("category_weight", "attribute_weight", "box_weight", "exist_weight", "loss_scale")) + \
+            (getattr(self, "mask_weight", None),)
         opt = self.optimizer
         hyper = (opt.momentum, opt.nesterov, opt.clipnorm) if opt is not None else ()
         dp = self._dp

@@ -275,11 +275,14 @@ class DecoderPrep(Layer):
 
 
 class PanopticAttention(Layer):
-    """transformers.py:460-559 ("not tested" in the reference, line 13), forward only.  Partial multi-head attention that
+    """transformers.py:460-559 ("not tested" in the reference, line 13).  Partial multi-head attention that
     emits one image-sized map per decoder box: value / key / query are ALL projected from the flattened image encoding
     (the reference feeds ``value`` to the key and query projections, lines 535-536 - reproduced), one softmax over the
     full num_heads*key_dim width (no head split), value width = num_heads * num_obj, LayerNormalization (eps 1e-3) of the
-    result, reshaped to [B, rows, cols, num_obj, num_heads].  Dense layers use the Keras default glorot_uniform."""
+    result, reshaped to [B, rows, cols, num_obj, num_heads].  Dense layers use the Keras default glorot_uniform.
+
+    When a Tape is recording (DETR(train_panoptic_head=True)) the backward runs LayerNorm backward, softmax backward and batched
+    GEMMs; the three projections read the same ``value``, so their input gradients are summed in the GEMM epilogues."""
 
     def __init__(self, num_attention_heads, hidden_dim, name="PanopticAttention", **kwargs):
         super().__init__(name=name, **kwargs)
@@ -307,14 +310,58 @@ class PanopticAttention(Layer):
         B, r, c, E = image_encoding.shape
         T = r * c
         value = image_encoding.reshape(B * T, E).contiguous()
-        v = K.linear_fwd(value, self.ValueProjection.kernel.value, self.ValueProjection.bias.value)      # [B*T, h*num_obj]
-        k = K.linear_fwd(value, self.KeyProjection.kernel.value, self.KeyProjection.bias.value)          # [B*T, h*kd]
-        q = K.linear_fwd(value, self.QueryProjection.kernel.value, self.QueryProjection.bias.value)
+        tape = ops.current_tape()
+        if tape is not None:
+            tape.record([value], [image_encoding], lambda g: (g.reshape(image_encoding.shape),))
+        Vp, Kp, Qp = self.ValueProjection, self.KeyProjection, self.QueryProjection
+        v = K.linear_fwd(value, Vp.kernel.value, Vp.bias.value)      # [B*T, h*num_obj]
+        k = K.linear_fwd(value, Kp.kernel.value, Kp.bias.value)      # [B*T, h*kd]
+        q = K.linear_fwd(value, Qp.kernel.value, Qp.bias.value)
         D, Dv = k.shape[1], v.shape[1]
+        scale = 1.0 / math.sqrt(float(self.key_dim))
         s = K.empty(B, T, T, like=value)
         K.gemm_raw(T, T, D, q, D, True, k, D, True, s, T, nb0=B, sa=(T * D, 0), sb=(T * D, 0), sc=(T * T, 0))       # MatMul_1
-        p = K.softmax_rows_fwd(s.view(-1, T), 1.0 / math.sqrt(float(self.key_dim)), out=s.view(-1, T))               # Divide + Softmax
+        p = K.softmax_rows_fwd(s.view(-1, T), scale, out=s.view(-1, T))                                             # Divide + Softmax
         o = K.empty(B, T, Dv, like=value)
         K.gemm_raw(T, Dv, T, p, T, True, v, Dv, False, o, Dv, nb0=B, sa=(T * T, 0), sb=(T * Dv, 0), sc=(T * Dv, 0))  # MatMul_2
-        o = K.layernorm_act(o, Dv, self.ln_gamma.value, self.ln_beta.value, LN_EPS, 1.0, ld_out=Dv)
-        return o.view(B, r, c, self.num_obj, Dv // self.num_obj)                                                       # ReshapeOutput
+        out = K.layernorm_act(o, Dv, self.ln_gamma.value, self.ln_beta.value, LN_EPS, 1.0, ld_out=Dv)
+        y = out.view(B, r, c, self.num_obj, Dv // self.num_obj)                                                      # ReshapeOutput
+        if tape is None:
+            return y
+
+        def backward(g_out):
+            g = g_out.contiguous().view(B * T, Dv)
+            sg, sb = ops.GradSink(self.ln_gamma), ops.GradSink(self.ln_beta)
+            do, _, _ = K.layernorm_act_bwd(o, Dv, self.ln_gamma.value, self.ln_beta.value, LN_EPS, 1.0, g, dgamma=sg.buf, dbeta=sb.buf)
+            sg.commit()
+            sb.commit()
+            # dP = dO V^T ; dV = P^T dO ; dS = softmax backward ; dQ = dS K ; dK = dS^T Q  (per image)
+            dp = K.empty(B, T, T, like=value)
+            K.gemm_raw(T, T, Dv, do, Dv, True, v, Dv, True, dp, T, nb0=B, sa=(T * Dv, 0), sb=(T * Dv, 0), sc=(T * T, 0), grad=True)
+            dv = K.empty(B * T, Dv, like=value)
+            K.gemm_raw(T, Dv, T, p, T, False, do, Dv, False, dv, Dv, nb0=B, sa=(T * T, 0), sb=(T * Dv, 0), sc=(T * Dv, 0), grad=True)
+            ds = K.softmax_rows_bwd(p, dp.view(-1, T), scale, out=dp.view(-1, T))
+            dq = K.empty(B * T, D, like=value)
+            K.gemm_raw(T, D, T, ds, T, True, k, D, False, dq, D, nb0=B, sa=(T * T, 0), sb=(T * D, 0), sc=(T * D, 0), grad=True)
+            dk = K.empty(B * T, D, like=value)
+            K.gemm_raw(T, D, T, ds, T, False, q, D, False, dk, D, nb0=B, sa=(T * T, 0), sb=(T * D, 0), sc=(T * D, 0), grad=True)
+            pairs = [(dv, Vp), (dk, Kp), (dq, Qp)]
+            if any(d.kernel.needs_grad or d.bias.needs_grad for _, d in pairs):
+                def param_grads():
+                    for gy, d in pairs:
+                        if d.kernel.needs_grad:
+                            sk = ops.GradSink(d.kernel)
+                            K.linear_bwd_weight(gy, value, dw=sk.buf, prezeroed=sk.mode == "direct")
+                            sk.commit()
+                        if d.bias.needs_grad:
+                            sbias = ops.GradSink(d.bias)
+                            K.colsum(gy, out=sbias.buf, prezeroed=sbias.mode == "direct")
+                            sbias.commit()
+                ops.side_task(param_grads, value, dv, dk, dq)
+            dvalue = K.linear_bwd_data(dv, Vp.kernel.value)
+            K.linear_bwd_data(dk, Kp.kernel.value, dx=dvalue, accumulate=True)
+            K.linear_bwd_data(dq, Qp.kernel.value, dx=dvalue, accumulate=True)
+            return (ops._own(dvalue),)
+
+        tape.record([y], [value], backward)
+        return y

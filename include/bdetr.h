@@ -148,8 +148,9 @@ int bdetr_conv2d_fwd(const float* x, const float* w, const float* bias, float* y
 /* number of partial-statistics rows bdetr_conv2d_fwd writes for this geometry */
 int bdetr_conv2d_fwd_stat_chunks(const bdetr_conv_desc* d);
 /* dx[N,H,W,C] (+)= conv_transpose(dy, w).  accumulate!=0 adds into dx (residual merge).
- * For stride>1 only 1x1/pad 0 is supported (Keras ResNet-50 v1 strides its 1x1s) and
- * the untouched pixels of dx are written as zero unless accumulate. */
+ * For stride>1 only 1x1/pad 0 (Keras ResNet-50 v1 strides its 1x1s) and pad 0 with R, S <= stride (taps that do not
+ * overlap: panoptic_neck.py:44's 3x3 stride-4 ConvOut) are supported; the untouched pixels of dx are written as zero
+ * unless accumulate. */
 int bdetr_conv2d_bwd_data(const float* dy, const float* w, float* dx,
                           const bdetr_conv_desc* d, int accumulate, void* stream);
 /* dw[K,R,S,C] = sum over pixels; split-K partials are combined with fp32 atomics, so the
@@ -494,7 +495,7 @@ int bdetr_rowchain_partial_rows(int64_t M);
 int bdetr_rowchain_pack_weights(const int64_t* table, int n, int* overflow_flag, void* stream);
 
 /* ------------------------------------------------------------------------
- * Panoptic head (forward only - the reference never wires it into a loss):
+ * Panoptic head (the forward - the reference never wires it into a loss; its training: next block):
  * panoptic_neck.py:20-21 Resizing (bilinear, half-pixel centres), 118-121 / 164-167 channel LayerNormalization
  * (eps 1e-3) + ReLU(negative_slope), 33-47 Concatenate / transpose; transformers.py:519 LayerNormalization.
  * Channel counts of the head are arbitrary (66, 44, 29 ...): tensors are stored with the channel dimension
@@ -509,6 +510,36 @@ int bdetr_layernorm_act_fwd(const float* x, int64_t rows, int C, int ldx, const 
                             float eps, float slope, float* out, int ldo, void* stream);
 int bdetr_copy_cols(const float* src, int64_t rows, int C, int ld_src, float* dst, int ld_dst, int dst_col0, void* stream);
 int bdetr_nhwc_to_nchw(const float* in, int B, int P, int C, int ld_in, float* out, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Panoptic head training (DETR(train_panoptic_head=True)): the adjoints of the pieces above, the device pack of the head's
+ * Keras-layout conv variables, and a mask loss.  The pack replaces a host-side repack of the Conv2D /
+ * Conv2DTranspose kernels of panoptic_neck.py:91-186 (a pure copy); the rest adds what the reference lacks: it never trains
+ * these layers and defines no mask loss (its model.py:4), so the loss is the DETR paper's
+ * panoptic-head loss (sigmoid focal, alpha .25 gamma 2 as TFA sigmoid_focal_crossentropy, averaged over the pixels,
+ * + DICE) on the matched queries.  Deterministic: no float atomics.
+ *   layernorm_act_bwd   adjoint of layernorm_act (x = the forward's input, dout [rows][ldo]): dx [rows][ldx] (0 beyond C),
+ *                       dgamma / dbeta [C]; part_g / part_b: workspaces of bdetr_layernorm_act_bwd_chunks(rows) x C floats
+ *   resize_bwd          adjoint of resize (dout [B,H,W,C] -> din [B,h,w,C]) as a gather over the output pixels, C % 4 == 0
+ *   nchw_to_nhwc        out[b][p][c] = in[b][c][p] for c < C, 0 for C <= c < ld_out (adjoint of nhwc_to_nchw)
+ *   conv_weight_pack    w [Kp][R][S][Cp] = Keras kernel HWIO [R][S][Cin][K] (transpose: the Conv2DTranspose kernel [R][S][K][Cin]
+ *                       with flipped taps), zeros beyond K / Cin; b [Kp] = bias, zeros beyond K
+ *   conv_weight_unpack  its adjoint: dkernel (Keras layout) / dbias [K] from the padded dw / db (either output may be null)
+ *   mask_loss           logits [B][N][P], masks [B][M][P], match int32 [B][M] (prediction per object, -1 none), num_objects [B]:
+ *                       row_loss [B][N] (focal + dice of the query's matched object, 0 unmatched; workspace), loss [B] =
+ *                       mask_weight * sum_n row_loss / max(n_b, 1), dlogits [B][N][P] = loss_scale * dloss / dlogits (null: none)
+ * ---------------------------------------------------------------------- */
+int bdetr_layernorm_act_bwd_chunks(int64_t rows);
+int bdetr_layernorm_act_bwd(const float* x, int64_t rows, int C, int ldx, const float* gamma, const float* beta, float eps, float slope,
+                            const float* dout, int ldo, float* dx, float* part_g, float* part_b, float* dgamma, float* dbeta, void* stream);
+int bdetr_resize_bilinear_nhwc_bwd(const float* dout, int B, int H, int W, int C, float* din, int h, int w, void* stream);
+int bdetr_nchw_to_nhwc(const float* in, int B, int P, int C, float* out, int ld_out, void* stream);
+int bdetr_conv_weight_pack(const float* kernel, const float* bias, int R, int S, int Cin, int K, int transpose, int Cp, int Kp,
+                           float* w, float* b, void* stream);
+int bdetr_conv_weight_unpack(const float* dw, const float* db, int R, int S, int Cin, int K, int transpose, int Cp,
+                             float* dkernel, float* dbias, void* stream);
+int bdetr_mask_loss(const float* logits, const float* masks, const int* match, const int* num_objects, int B, int M, int N, int P,
+                    float alpha, float gamma, float mask_weight, float loss_scale, float* row_loss, float* loss, float* dlogits, void* stream);
 
 /* ------------------------------------------------------------------------
  * K9  head activations (prediction_heads.py:44,60-62,111,127-129,180,197-199)
