@@ -276,6 +276,7 @@ int hwgrad_slices(int N, int H, int W, int C, int K) {
     static int enabled = -1;
     if (enabled < 0) { const char* e = getenv("BDETR_HWGRAD"); enabled = e ? atoi(e) : 0; }
     if (!enabled || K % BKO || C % BCI) return 0;
+    if (W + 2 < SP / 2) return 0;                                 // pad_advance() wraps at most two frame rows per 32-pixel stage: PW = W + 2 >= 16 (narrower maps gave wrong sums)
     const int XL = (W + 3 + SP - 1) / SP * SP;
     if (XL > MAX_XL) return 0;
     const long long Mp = (long long)N * (H + 2) * (W + 2);

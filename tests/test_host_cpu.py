@@ -375,3 +375,35 @@ def test_side_stream_tuning_schedule_has_a_fixed_length_and_keeps_the_fastest_ca
         assert placement["step_ms"] == {c: step_ms[c] for c in good}, placement
     else:
         assert not sel, sel
+
+
+def test_every_kernel_switch_is_forced_by_some_test():
+    """Each getenv("BDETR_...") in csrc/*.hip selects a compiled variant or a code path: every name must be set by some test (the
+    forced-variant children of tests/test_variants_gpu.py, mostly) or be listed here with the reason it needs none.  A new A/B
+    switch fails this test until a test forces it."""
+    import glob
+    import re
+    needs_no_variant_test = {
+        "BDETR_SGEMM_DBG": "diagnostic builds only (compiled under BDETR_SGEMM_DIAG)",
+        "BDETR_GEMM_PRECISION": "initial value of the policy word every precision test sets through bdetr_set_gemm_precision",
+        "BDETR_WGRAD_WANT": "split-K occupancy target: changes the slice count, no kernel",
+        "BDETR_WGRAD_WANT_3X3": "split-K occupancy target of the im2col layers: no kernel",
+        "BDETR_WGRAD_WANT_64": "split-K occupancy target of the 64x64 3x3 layers: no kernel",
+        "BDETR_WGRAD_MINSTAGES": "lower bound of K-steps per split-K slice: no kernel",
+        "BDETR_ZERO_MEMSET": "set by tests/test_training_gpu.py (hipMemsetAsync instead of the zero kernel)",
+    }
+    names = set()
+    for path in glob.glob(os.path.join(ROOT, "boosted_detr_amd", "csrc", "*.hip")):
+        with open(path) as f:
+            names |= set(re.findall(r'getenv\("(BDETR_[A-Z0-9_]+)"\)', f.read()))
+    assert len(names) >= 15, sorted(names)                       # the scan itself still finds the switches
+    tests = ""
+    for path in glob.glob(os.path.join(ROOT, "tests", "*.py")):
+        if os.path.basename(path) != "test_host_cpu.py":
+            with open(path) as f:
+                tests += f.read()
+    forced = {n for n in names if re.search(r'["\']%s["\']\s*:|\b%s\s*=' % (n, n), tests)}
+    stale = sorted(set(needs_no_variant_test) - names)
+    assert not stale, f"allow-list entries without a getenv in csrc: {stale}"
+    missing = sorted(names - forced - set(needs_no_variant_test))
+    assert not missing, f"kernel switches no test forces: {missing}"
