@@ -78,7 +78,7 @@ def __getattr__(name):
     if name == "BoostedDETR":
         from .boosted_model import BoostedDETR
         return BoostedDETR
-    if name in ("SGD", "CosineDecayRestarts", "ModelCheckpoint", "TerminateOnNaN", "TensorBoard", "latest_checkpoint"):
+    if name in ("SGD", "AdamW", "Adam", "CosineDecayRestarts", "ModelCheckpoint", "TerminateOnNaN", "TensorBoard", "latest_checkpoint"):
         from . import training
         return getattr(training, name)
     raise AttributeError(name)

@@ -190,6 +190,7 @@ SIGNATURES = {
     "bdetr_match_to_mask": (I, [P, P, I, I, I, P]),
     "bdetr_sgd_slab_elems": (I, []),
     "bdetr_sgd_nesterov_clipnorm": (I, [P, P, I, P, P, I, P, P, P, F, F, F, P, P]),
+    "bdetr_adamw_clipnorm": (I, [P, P, I, P, P, I, P, P, P, P, F, F, F, F, F, F, F, P, P]),
 }
 
 

@@ -1,6 +1,6 @@
 """The sliver of the Keras training runtime the reference's notebooks use: Model
 (compile / fit / train_step / test_step / save_weights / load_weights / summary), the SGD
-(Nesterov, per-tensor clipnorm) optimizer, CosineDecayRestarts, callbacks, and the
+(Nesterov, per-tensor clipnorm) and AdamW / Adam optimizers, CosineDecayRestarts, callbacks, and the
 data-parallel gradient all-reduce (RCCL through torch.distributed).
 
 Reference usage being mirrored: DETR_COCO.ipynb cells 26, 30, 35 (compile(optimizer=...),
@@ -54,24 +54,27 @@ class CosineDecayRestarts:
 # ----------------------------------------------------------------------------------------
 # optimizer
 # ----------------------------------------------------------------------------------------
-class SGD:
-    """Keras SGD(momentum, nesterov=True, clipnorm) as one fused multi-tensor HIP launch
-    (csrc/optim.hip).  Gradients live in one flat HBM buffer so the data-parallel all-reduce
-    moves a few large buckets."""
+class Optimizer:
+    """What the fused multi-tensor optimizers share: the flat 16-byte-aligned gradient buffer and its per-variable views (the
+    data-parallel all-reduce moves a few large buckets of it), one flat buffer per slot variable, the pointer / slab tables of the
+    kernels in csrc/optim.hip, gradient staging and the iteration counter.  A subclass names its slots, stages its per-step scalars
+    (``stage_lr``) and launches its entry point (``_launch``)."""
 
-    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None, name="SGD"):
+    SLOTS: tuple = ()        # (slot name, attribute a Variable parks its copy on while it is outside the trainable set)
+
+    def __init__(self, learning_rate, clipnorm=None):
         self.learning_rate = learning_rate
-        self.momentum = float(momentum)
-        self.nesterov = bool(nesterov)
         self.clipnorm = float(clipnorm) if clipnorm else 0.0
         self.iterations = 0
         self._built_for = None
-        if not self.nesterov and self.momentum != 0.0:
-            raise NotImplementedError("the hot path's optimizer is SGD(momentum, nesterov=True); plain momentum is not built")
 
     def current_lr(self) -> float:
         lr = self.learning_rate
         return float(lr(self.iterations)) if callable(lr) else float(lr)
+
+    def hyper(self) -> tuple:
+        """Every hyper-parameter a captured optimizer segment bakes in by value (Model._graph_env): a change forces a fresh capture."""
+        raise NotImplementedError
 
     def release(self) -> None:
         """Detach the variables of the previous build from this optimizer's flat buffer."""
@@ -81,37 +84,41 @@ class SGD:
 
     def build(self, variables: List[Variable]) -> None:
         dev = device()
-        # momentum survives a rebuild for every variable that stays trainable (Keras keeps one slot variable per weight:
-        # freezing the backbone and unfreezing it later, Boosted_DETR_COCO.ipynb cell 30, does not reset the others' velocity)
-        # The velocity also survives a freeze -> unfreeze cycle: a variable that leaves the trainable set parks a copy of its velocity on
-        # itself (v._momentum) and gets it back when it re-enters (keyed by the Variable object, not by id(): ids are reused after garbage
-        # collection).
-        old_mom = {}
-        for v, m in zip(getattr(self, "vars", []), getattr(self, "mom_views", [])):
-            old_mom[id(v)] = (v, m)
+        # slot variables (SGD's velocity, Adam's moments) survive a rebuild for every variable that stays trainable (Keras keeps one slot
+        # variable per weight: freezing the backbone and unfreezing it later, Boosted_DETR_COCO.ipynb cell 30, does not reset the others')
+        # They also survive a freeze -> unfreeze cycle: a variable that leaves the trainable set parks a copy of its slots on
+        # itself (v._momentum for SGD) and gets them back when it re-enters (keyed by the Variable object, not by id(): ids are reused
+        # after garbage collection).
+        old_views = getattr(self, "slot_views", {})
+        old = {}
+        for i, v in enumerate(getattr(self, "vars", [])):
+            old[id(v)] = (v, {slot: old_views[slot][i] for slot, _ in self.SLOTS})
         staying = {id(v) for v in variables}
-        for k, (v, m) in old_mom.items():
+        for k, (v, views) in old.items():
             if k not in staying:
-                v._momentum = m.clone()
+                for slot, park in self.SLOTS:
+                    setattr(v, park, views[slot].clone())
         self.release()
         self.vars = list(variables)
         sizes = [v.value.numel() for v in self.vars]
         offs = np.concatenate([[0], np.cumsum([(s + 3) // 4 * 4 for s in sizes])])      # 16-byte aligned slots
         self.flat_grad = torch.zeros(int(offs[-1]), dtype=torch.float32, device=dev)
-        self.flat_mom = torch.zeros(int(offs[-1]), dtype=torch.float32, device=dev)
         self.grad_views = [self.flat_grad[int(o): int(o) + s].view(v.value.shape) for o, s, v in zip(offs[:-1], sizes, self.vars)]
-        mom_views = [self.flat_mom[int(o): int(o) + s] for o, s in zip(offs[:-1], sizes)]
-        for v, m in zip(self.vars, mom_views):
-            have = old_mom.get(id(v))
-            if have is not None and have[0] is v and have[1].numel() == m.numel():
-                m.copy_(have[1])
-            elif getattr(v, "_momentum", None) is not None and v._momentum.numel() == m.numel():
-                m.copy_(v._momentum)                 # re-entering the trainable set: Keras kept its slot variable all along
-            v._momentum = None
-        self.mom_views = mom_views
-        ptrs = np.zeros((len(self.vars), 3), np.uint64)
+        self.flat_slots, self.slot_views = {}, {}
+        for slot, park in self.SLOTS:
+            flat = torch.zeros(int(offs[-1]), dtype=torch.float32, device=dev)
+            views = [flat[int(o): int(o) + s] for o, s in zip(offs[:-1], sizes)]
+            for v, m in zip(self.vars, views):
+                have = old.get(id(v))
+                if have is not None and have[0] is v and have[1][slot].numel() == m.numel():
+                    m.copy_(have[1][slot])
+                elif getattr(v, park, None) is not None and getattr(v, park).numel() == m.numel():
+                    m.copy_(getattr(v, park))          # re-entering the trainable set: Keras kept its slot variable all along
+                setattr(v, park, None)
+            self.flat_slots[slot], self.slot_views[slot] = flat, views
+        ptrs = np.zeros((len(self.vars), 2 + len(self.SLOTS)), np.uint64)
         for i, v in enumerate(self.vars):
-            ptrs[i] = (v.value.data_ptr(), self.grad_views[i].data_ptr(), mom_views[i].data_ptr())
+            ptrs[i] = (v.value.data_ptr(), self.grad_views[i].data_ptr()) + tuple(self.slot_views[slot][i].data_ptr() for slot, _ in self.SLOTS)
         slab = _lib.lib().bdetr_sgd_slab_elems()
         slab_tensor, slab_first = [], [0]
         for i, s in enumerate(sizes):
@@ -125,10 +132,14 @@ class SGD:
         self.d_slab_first = to_device(np.asarray(slab_first, np.int64), torch.int64)
         self.d_partial = torch.empty(self.nslabs, dtype=torch.float32, device=dev)
         self.d_norms = torch.empty(len(self.vars), dtype=torch.float32, device=dev)
-        self.d_lr = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._build_scalars(dev)
         for v, gv in zip(self.vars, self.grad_views):
             v.grad_buf, v._grad_flat = gv, self.flat_grad
         self._built_for = [id(v) for v in self.vars]
+
+    def _build_scalars(self, dev) -> None:
+        """Device memory for what changes per step (read by the kernel, so that a captured segment replays with this step's values)."""
+        raise NotImplementedError
 
     def stage_gradients(self, variables: List[Variable]) -> None:
         """Copy the per-variable gradients produced by the backward kernels into the flat buffer."""
@@ -144,21 +155,188 @@ class SGD:
             v.grad = gv
 
     def stage_lr(self) -> None:
-        self.d_lr.fill_(self.current_lr())
+        """Write this iteration's scalars to the device (the eager step, and before every graph replay)."""
+        raise NotImplementedError
+
+    def _launch(self, grad_scale: float, skip_flag: Optional[int], stream: int) -> None:
+        raise NotImplementedError
 
     def apply_gradients(self, grad_scale: float = 1.0, skip_flag: Optional[torch.Tensor] = None, stage_lr: bool = True) -> None:
         """skip_flag: device int32; while it is non-zero the update is not applied (the step's range guard).
         stage_lr=False: the caller already wrote this iteration's learning rate to the device (graph replays)."""
         if stage_lr:
             self.stage_lr()
-        st = torch.cuda.current_stream().cuda_stream
+        self._launch(float(grad_scale), skip_flag.data_ptr() if skip_flag is not None else None, torch.cuda.current_stream().cuda_stream)
+        bump_weights_version()
+        self.iterations += 1
+
+    # -- slot variables in checkpoints ----------------------------------------------------------------------------------
+    STATE_PREFIX = "optimizer_slot/"
+
+    def get_state(self, variables: Optional[List[Variable]] = None) -> Dict[str, np.ndarray]:
+        """'optimizer_slot/<slot>/<variable name>' -> array in the variable's Keras layout, for every variable this optimizer was built
+        for and, from `variables` (the model's), every one that is frozen right now and carries a parked copy of its slots."""
+        out = {}
+        for slot, park in self.SLOTS:
+            for v, m in zip(getattr(self, "vars", []), getattr(self, "slot_views", {}).get(slot, [])):
+                out[f"{self.STATE_PREFIX}{slot}/{v.name}"] = v._to_keras(m.detach().view(v.value.shape).cpu().numpy())
+            for v in variables or []:
+                key = f"{self.STATE_PREFIX}{slot}/{v.name}"
+                if key not in out and getattr(v, park, None) is not None:
+                    out[key] = v._to_keras(getattr(v, park).detach().view(v.value.shape).cpu().numpy())
+        return out
+
+    def set_state(self, state: Dict[str, np.ndarray], variables: Optional[List[Variable]] = None) -> None:
+        """Inverse of get_state.  A variable inside the built set takes the value into its slot; any other one of `variables` parks it
+        on itself, where the next build (first step, unfreeze) picks it up.  Keys of another optimizer's slots are an error."""
+        built = {id(v): i for i, v in enumerate(getattr(self, "vars", []))}
+        by_name = {v.name: v for v in list(getattr(self, "vars", [])) + list(variables or [])}
+        slots = dict(self.SLOTS)
+        for key, a in state.items():
+            if not key.startswith(self.STATE_PREFIX):
+                raise KeyError(f"not an optimizer slot: {key}")
+            slot, name = key[len(self.STATE_PREFIX):].split("/", 1)
+            if slot not in slots:
+                raise KeyError(f"{key}: {type(self).__name__} has no slot '{slot}' (its slots: {sorted(slots)})")
+            v = by_name.get(name)
+            if v is None or v.value is None:
+                raise KeyError(f"{key}: no such variable")
+            t = to_device(v._to_internal(np.asarray(a))).reshape(-1)
+            if id(v) in built:
+                self.slot_views[slot][built[id(v)]].copy_(t)
+            else:
+                setattr(v, slots[slot], t)
+
+
+class SGD(Optimizer):
+    """Keras SGD(momentum, nesterov=True, clipnorm) as one fused multi-tensor HIP launch
+    (csrc/optim.hip).  Gradients live in one flat HBM buffer so the data-parallel all-reduce
+    moves a few large buckets."""
+
+    SLOTS = (("momentum", "_momentum"),)
+
+    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None, name="SGD"):
+        super().__init__(learning_rate, clipnorm)
+        self.momentum = float(momentum)
+        self.nesterov = bool(nesterov)
+        if not self.nesterov and self.momentum != 0.0:
+            raise NotImplementedError("the hot path's optimizer is SGD(momentum, nesterov=True); plain momentum is not built")
+
+    def hyper(self) -> tuple:
+        return (self.momentum, self.nesterov, self.clipnorm)
+
+    @property
+    def flat_mom(self) -> torch.Tensor:
+        return self.flat_slots["momentum"]
+
+    @property
+    def mom_views(self) -> List[torch.Tensor]:
+        return self.slot_views["momentum"]
+
+    def _build_scalars(self, dev) -> None:
+        self.d_lr = torch.zeros(1, dtype=torch.float32, device=dev)
+
+    def stage_lr(self) -> None:
+        self.d_lr.fill_(self.current_lr())
+
+    def _launch(self, grad_scale, skip_flag, stream) -> None:
         _lib.check(_lib.lib().bdetr_sgd_nesterov_clipnorm(
             self.d_ptrs.data_ptr(), self.d_sizes.data_ptr(), len(self.vars), self.d_slab_tensor.data_ptr(),
             self.d_slab_first.data_ptr(), self.nslabs, self.d_partial.data_ptr(), self.d_norms.data_ptr(),
-            self.d_lr.data_ptr(), self.momentum, self.clipnorm, float(grad_scale),
-            skip_flag.data_ptr() if skip_flag is not None else None, st), "sgd")
-        bump_weights_version()
-        self.iterations += 1
+            self.d_lr.data_ptr(), self.momentum, self.clipnorm, grad_scale, skip_flag, stream), "sgd")
+
+
+class AdamW(Optimizer):
+    """tfa.optimizers.AdamW (both notebooks' cell 26) = Keras Adam (non-amsgrad) wrapped by TFA's DecoupledWeightDecayExtension, with
+    Keras' per-tensor clipnorm, as one fused multi-tensor HIP launch (bdetr_adamw_clipnorm, csrc/optim.hip).  For step
+    t = iterations + 1, per tensor:
+
+        g   <- g * grad_scale ;  g <- g * min(1, clipnorm / ||g||_2)      (as SGD; clipnorm 0 / None = off)
+        w   <- w - wd_t * w                                               (decoupled: NOT multiplied by lr; skipped for excluded tensors)
+        m   <- b1*m + (1-b1)*g ;  v <- b2*v + (1-b2)*g*g
+        lr_t = lr(t-1) * sqrt(1 - b2^t) / (1 - b1^t)
+        w   <- w - lr_t * m / (sqrt(v) + eps)                             (Keras' "epsilon hat" placement, eps = 1e-7)
+
+    TensorFlow-Addons is not importable here, so this is an assumption in the sense of SURVEY 8(c)-S; it is pinned independently:
+    with weight_decay_torch = wd / lr and a negligible epsilon, torch.optim.AdamW in fp64 is the same update (tests/test_adamw_cpu.py).
+
+    learning_rate and weight_decay: a float or a callable of the iteration count.  weight_decay is required and keyword-only (TFA
+    takes it first, Keras' Adam takes learning_rate first: no positional guess).  exclude_from_weight_decay: regular expressions
+    (re.search over variable names, TFA's argument of that name); default: every variable decays, as in TFA.
+    lr_t and wd_t are staged in HBM per step from `iterations` (bias correction folded in on the host, in double): a captured
+    optimizer segment replays with the right t, and a range-guard redo that rolls `iterations` back rolls the bias correction back."""
+
+    SLOTS = (("m", "_adam_m"), ("v", "_adam_v"))
+
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False, *, weight_decay,
+                 clipnorm=None, exclude_from_weight_decay=None, name="AdamW"):
+        super().__init__(learning_rate, clipnorm)
+        if amsgrad:
+            raise NotImplementedError("amsgrad is not built")
+        self.weight_decay = weight_decay
+        self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
+        self.exclude_from_weight_decay = list(exclude_from_weight_decay or [])
+        self.name = name
+
+    def hyper(self) -> tuple:
+        return (type(self).__name__, self.beta_1, self.beta_2, self.epsilon, self.clipnorm, tuple(self.exclude_from_weight_decay))
+
+    def current_weight_decay(self) -> float:
+        wd = self.weight_decay
+        return float(wd(self.iterations)) if callable(wd) else float(wd)
+
+    def decays(self, name: str) -> bool:
+        """Does the variable called `name` take weight decay?"""
+        import re
+        return not any(re.search(p, name) for p in self.exclude_from_weight_decay)
+
+    def step_scalars(self):
+        """(lr_t, wd_t) of the step about to be applied (t = iterations + 1): computed in double, each rounded once to fp32."""
+        t = self.iterations + 1
+        lr_t = self.current_lr() * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
+        return np.float32(lr_t), np.float32(self.current_weight_decay())
+
+    @property
+    def flat_m(self) -> torch.Tensor:
+        return self.flat_slots["m"]
+
+    @property
+    def flat_v(self) -> torch.Tensor:
+        return self.flat_slots["v"]
+
+    @property
+    def m_views(self) -> List[torch.Tensor]:
+        return self.slot_views["m"]
+
+    @property
+    def v_views(self) -> List[torch.Tensor]:
+        return self.slot_views["v"]
+
+    def _build_scalars(self, dev) -> None:
+        self.d_step = torch.zeros(2, dtype=torch.float32, device=dev)          # {lr_t, wd_t}
+        self.d_lr = self.d_step[0:1]
+        no_decay = not callable(self.weight_decay) and float(self.weight_decay) == 0.0      # Adam: no tensor decays
+        self.d_decays = to_device(np.asarray([0 if no_decay else int(self.decays(v.name)) for v in self.vars], np.uint8), torch.uint8)
+
+    def stage_lr(self) -> None:
+        lr_t, wd_t = self.step_scalars()
+        self.d_step[0:1].fill_(float(lr_t))          # (two one-element fill kernels: no host synchronisation, no pageable copy)
+        self.d_step[1:2].fill_(float(wd_t))
+
+    def _launch(self, grad_scale, skip_flag, stream) -> None:
+        # 1 - beta in double, rounded once: 1.0f - 0.999f is 9.9998713e-4 in fp32, 1.3e-5 off (include/bdetr.h)
+        _lib.check(_lib.lib().bdetr_adamw_clipnorm(
+            self.d_ptrs.data_ptr(), self.d_sizes.data_ptr(), len(self.vars), self.d_slab_tensor.data_ptr(),
+            self.d_slab_first.data_ptr(), self.nslabs, self.d_partial.data_ptr(), self.d_norms.data_ptr(),
+            self.d_step.data_ptr(), self.d_decays.data_ptr(), self.beta_1, self.beta_2, 1.0 - self.beta_1, 1.0 - self.beta_2,
+            self.epsilon, self.clipnorm, grad_scale, skip_flag, stream), "adamw")
+
+
+class Adam(AdamW):
+    """Keras Adam: AdamW with weight_decay = 0."""
+
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False, clipnorm=None, name="Adam"):
+        super().__init__(learning_rate, beta_1, beta_2, epsilon, amsgrad, weight_decay=0.0, clipnorm=clipnorm, name=name)
 
 
 # ----------------------------------------------------------------------------------------
@@ -206,7 +384,7 @@ class DataParallel:
             h.wait()
 
     # -- overlapped path ---------------------------------------------------------------------------------------
-    def prepare(self, optimizer: "SGD") -> None:
+    def prepare(self, optimizer: "Optimizer") -> None:
         """Bucket table for the optimizer's current flat buffer: bucket b covers [lo, hi) elements, counted from the end."""
         flat = optimizer.flat_grad
         if self._flat is flat:
@@ -239,7 +417,7 @@ class DataParallel:
             for k in {b, b2}:
                 self._bucket_size[k] += 1
 
-    def begin_step(self, optimizer: "SGD", main_stream, side_stream) -> None:
+    def begin_step(self, optimizer: "Optimizer", main_stream, side_stream) -> None:
         self._active = False
         if not self.active or not self.overlap or getattr(optimizer, "flat_grad", None) is None:
             return
@@ -444,7 +622,7 @@ class ModelCheckpoint(Callback):
         path = self.filepath.format(epoch=epoch + 1, **(logs or {}))
         dp = getattr(self.model, "_dp", None)
         if dp is None or dp.rank == 0:              # replicas hold identical weights: one writer, the others wait
-            self.model.save_weights(path)
+            self.model.save_weights(path, include_optimizer=not self.save_weights_only)      # Keras: the full model keeps the optimizer's slots
         if dp is not None:
             dp.barrier()
 
@@ -473,7 +651,7 @@ def latest_checkpoint(checkpoint_dir: str) -> Optional[str]:
 class Model(Layer):
     def __init__(self, name=None, **kwargs):
         super().__init__(name=name, **kwargs)
-        self.optimizer: Optional[SGD] = None
+        self.optimizer: Optional[Optimizer] = None
         self.stop_training = False
         self._step_losses: List[torch.Tensor] = []      # [B] vectors handed to add_loss
         self._loss_roots: List[torch.Tensor] = []       # tape roots whose backward seeds the step
@@ -670,7 +848,7 @@ class Model(Layer):
         loss = tuple(getattr(lf, k, None) for k in ("category_weight", "attribute_weight", "box_weight", "exist_weight", "loss_scale")) + \
             (getattr(self, "mask_weight", None),)
         opt = self.optimizer
-        hyper = (opt.momentum, opt.nesterov, opt.clipnorm) if opt is not None else ()
+        hyper = opt.hyper() if opt is not None else ()
         dp = self._dp
         return (id(opt), (id(dp), dp.world, dp.active, dp.overlap) if dp is not None else None,
                 tuple(getattr(opt, "_built_for", None) or ()), tuple(id(v) for v in self.trainable_variables),
@@ -1034,20 +1212,31 @@ class Model(Layer):
             if v.name in weights:
                 v.assign(weights[v.name])
 
-    def save_weights(self, filepath: str) -> None:
+    def save_weights(self, filepath: str, include_optimizer: bool = False) -> None:
+        """include_optimizer: also store the optimizer's slot variables (SGD's velocity, Adam's moments; Keras' TF-format
+        save_weights keeps them).  A resume then continues the run exactly: Adam's bias correction at a restored iteration count
+        over zeroed moments would be wrong arithmetic."""
         from safetensors.numpy import save_file
         if not filepath.endswith(".safetensors"):
             filepath += ".safetensors"
         os.makedirs(os.path.dirname(os.path.abspath(filepath)), exist_ok=True)
         meta = {"steps_done": str(self.steps_done),
                 "optimizer_iterations": str(self.optimizer.iterations if self.optimizer is not None else 0)}
-        save_file({k: np.ascontiguousarray(v) for k, v in self.get_weights_dict().items()}, filepath, metadata=meta)
+        tensors = self.get_weights_dict()
+        if include_optimizer and self.optimizer is not None:
+            tensors.update(self.optimizer.get_state(self.variables))
+            meta["optimizer"] = type(self.optimizer).__name__
+        save_file({k: np.ascontiguousarray(v) for k, v in tensors.items()}, filepath, metadata=meta)
 
     def load_weights(self, filepath: str) -> None:
         from safetensors.numpy import load_file
         if not filepath.endswith(".safetensors"):
             filepath += ".safetensors"
-        self.set_weights_dict(load_file(filepath))
+        tensors = load_file(filepath)
+        slots = {k: tensors.pop(k) for k in list(tensors) if k.startswith(Optimizer.STATE_PREFIX)}
+        self.set_weights_dict(tensors)
+        if slots and self.optimizer is not None:
+            self.optimizer.set_state(slots, self.variables)      # (a file without slots leaves them as they are: zero in a fresh optimizer)
         from safetensors import safe_open
         with safe_open(filepath, framework="np") as f:
             meta = f.metadata() or {}

@@ -598,13 +598,15 @@ int bdetr_set_loss(const bdetr_loss_desc* d, const float* cat_pred, const float*
 int bdetr_match_to_mask(const int32_t* match, float* mask, int B, int M, int N, void* stream);
 
 /* ------------------------------------------------------------------------
- * K13  optimizer: per-tensor clip-by-norm + Keras SGD(nesterov) (notebook cell 26, S15).
+ * K13  optimizers: per-tensor clip-by-norm + Keras SGD(nesterov) (notebook cell 26, S15), and AdamW (same cell).
  *      Multi-tensor: `ptrs` is a device array of ntensors x {w,g,v} pointers, `sizes` the
  *      element counts; norms: ntensors floats of workspace.
  *      Work is split in slabs of bdetr_sgd_slab_elems() elements; the host builds the slab
  *      table once: slab_tensor[nslabs] (owning tensor of each slab) and slab_first[ntensors+1]
  *      (first slab of each tensor), both int64 on the device.  partial: nslabs floats.
  *      lr is read from device memory (so a captured graph sees schedule updates).
+ *      ||g||: fp32 squares summed in fp32 within a slab (fixed order), the slabs' sums added in double, square root in double,
+ *      rounded once to fp32.
  *      skip_flag (optional, the range guard's device int): nothing is applied while it is up, and the call itself raises it
  *      when a tensor's gradient norm is not finite (a NaN / Inf born in the backward pass) - no tensor is then updated. */
 int bdetr_sgd_slab_elems(void);
@@ -612,6 +614,26 @@ int bdetr_sgd_nesterov_clipnorm(const uint64_t* ptrs, const int64_t* sizes, int 
                                 const int64_t* slab_tensor, const int64_t* slab_first, int nslabs,
                                 float* partial, float* norms, const float* lr, float momentum,
                                 float clipnorm, float grad_scale, int* skip_flag, void* stream);
+
+/*      AdamW = Keras Adam (non-amsgrad) + TFA's decoupled weight decay + Keras' per-tensor clipnorm (notebook cell 26:
+ *      tfa.optimizers.AdamW).  Same conventions and the same slab table / partial / norms workspaces as the SGD call; `ptrs` holds
+ *      ntensors x {w,g,m,v}.  Per element, every operation rounded to fp32 on its own, in this order (no fused multiply-add):
+ *          scale = grad_scale ; if clipnorm > 0 and ||g|| * |grad_scale| > clipnorm: scale *= clipnorm / (||g|| * |grad_scale|)
+ *          g' = g * scale
+ *          w1 = decays[t] ? w - wd_t * w : w                        (decoupled: not multiplied by the learning rate)
+ *          m' = beta1 * m + one_minus_beta1 * g'
+ *          v' = beta2 * v + one_minus_beta2 * (g' * g')
+ *          w' = w1 - (lr_t * m') / (sqrt(v') + epsilon)             (IEEE sqrt and division)
+ *      step_scalars: device float[2] = {lr_t, wd_t}, read by the kernel (a captured graph sees this step's values); the caller folds
+ *      the bias correction into lr_t in double: lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t).  one_minus_beta1/2 are arguments of
+ *      their own because 1.0f - 0.999f is 9.9998713e-4 in fp32 (1.3e-5 off, relative): compute them in double.  decays: ntensors bytes on the device,
+ *      non-zero = the tensor takes weight decay (NULL: all do).  skip_flag as above: while it is up w, m and v are all left
+ *      untouched, and a non-finite gradient norm raises it. */
+int bdetr_adamw_clipnorm(const uint64_t* ptrs, const int64_t* sizes, int ntensors,
+                         const int64_t* slab_tensor, const int64_t* slab_first, int nslabs,
+                         float* partial, float* norms, const float* step_scalars, const uint8_t* decays,
+                         float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float epsilon,
+                         float clipnorm, float grad_scale, int* skip_flag, void* stream);
 
 #ifdef __cplusplus
 }
