@@ -42,7 +42,7 @@ def to_device(a, dtype=torch.float32) -> torch.Tensor:
 # variables
 # ----------------------------------------------------------------------------------------
 # Bumped whenever weight values change (optimizer step, assign): derived copies of a weight (the pre-split P16
-# operand copies of the conv kernels, ops.packed_weights) are valid for one version only.
+# operand copies of the conv kernels, ops._PackCache) are valid for one version only.
 WEIGHTS_VERSION = [0]
 
 
@@ -178,28 +178,75 @@ def initializer(kind: str) -> Callable:
 # ----------------------------------------------------------------------------------------
 # tape
 # ----------------------------------------------------------------------------------------
+class GradInfo:
+    """What a gradient tensor carries through the backward pass besides its values; hangs on the tensor as `_grad_info`."""
+    # owned               the Tape is the tensor's sole owner: ops may accumulate into it
+    # lazy_mask           the tensor stands for tensor * mask (a residual unit's skip gradient, handed on without applying the unit's ReLU
+    #                     bit mask: ops.conv_bn); ops that know the tag fold the mask into their own kernel, `materialise` applies it
+    # compact_even        (N, H, W): the gradient exists at the pixels (2i, 2j) only and is held as the compact [N, H/2, W/2, C] tensor the
+    #                     stride-2 1x1 backward-data products wrote
+    # even_pixels         (N, H, W): a dense tensor that is zero off the even pixels (its BatchNorm backward reduces over a quarter of the rows)
+    # bnb_parts           BatchNorm-backward partial sums of the producer, reduced in the epilogue that wrote this tensor
+    # bnb_parts_shortcut  ... and those of the producer's projection shortcut
+    __slots__ = ("owned", "lazy_mask", "compact_even", "even_pixels", "bnb_parts", "bnb_parts_shortcut")
+
+    def __init__(self):
+        self.owned = False
+        self.lazy_mask = self.compact_even = self.even_pixels = self.bnb_parts = self.bnb_parts_shortcut = None
+
+
+_NO_INFO = GradInfo()       # shared by every untagged tensor: read-only
+
+
+def info(g) -> GradInfo:
+    """The record of a gradient tensor to READ (the shared empty one for an untagged tensor or None: nothing is allocated)."""
+    return getattr(g, "_grad_info", _NO_INFO)
+
+
+def tag(g: torch.Tensor) -> GradInfo:
+    """The record of a gradient tensor to WRITE (created on first use)."""
+    r = getattr(g, "_grad_info", None)
+    if r is None:
+        r = g._grad_info = GradInfo()
+    return r
+
+
+def own(t: torch.Tensor) -> torch.Tensor:
+    """Mark a freshly produced gradient tensor as solely owned by the Tape (safe to accumulate into)."""
+    tag(t).owned = True
+    return t
+
+
+def dense_contribution(g: torch.Tensor, keep_even=None) -> None:
+    """A dense contribution was added to the accumulated gradient `g`.  Partial sums that rode in with it (a BatchNorm-backward
+    reduction fused into the epilogue that produced it) describe the tensor BEFORE this contribution, and it is no longer zero off the
+    even pixels: drop both.  keep_even = (N, H, W): the contribution came from a further stride-2 1x1 convolution on that map, which
+    writes the even pixels only - an `even_pixels` tag of exactly that map survives."""
+    r = info(g)
+    if r is _NO_INFO:
+        return
+    r.bnb_parts = r.bnb_parts_shortcut = None
+    if r.even_pixels != keep_even:
+        r.even_pixels = None
+
+
 def materialise(g):
-    """A gradient tensor tagged ``_lazy_mask`` stands for tensor * mask (the skip gradient of a residual unit, handed on
-    without applying the unit's ReLU bit mask: ops.conv_bn).  Ops that know the tag fold the mask into their own kernel;
-    for everybody else the mask is applied in place here."""
-    c = getattr(g, "_compact_even", None) if g is not None else None
-    if c is not None:
-        # A gradient that exists at the pixels (2i, 2j) only, held as the compact [N, H/2, W/2, C] tensor the stride-2 backward-data
-        # products wrote (ops.conv_bn).  Its two regular consumers read it through the pixel map; anybody else gets the dense
-        # zero-filled tensor, built here (a torch strided copy: the fallback, not the step's path) - a NEW tensor: callers re-bind.
-        N, H, W = c
+    """The plain dense tensor behind a gradient: expands a compact even-pixel tensor and applies a lazy mask in place (GradInfo).  The
+    single place that does either - ops whose kernels do not read the tags call it, and so does the Tape for ops without `accepts_lazy`."""
+    r = info(g)
+    if r.compact_even is not None:
+        # Its two regular consumers read a compact tensor through the pixel map; anybody else gets the dense zero-filled tensor, built
+        # here (a torch strided copy: the fallback, not the step's path) - a NEW tensor: callers re-bind.
+        N, H, W = r.compact_even
         d = torch.empty(N, H, W, g.shape[-1], dtype=g.dtype, device=g.device)
         K.zero_(d)                                   # (a kernel, not torch.zeros: a hipMemset node must not enter a captured step - SegmentedCapture.census)
         d[:, ::2, ::2] = g.view(N, H // 2, W // 2, g.shape[-1])
-        d._bdetr_owned = True
-        d._even_pixels = (N, H, W)
-        if getattr(g, "_lazy_mask", None) is not None:
-            d._lazy_mask = g._lazy_mask
+        mask, r = r.lazy_mask, tag(d)
+        r.owned, r.even_pixels, r.lazy_mask = True, (N, H, W), mask
         g = d
-    m = getattr(g, "_lazy_mask", None)
-    if m is not None:
-        K.relu_mask_apply_(g, m)
-        del g._lazy_mask
+    if r.lazy_mask is not None:
+        K.relu_mask_apply_(g, r.lazy_mask)
+        r.lazy_mask = None
     return g
 
 
@@ -228,7 +275,7 @@ class Tape:
                 acc = []
                 for t in inputs:
                     have = grads.get(id(t)) if t is not None else None
-                    acc.append(have if getattr(have, "_bdetr_owned", False) else None)
+                    acc.append(have if info(have).owned else None)
                 gins = fn(*gouts, acc=acc)
             else:
                 gins = fn(*gouts)
@@ -240,29 +287,18 @@ class Tape:
                     continue
                 key = id(t)
                 if key in grads:
-                    have = grads[key]
                     if acc is not None and acc[i] is not None and g is acc[i]:
-                        continue                                    # the op already accumulated into the offered tensor
-                    if acc is not None and acc[i] is not None and getattr(g, "_replaces_acc", False):
-                        del g._replaces_acc                         # ... or folded it into a fresh tensor (a compact even-pixel gradient merged into a dense one)
+                        # the op already accumulated into the offered tensor - or folded it into a fresh one that it put into acc[i]
+                        # (a compact even-pixel gradient merged into a dense one)
                         grads[key] = g
                         continue
-                    g, have = materialise(g), materialise(have)
-                    grads[key] = have                               # (materialise re-binds a compact even-pixel tensor to its dense form)
-                    # partial sums that rode in with `have` (a BatchNorm-backward reduction fused into the epilogue that
-                    # produced it: ops.conv_bn) describe the tensor BEFORE this contribution: drop them
-                    if hasattr(have, "_bnb_parts"):
-                        del have._bnb_parts
-                    if hasattr(have, "_bnb_parts_shortcut"):
-                        del have._bnb_parts_shortcut
-                    if hasattr(have, "_even_pixels"):      # (ops.conv_bn's tag of a gradient that is zero off the even pixels: no longer true)
-                        del have._even_pixels
-                    if getattr(have, "_bdetr_owned", False):       # sole owner: accumulate in place
+                    g, have = materialise(g), materialise(grads[key])
+                    dense_contribution(have)
+                    if info(have).owned:                            # sole owner: accumulate in place
                         K.axpy_(1.0, g.view(have.shape), have)
+                        grads[key] = have                           # (materialise re-binds a compact even-pixel tensor to its dense form)
                     else:
-                        s = K.add(have, g.view(have.shape))
-                        s._bdetr_owned = True
-                        grads[key] = s
+                        grads[key] = own(K.add(have, g.view(have.shape)))
                 else:
                     grads[key] = g
             if _CAPTURE[0] is not None:
@@ -775,7 +811,9 @@ class Layer:
             # diagnostic (DebugLog): fingerprint every layer's first output tensor and the range-guard word in forward order
             t = out[0] if isinstance(out, (list, tuple)) and out else out
             if isinstance(t, torch.Tensor):
-                _DEBUG_LOG[0].emit("L", getattr(t, "_p16f", t) if getattr(t, "_p16_only", False) else t)
+                from . import ops
+                a = ops.act_info(t)
+                _DEBUG_LOG[0].emit("L", a.f16 if a.p16_only else t)
                 _DEBUG_LOG[0].emit("F", K.overflow_flag().view(torch.float32))
         return out
 

@@ -11,12 +11,15 @@ from __future__ import annotations
 
 import math
 import os
+import weakref
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import kernels as K
-from .engine import WEIGHTS_VERSION, Variable, current_tape, materialise, side_task
+from . import _lib
+from .engine import WEIGHTS_VERSION, Variable, current_tape, dense_contribution, info, materialise, own, side_task, tag
 
 # Dropout masks are keyed by (per-step seed, dropout site, element index).  The per-step seed lives in HBM
 # (one int64 the host rewrites before every step), the site salt is a launch argument: a captured step graph then
@@ -51,12 +54,6 @@ def _rec(outputs, inputs, fn):
 
 def _2d(t: torch.Tensor) -> torch.Tensor:
     return t.view(-1, t.shape[-1])
-
-
-def _own(t: torch.Tensor) -> torch.Tensor:
-    """Mark a freshly produced gradient tensor as solely owned by the Tape (safe to accumulate into)."""
-    t._bdetr_owned = True
-    return t
 
 
 _live_flat_grad = [None]
@@ -118,7 +115,7 @@ def image_prep(image: torch.Tensor, H: int, W: int) -> torch.Tensor:
     return K.image_prep(image, H, W)     # input images need no gradient
 
 
-COMPACT_S2 = os.environ.get("BDETR_COMPACT_S2", "1") != "0"       # stride-2 1x1 input gradients as compact even-pixel tensors (conv_bn backward)
+COMPACT_S2 = os.environ.get("BDETR_COMPACT_S2", "1") != "0"       # stride-2 1x1 input gradients as compact even-pixel tensors (_p16_input_grad)
 
 
 class BNState:
@@ -157,79 +154,146 @@ def _bn_backward(g2d, out2d, x2d, mean, rstd, bn: BNState, relu: bool, frozen: b
 # Under the 'split' policy a training-mode Conv+BN unit whose channel counts allow it runs on operands that their
 # producers already wrote as 16-bit pairs: BatchNorm apply writes the f16 pair (forward operand of the next conv)
 # and the bf16 pair (its weight-gradient operand), BatchNorm backward writes the bf16 pair of dy, the weights are
-# packed once per optimizer step.  A tensor handle carries its packed companions as attributes:
-#   t._p16f / t._p16b   P16-f16 / P16-bf16 copies (fp32-shaped torch tensors, never read as floats)
-#   t._p16_only         the handle IS the f16 copy: no fp32 tensor was materialised (links inside a bottleneck)
+# packed once per optimizer step.  A tensor handle carries its packed companions in an ActInfo record (below).
 P16_ENABLED = [os.environ.get("BDETR_P16", "1") != "0"]
-# Round 3: the weight gradient reads the f16 pair the FORWARD of its convolution read (converted to bf16 pairs inside the kernel,
+# The weight gradient reads the f16 pair the FORWARD of its convolution read (converted to bf16 pairs inside the kernel,
 # bdetr_p16_conv2d_bwd_weight_xf16), so activations have no bf16 pair copy at all: bn_apply_p16 writes 4 bytes per element less.
 WGRAD_XF16 = os.environ.get("BDETR_WGRAD_XF16", "1") != "0"
 BF16_FOR_3X3 = os.environ.get("BDETR_BF16_3X3", "1") != "0"       # ... except in front of a 3x3 convolution (conv_bn want_bf16)
-EVEN_PIXELS = os.environ.get("BDETR_EVEN_PIXELS", "1") != "0"  # stage-last BatchNorm backward reduces over the even pixels only (conv_bn.backward)
-LAZY_SKIP = os.environ.get("BDETR_LAZY_SKIP", "1") != "0"      # residual units hand their skip gradient on unmasked (conv_bn.backward)
+EVEN_PIXELS = os.environ.get("BDETR_EVEN_PIXELS", "1") != "0"  # stage-last BatchNorm backward reduces over the even pixels only (_p16_bn_backward)
+LAZY_SKIP = os.environ.get("BDETR_LAZY_SKIP", "1") != "0"      # residual units hand their skip gradient on unmasked (_p16_bn_backward)
+BN_FUSE = os.environ.get("BDETR_BN_FUSE", "1") != "0"          # BatchNorm-backward sums in the consumer's backward-data epilogue (ActInfo.bn_ctx, bn_ctx_bits)
+BN_FUSE2 = os.environ.get("BDETR_BN_FUSE2", "1") != "0"        # ... also those of a deferred projection-shortcut BatchNorm (ActInfo.bn_ctx_bits2)
 
 
 def _p16_active() -> bool:
     return P16_ENABLED[0] and K.get_gemm_precision() == "split"
 
 
+# ---- what a conv_bn output handle carries forward for its consumers ----
+class ActInfo:
+    """Packed companions and BatchNorm contexts of an activation handle; hangs on the tensor as `_act_info`.  A record never holds the
+    tensor it hangs on, nor a view of it (see conv_bn_relu_maxpool): that would be a reference cycle the GC collects late or never."""
+    # f16 / bf16     P16-f16 / P16-bf16 copies (fp32-shaped torch tensors, never read as floats)
+    # p16_only       the handle IS the f16 copy: no fp32 tensor was materialised (links inside a bottleneck)
+    # deferred_bn    (mean, rstd, gamma, beta): the handle is a projection shortcut's RAW convolution output, its BatchNorm still to apply
+    # bn_ctx         (y, mean, rstd, gamma, beta, relu) of the BatchNorm that wrote a link with exactly one consumer (the next conv of the
+    #                bottleneck): that conv's backward-data epilogue can do THIS BatchNorm's backward reduction while it stores the gradient
+    # bn_ctx_bits    (y, mean, rstd, gamma, beta, relu bit mask) of a residual unit whose output gradient the next unit's skip merge completes
+    # bn_ctx_bits2   (raw shortcut output, mean, rstd) of that unit's deferred projection-shortcut BatchNorm: it gets the same gradient
+    __slots__ = ("f16", "bf16", "p16_only", "deferred_bn", "bn_ctx", "bn_ctx_bits", "bn_ctx_bits2")
+
+    def __init__(self):
+        self.p16_only = False
+        self.f16 = self.bf16 = self.deferred_bn = self.bn_ctx = self.bn_ctx_bits = self.bn_ctx_bits2 = None
+
+
+_NO_ACT = ActInfo()         # shared by every untagged tensor (and None): read-only
+
+
+def act_info(t) -> ActInfo:
+    return getattr(t, "_act_info", _NO_ACT)
+
+
+def _act_tag(t: torch.Tensor) -> ActInfo:
+    a = getattr(t, "_act_info", None)
+    if a is None:
+        a = t._act_info = ActInfo()
+    return a
+
+
+def attach_packed(t: torch.Tensor, f16: torch.Tensor, bf16: Optional[torch.Tensor] = None, p16_only: bool = False) -> torch.Tensor:
+    """Hang the packed copies of activation `t` on its handle (p16_only: `t` has no fp32 values, `f16` is all there is)."""
+    a = _act_tag(t)
+    a.f16, a.bf16, a.p16_only = f16, bf16, p16_only
+    return t
+
+
+def is_p16_only(t: torch.Tensor) -> bool:
+    return act_info(t).p16_only
+
+
 def as_fp32(t: torch.Tensor) -> torch.Tensor:
     """The fp32 tensor behind a handle (unpacks a P16-only handle: 2^-23 relative round trip; applies a deferred
     BatchNorm: conv_bn(defer_apply=True))."""
-    if getattr(t, "_p16_only", False):
-        return K.p16_unpack(t._p16f, True).view(t.shape)
-    dbn = getattr(t, "_deferred_bn", None)
-    if dbn is not None:
-        return K.bn_apply(_2d(t), *dbn, None, False).view(t.shape)
+    a = act_info(t)
+    if a.p16_only:
+        return K.p16_unpack(a.f16, True).view(t.shape)
+    if a.deferred_bn is not None:
+        return K.bn_apply(_2d(t), *a.deferred_bn, None, False).view(t.shape)
     return t
 
 
 def _packed_input(x: torch.Tensor, need_bf16: bool):
     """(f16 pair, bf16 pair | None) of an activation, packing an fp32 handle once and caching the result on it."""
-    xf, xb = getattr(x, "_p16f", None), getattr(x, "_p16b", None)
+    a = act_info(x)
+    xf, xb = a.f16, a.bf16
     need_bf16 = need_bf16 and not WGRAD_XF16
     if xf is None or (need_bf16 and xb is None):
         f, b = K.p16_pack(x, want_f16=xf is None, want_bf16=need_bf16 and xb is None)
         xf, xb = (f if xf is None else xf), (b if b is not None else xb)
-        x._p16f, x._p16b = xf, xb
+        attach_packed(x, xf, xb, a.p16_only)
     return xf, xb
 
 
-class _PackedWeights:
-    """Both P16 copies of every conv kernel that takes the pre-split path, in persistent buffers, refreshed by ONE
-    multi-tensor launch the first time a copy is asked for after the weights changed (optimizer step / assign).
-    The table keeps the buffers of its rows alive; rows of variables that no longer exist are dropped whenever the
-    table is rebuilt (a new variable registers)."""
+class _PackCache:
+    """The two packed copies (forward operand, backward-data operand) of every weight matrix of one kind, in persistent buffers,
+    refreshed by ONE multi-tensor launch the first time a copy is asked for after the weights changed (optimizer step / assign).
+    The table keeps the buffers of its rows alive; rows of variables that no longer exist are dropped whenever the table is rebuilt
+    (a new variable registers).  alloc(value) -> the two buffers of a row; table_row(value, fwd, bwd) -> its int64 table row;
+    pack(table) -> the launch that refreshes every row.  A Variable belongs to one cache (it carries its row as `_packs`)."""
 
-    def __init__(self):
-        self.rows, self.table, self.version = [], None, -1       # rows: (weakref(var), value, wf, wt)
+    def __init__(self, alloc, table_row, pack):
+        self.alloc, self.table_row, self.pack = alloc, table_row, pack
+        self.rows, self.table, self.version = [], None, -1       # rows: (weakref(var), value, fwd copy, bwd copy)
 
     def get(self, w: Variable):
-        import weakref
-        c = getattr(w, "_p16", None)
+        c = getattr(w, "_packs", None)
         if c is None or c[0].data_ptr() != w.value.data_ptr():
-            Kout, R, S, Cin = w.value.shape
-            c = (w.value, torch.empty_like(w.value), torch.empty((Cin, R, S, Kout), dtype=torch.float32, device=w.value.device))
-            w._p16 = c
+            c = w._packs = (w.value,) + self.alloc(w.value)
             self.rows = [r for r in self.rows if r[0]() is not None and r[0]() is not w]
             self.rows.append((weakref.ref(w),) + c)
             self.table, self.version = None, -1
         if self.version != WEIGHTS_VERSION[0]:
             if self.table is None:
-                import numpy as np
-                rows = np.array([[v.data_ptr(), wf.data_ptr(), wt.data_ptr(), *v.shape] for _, v, wf, wt in self.rows], np.int64)
+                rows = np.array([self.table_row(*r[1:]) for r in self.rows], np.int64)
                 self.table = torch.from_numpy(rows).to(w.value.device)
-            K.p16_pack_conv_weights_multi(self.table)
+            self.pack(self.table)
             self.version = WEIGHTS_VERSION[0]
         return c[1], c[2]
 
 
-_PACKED = _PackedWeights()
+def _conv_pack_buffers(v: torch.Tensor):
+    Kout, R, S, Cin = v.shape
+    return torch.empty_like(v), torch.empty((Cin, R, S, Kout), dtype=torch.float32, device=v.device)
 
 
-def packed_weights(w: Variable, need_bwd: bool = True):
-    """(P16-f16 forward copy [K,R,S,C], P16-bf16 transposed tap-flipped copy [C,R,S,K]) of a conv kernel."""
-    return _PACKED.get(w)
+# conv kernels on the pre-split path: (P16-f16 forward copy [K,R,S,C], P16-bf16 transposed tap-flipped copy [C,R,S,K])
+_PACKED = _PackCache(_conv_pack_buffers, lambda v, f, t: [v.data_ptr(), f.data_ptr(), t.data_ptr(), *v.shape],
+                     K.p16_pack_conv_weights_multi)
+
+
+def _write_param_grads(w: Variable, b: Variable, write_dw, bias_from: Optional[torch.Tensor]) -> None:
+    """Weight, then bias gradient of a conv / dense unit into their GradSinks.  write_dw(buf, prezeroed) launches the weight gradient;
+    the bias gradient is the column sum of the 2-D gradient `bias_from`, or - bias_from None - exactly zero: a bias in front of a
+    batch-statistics BatchNorm, where sum_rows(dy) = -rstd*gamma*mean(g*xhat)*sum(xhat) and sum(xhat) == 0 (the fp64 oracle gives ~1e-15)."""
+    if w.needs_grad:
+        s = GradSink(w)
+        write_dw(s.buf, s.mode == "direct")
+        s.commit()
+    if b.needs_grad:
+        s = GradSink(b)
+        if bias_from is not None:
+            K.colsum(bias_from, out=s.buf, prezeroed=s.mode == "direct")
+        elif s.mode != "direct":
+            K.zero_(s.buf)
+        s.commit()
+
+
+def _param_grads_task(w: Variable, b: Variable, write_dw, bias_from: Optional[torch.Tensor], *keep) -> None:
+    """_write_param_grads as one side task (`keep`: the operands the side stream reads, see engine.on_side_stream)."""
+    if w.needs_grad or b.needs_grad:
+        side_task(lambda: _write_param_grads(w, b, write_dw, bias_from), *keep)
 
 
 def conv_bn(x: torch.Tensor, w: Variable, b: Variable, bn: BNState, stride: int, pad: int, relu: bool,
@@ -240,9 +304,9 @@ def conv_bn(x: torch.Tensor, w: Variable, b: Variable, bn: BNState, stride: int,
 
     sole_consumer_is_identity_unit (residual units): the only consumers of this output are the next unit's first 1x1
     convolution and its identity skip - the masked accumulate that completes this output's gradient there can then also do
-    THIS unit's BatchNorm-backward reduction (ctx attached to the handle as `_bn_ctx_bits`).
+    THIS unit's BatchNorm-backward reduction (ctx attached to the handle as `bn_ctx_bits`).
     defer_apply (projection shortcut, no ReLU, no residual; P16 path only): the statistics are reduced but the normalised
-    tensor is not written - the returned handle is the RAW convolution output tagged `_deferred_bn`, and the unit that takes
+    tensor is not written - the returned handle is the RAW convolution output tagged `deferred_bn`, and the unit that takes
     it as `residual` applies both BatchNorms in its one pass (bn_apply_p16 residual_bn; as_fp32 is the fallback).
 
     want_p16: the consumer is another conv_bn - also emit the packed copy of the output (P16 path only): the f16 pair, which feeds
@@ -254,225 +318,224 @@ def conv_bn(x: torch.Tensor, w: Variable, b: Variable, bn: BNState, stride: int,
     Kout, R, S, _ = w.value.shape
     g = K.ConvGeom(N, H, W, Cin, Kout, R, S, stride, pad)
     use_batch = training if bn_batch_stats is None else bn_batch_stats
-    p16 = training and use_batch and _p16_active() and K.p16_supported(g)
-    x_handle, res_handle = x, residual                 # the Tape keys gradients by the handles their producers returned
-    res_p16 = p16 and residual is not None and getattr(residual, "_p16_only", False)
-    res_bn = getattr(residual, "_deferred_bn", None) if (p16 and residual is not None) else None
-    if residual is not None and not res_p16 and res_bn is None:
-        residual = as_fp32(residual)
-    res2d = _2d(residual) if residual is not None else None     # a P16-only handle IS its f16 pair copy
-    xb = ob = relu_bits = None
-    if p16:
-        xf, xb = _packed_input(x, need_bf16=w.needs_grad)
-        wf, _ = packed_weights(w, need_bwd=False)
-        y, parts = K.p16_conv2d_fwd(xf, wf, b.value, g, K.ACT_NONE, want_stats=True)
-        y2d = _2d(y)
-        mean, rstd = K.bn_stats(g.M, Kout, parts, bn.eps, bn.momentum, True, bn.moving_mean.value, bn.moving_var.value, like=y2d)
-        fp32_out = want_fp32 or not want_p16
-        # a residual unit without an fp32 output: its backward ReLU mask is a 1-bit-per-element by-product of this pass
-        want_mask = relu and residual is not None and not fp32_out
-        if defer_apply and not relu and residual is None:
-            out2d = None
-            out = y.view(N, g.OH, g.OW, Kout)            # (a fresh handle: y itself stays this unit's own tensor)
-            out._deferred_bn = (mean, rstd, bn.gamma.value, bn.beta.value)
-        else:
-            o32, of, ob, *rest = K.bn_apply_p16(y2d, mean, rstd, bn.gamma.value, bn.beta.value, res2d, relu, want_fp32=fp32_out,
-                                                want_f16=want_p16, want_bf16=want_p16 and ((want_bf16 and BF16_FOR_3X3) or not WGRAD_XF16), residual_p16=res_p16, want_mask=want_mask,
-                                                residual_bn=res_bn)
-            relu_bits = rest[0] if want_mask else None
-            out2d = o32
-            out = (o32 if fp32_out else of).view(N, g.OH, g.OW, Kout)
-        if want_p16:
-            out._p16f, out._p16b, out._p16_only = of.view(out.shape), (ob.view(out.shape) if ob is not None else None), not fp32_out
-        if relu_bits is not None and sole_consumer_is_identity_unit and os.environ.get("BDETR_BN_FUSE", "1") != "0":
-            out._bn_ctx_bits = (y2d, mean, rstd, bn.gamma.value, bn.beta.value, relu_bits)
-            if res_bn is not None and os.environ.get("BDETR_BN_FUSE2", "1") != "0":
-                # a stage's first unit: the projection shortcut's BatchNorm (deferred: res2d is its RAW conv output) gets the same gradient -
-                # its sum(g * xhat0) rides the same epilogue (round 4)
-                out._bn_ctx_bits2 = (res2d, res_bn[0], res_bn[1])
-        if not fp32_out and residual is None and os.environ.get("BDETR_BN_FUSE", "1") != "0":
-            # a link with exactly one consumer (the next conv of the bottleneck): that conv's backward-data epilogue can do
-            # THIS BatchNorm's backward reduction while it stores the gradient (ops: see `backward` below)
-            out._bn_ctx = (y2d, mean, rstd, bn.gamma.value, bn.beta.value, relu)
-    else:
-        x = as_fp32(x)
-        y, parts = K.conv2d_fwd(x, w.value, b.value, g, K.ACT_NONE, want_stats=use_batch)
-        y2d = _2d(y)
-        out2d, mean, rstd = _bn_forward(y2d, g.M, Kout, parts, bn, use_batch, True, res2d, relu)
-        out = out2d.view(N, g.OH, g.OW, Kout)
+    if training and use_batch and _p16_active() and K.p16_supported(g):
+        return _conv_bn_p16(x, w, b, bn, g, relu, residual, x_needs_grad, want_fp32, want_p16, defer_apply, sole_consumer_is_identity_unit,
+                            want_bf16)
+    return _conv_bn_fp32(x, w, b, bn, g, relu, residual, use_batch, x_needs_grad)
+
+
+def _conv_bn_fp32(x, w: Variable, b: Variable, bn: BNState, g, relu: bool, residual, use_batch: bool, x_needs_grad: bool) -> torch.Tensor:
+    """conv_bn on the plain fp32 kernels (inference, moving statistics, policies and geometries without a pre-split kernel)."""
+    x32 = as_fp32(x)
+    res2d = _2d(as_fp32(residual)) if residual is not None else None
+    y, parts = K.conv2d_fwd(x32, w.value, b.value, g, K.ACT_NONE, want_stats=use_batch)
+    y2d = _2d(y)
+    out2d, mean, rstd = _bn_forward(y2d, g.M, g.K, parts, bn, use_batch, True, res2d, relu)
+    out = out2d.view(g.N, g.OH, g.OW, g.K)
+    res_shape = residual.shape if residual is not None else None
 
     def backward(g_out, acc=None):
-        want_res = residual is not None
-        # A gradient that exists at the pixels (2i, 2j) only arrives as the compact [N, OH/2, OW/2, K] tensor its producers - the next
-        # stage's stride-2 1x1 backward-data products, below - wrote densely (round 5: no zero-filled dense tensor, no scatter).  A
-        # residual unit on the pre-split path reads it through the pixel map in both of its consumers (this BatchNorm backward and
-        # the skip merge of the unit's first convolution); every other case gets the dense form (engine.materialise).
-        compact = getattr(g_out, "_compact_even", None)
-        if compact is not None and not (p16 and _p16_active() and relu and want_res and relu_bits is not None and LAZY_SKIP and compact == (N, g.OH, g.OW)
-                                         and getattr(g_out, "_bdetr_owned", False) and getattr(g_out, "_lazy_mask", None) is None
-                                         and getattr(g_out, "_bnb_parts", None) is None and g_out.is_contiguous()):
-            g_out, compact = materialise(g_out), None
-        lazy_bits = getattr(g_out, "_lazy_mask", None)      # g_out still needs its producer's ReLU mask (see below)
-        if lazy_bits is not None and not (p16 and _p16_active() and not relu and residual is None):
-            g_out, lazy_bits = materialise(g_out), None
-        g2d = _2d(g_out.contiguous())
-        if p16 and _p16_active():
-            sg, sb = GradSink(bn.gamma), GradSink(bn.beta)
-            # ReLU mask: recomputed from y when there is no residual, else read from the forward output (fp32, or the
-            # hi halves of its bf16 pair copy when the output was never materialised in fp32)
-            # ReLU mask: recomputed from y when there is no residual, else the forward output (fp32), or - when that was never
-            # materialised in fp32 - the bit mask bn_apply wrote (else the hi halves of the bf16 pair copy)
-            mask_src, mode = None, 0
-            if relu and want_res:
-                mask_src, mode = (out2d, 0) if out2d is not None else ((relu_bits, 2) if relu_bits is not None else (ob, 1))
-                assert mask_src is not None, "a residual unit without an fp32 output keeps its ReLU bit mask"
-            pre = getattr(g_out, "_bnb_parts", None)        # the reduction came with the gradient (fused into the consumer's epilogue)
-            # The skip gradient of a residual unit is g_out * mask.  With the bit mask at hand it is not written out: the
-            # incoming gradient tensor itself is handed to the shortcut's producer tagged with the mask, and the consumers
-            # that know the tag (the 1x1 backward-data below, the projection shortcut's BatchNorm backward) fold the mask into
-            # their own kernels - one 4-byte-per-element write per unit less (engine.materialise is the fallback).
-            lazy_skip = (want_res and mode == 2 and LAZY_SKIP and getattr(g_out, "_bdetr_owned", False) and lazy_bits is None
-                         and g_out.is_contiguous())
-            bn_relu = relu
-            if lazy_bits is not None:                       # this BatchNorm has no ReLU of its own: apply the incoming mask instead
-                mask_src, mode, bn_relu = lazy_bits, 2, True
-            even = getattr(g_out, "_even_pixels", None) if EVEN_PIXELS else None     # zero off the even pixels: a quarter-size reduction pass
-            if even is not None and even != (N, g.OH, g.OW):
-                even = None
-            if compact is not None:
-                assert lazy_skip and pre is None, "a compact even-pixel gradient is handed on to the skip merge as it is"
-                even = compact
-            dyb, _, _, _, dres = K.bn_bwd_p16(g2d, mask_src, y2d, mean, rstd, bn.gamma.value, bn_relu, False,
-                                              want_residual_grad=want_res and not lazy_skip,
-                                              dgamma=sg.buf, dbeta=sb.buf, beta=bn.beta.value, out_p16=mode, pre=pre, even_pixels=even,
-                                              dout_compact=compact is not None)
-            if lazy_skip:
-                dres = _own(g_out.view(residual.shape)) if compact is None else _own(g_out)      # (compact: keeps its `_compact_even` tag)
-                dres._lazy_mask = relu_bits
-                sc_parts = getattr(g_out, "_bnb_parts_shortcut", None)
-                if sc_parts is not None and res_bn is not None:
-                    dres._bnb_parts = sc_parts          # the shortcut's BatchNorm backward finds its reduction done (it reads them as `pre`)
-            sg.commit()
-            sb.commit()
-            dyb4 = dyb.view(N, g.OH, g.OW, Kout)
-            if w.needs_grad or b.needs_grad:
-                xw, xw_f16 = (xb, False) if xb is not None else (xf, True)     # the weight gradient's x operand: a bf16 pair copy where the producer wrote one, else the forward's f16 pair
-
-                def param_grads(xw=xw, xw_f16=xw_f16, dyb4=dyb4):
-                    if w.needs_grad:
-                        s = GradSink(w)
-                        K.p16_conv2d_bwd_weight(xw, dyb4, g, dw=s.buf, prezeroed=s.mode == "direct", x_f16=xw_f16)
-                        s.commit()
-                    if b.needs_grad:
-                        s = GradSink(b)             # a bias in front of a batch-statistics BN has an exactly zero gradient (see below)
-                        if s.mode != "direct":
-                            K.zero_(s.buf)
-                        s.commit()
-                side_task(param_grads, xw, dyb)
-            dx = None
-            s2 = R == 1 and S == 1 and stride == 2 and pad == 0
-            # a stride-2 1x1 convolution's input gradient lives at the pixels (2i, 2j): on an even map it is produced as the compact
-            # [N, H/2, W/2, C] tensor - a plain dense product over the OUTPUT grid - and tagged; see the top of this function
-            s2c = s2 and COMPACT_S2 and H % 2 == 0 and W % 2 == 0
-            gc = K.ConvGeom(N, g.OH, g.OW, Cin, Kout, 1, 1, 1, 0) if s2c else None
-            if x_needs_grad:
-                _, wt = packed_weights(w, need_bwd=True)
-                ctx = getattr(x_handle, "_bn_ctx", None)
-                have_c = getattr(acc[0], "_compact_even", None) if acc is not None and acc[0] is not None else None
-                if have_c is not None and s2c and have_c == (N, H, W) and getattr(acc[0], "_lazy_mask", None) is None:
-                    # the other stride-2 consumer of x was first: add into its compact tensor
-                    K.p16_conv2d_bwd_data(dyb4, wt, gc, dx=acc[0].view(N, g.OH, g.OW, Cin), accumulate=True)
-                    dx = acc[0]
-                elif have_c is not None and getattr(acc[0], "_lazy_mask", None) is not None and R == 1 and S == 1 and stride == 1 and pad == 0 \
-                        and have_c == (N, H, W) and getattr(x_handle, "_bn_ctx_bits2", None) is None:
-                    # the skip merge of a stage's last unit: conv_transpose(dy) + expand(compact gradient) * mask into a FRESH dense tensor
-                    ctx_bits = getattr(x_handle, "_bn_ctx_bits", None)
-                    fresh = K.empty(N, H, W, Cin, like=dyb)
-                    r = K.p16_conv2d_bwd_data_masked_accum(dyb4, wt, g, fresh, acc[0]._lazy_mask, bn_ctx=ctx_bits, old_even=acc[0])
-                    dx = _own(fresh)
-                    if ctx_bits is not None:
-                        dx._bnb_parts = r[1]
-                    dx._replaces_acc = True                 # (engine.Tape: this tensor IS the accumulated gradient now)
-                elif have_c is not None:
-                    base = materialise(acc[0])              # any other pairing: the dense form (a new tensor), then the plain accumulate
-                    K.p16_conv2d_bwd_data(dyb4, wt, g, dx=base.view(N, H, W, Cin), accumulate=True)
-                    if hasattr(base, "_even_pixels") and not (s2 and base._even_pixels == (N, H, W)):
-                        del base._even_pixels
-                    dx = base
-                    dx._replaces_acc = True
-                elif acc is not None and acc[0] is not None:
-                    skip_bits = getattr(acc[0], "_lazy_mask", None)
-                    if skip_bits is not None and R == 1 and S == 1 and stride == 1 and pad == 0:
-                        ctx_bits = getattr(x_handle, "_bn_ctx_bits", None)
-                        if ctx_bits is not None:        # this merge completes the previous unit's output gradient: do its BN-backward sums too
-                            ctx2 = getattr(x_handle, "_bn_ctx_bits2", None)
-                            r = K.p16_conv2d_bwd_data_masked_accum(dyb4, wt, g, acc[0].view(N, H, W, Cin), skip_bits, bn_ctx=ctx_bits, bn_ctx2=ctx2)
-                            acc[0]._bnb_parts = r[1]
-                            if ctx2 is not None:
-                                acc[0]._bnb_parts_shortcut = r[2]      # ... and those of its projection shortcut's BatchNorm
-                        else:
-                            K.p16_conv2d_bwd_data_masked_accum(dyb4, wt, g, acc[0].view(N, H, W, Cin), skip_bits)
-                        del acc[0]._lazy_mask
-                    else:
-                        K.p16_conv2d_bwd_data(dyb4, wt, g, dx=materialise(acc[0]).view(N, H, W, Cin), accumulate=True)
-                    if hasattr(acc[0], "_even_pixels") and not (s2 and acc[0]._even_pixels == (N, H, W)):
-                        del acc[0]._even_pixels         # this contribution is dense
-                    dx = acc[0]
-                elif ctx is not None and stride == 1:
-                    dx, parts = K.p16_conv2d_bwd_data_bnstats(dyb4, wt, g, *ctx)
-                    dx = _own(dx)
-                    dx._bnb_parts = parts
-                elif s2c:
-                    dx = _own(K.p16_conv2d_bwd_data(dyb4, wt, gc))
-                    dx._compact_even = (N, H, W)
-                else:
-                    dx = _own(K.p16_conv2d_bwd_data(dyb4, wt, g))
-                    if s2:
-                        # a stride-2 1x1 convolution's input gradient: zero-filled, then written at the pixels (2i, 2j) only.  The tag lets
-                        # the producer's BatchNorm backward reduce over those pixels alone (it survives further stride-2 1x1 contributions)
-                        dx._even_pixels = (N, H, W)
-            return dx, ((dres if lazy_skip else _own(dres.view(residual.shape))) if want_res else None)
-        x32 = as_fp32(x)
-        out32 = out2d if (out2d is not None or not (relu and want_res)) else _2d(as_fp32(out))
-        dy, dres = _bn_backward(g2d, out32, y2d, mean, rstd, bn, relu, not use_batch, want_res)
-        dy4 = dy.view(N, g.OH, g.OW, Kout)
-        if w.needs_grad or b.needs_grad:
-            def param_grads(x32=x32, dy=dy, dy4=dy4):
-                if w.needs_grad:
-                    s = GradSink(w)
-                    K.conv2d_bwd_weight(x32, dy4, g, dw=s.buf, prezeroed=s.mode == "direct")
-                    s.commit()
-                if b.needs_grad:
-                    s = GradSink(b)
-                    if use_batch:
-                        # A bias in front of a batch-statistics BN has an exactly zero gradient: sum_rows(dy) =
-                        # -rstd*gamma*mean(g*xhat)*sum(xhat) and sum(xhat) == 0.  (The fp64 oracle gives ~1e-15.)
-                        if s.mode != "direct":
-                            K.zero_(s.buf)
-                    else:
-                        K.colsum(dy, out=s.buf, prezeroed=s.mode == "direct")
-                    s.commit()
-            side_task(param_grads, x32, dy)
-        dx = None
-        if x_needs_grad:
-            if acc is not None and acc[0] is not None:
-                # residual merge fused into the GEMM epilogue: dx += conv_transpose(dy) (no separate add pass)
-                base = materialise(acc[0])                  # (a compact even-pixel gradient comes back as a NEW dense tensor)
-                K.conv2d_bwd_data(dy4, w.value, g, dx=base.view(N, H, W, Cin), accumulate=True)
-                if hasattr(base, "_even_pixels"):
-                    del base._even_pixels
-                dx = base
-                if base is not acc[0]:
-                    dx._replaces_acc = True                 # (engine.Tape re-binds the accumulated gradient to it)
-            else:
-                dx = _own(K.conv2d_bwd_data(dy4, w.value, g))
-        dr = _own(dres.view(residual.shape)) if want_res else None
-        return dx, dr
+        return _conv_bn_backward_fp32(g_out, acc, x32, w, b, bn, g, relu, res_shape, use_batch, x_needs_grad, y2d, mean, rstd, out2d)
 
     backward.wants_acc = True
     backward.accepts_lazy = True
-    _rec([out], [x_handle, res_handle], backward)
+    _rec([out], [x, residual], backward)       # the Tape keys gradients by the handles their producers returned
     return out
+
+
+def _conv_bn_backward_fp32(g_out, acc, x32, w: Variable, b: Variable, bn: BNState, g, relu: bool, res_shape, use_batch: bool,
+                           x_needs_grad: bool, y2d, mean, rstd, out2d):
+    """Backward of a Conv+BN unit on the plain fp32 kernels, from fp32 tensors (out2d: only read for the ReLU mask of a residual unit).
+    Its kernels know none of the gradient tags: the incoming gradient is materialised."""
+    g2d = _2d(materialise(g_out).contiguous())
+    want_res = res_shape is not None
+    dy, dres = _bn_backward(g2d, out2d, y2d, mean, rstd, bn, relu, not use_batch, want_res)
+    dy4 = dy.view(g.N, g.OH, g.OW, g.K)
+    _param_grads_task(w, b, lambda dw, pz: K.conv2d_bwd_weight(x32, dy4, g, dw=dw, prezeroed=pz), None if use_batch else dy, x32, dy)
+    dx = None
+    if x_needs_grad and acc is not None and acc[0] is not None:
+        # residual merge fused into the GEMM epilogue: dx += conv_transpose(dy) (no separate add pass).  A compact even-pixel gradient
+        # comes back from materialise as a NEW dense tensor: it replaces the offered one in `acc`, the Tape re-binds to it
+        dx = acc[0] = materialise(acc[0])
+        K.conv2d_bwd_data(dy4, w.value, g, dx=dx.view(g.N, g.H, g.W, g.C), accumulate=True)
+        dense_contribution(dx)
+    elif x_needs_grad:
+        dx = own(K.conv2d_bwd_data(dy4, w.value, g))
+    return dx, (own(dres.view(res_shape)) if want_res else None)
+
+
+def _conv_bn_p16(x, w: Variable, b: Variable, bn: BNState, g, relu: bool, residual, x_needs_grad: bool, want_fp32: bool, want_p16: bool,
+                 defer_apply: bool, sole_consumer_is_identity_unit: bool, want_bf16: bool) -> torch.Tensor:
+    """conv_bn on the pre-split operand path (training with batch statistics under the 'split' policy)."""
+    ra = act_info(residual)
+    res_p16, res_bn = ra.p16_only, ra.deferred_bn
+    res2d = _2d(residual) if residual is not None else None     # a P16-only handle IS its f16 pair copy, a deferred one the RAW conv output
+    xf, xb = _packed_input(x, need_bf16=w.needs_grad)
+    y, parts = K.p16_conv2d_fwd(xf, _PACKED.get(w)[0], b.value, g, K.ACT_NONE, want_stats=True)
+    y2d = _2d(y)
+    mean, rstd = K.bn_stats(g.M, g.K, parts, bn.eps, bn.momentum, True, bn.moving_mean.value, bn.moving_var.value, like=y2d)
+    fp32_out = want_fp32 or not want_p16
+    # a residual unit without an fp32 output: its backward ReLU mask is a 1-bit-per-element by-product of this pass
+    want_mask = relu and residual is not None and not fp32_out
+    out2d = ob = relu_bits = None
+    if defer_apply and not relu and residual is None:
+        out = y.view(g.N, g.OH, g.OW, g.K)               # (a fresh handle: y itself stays this unit's own tensor)
+        _act_tag(out).deferred_bn = (mean, rstd, bn.gamma.value, bn.beta.value)
+    else:
+        out2d, of, ob, *rest = K.bn_apply_p16(y2d, mean, rstd, bn.gamma.value, bn.beta.value, res2d, relu, want_fp32=fp32_out, want_f16=want_p16,
+                                              want_bf16=want_p16 and ((want_bf16 and BF16_FOR_3X3) or not WGRAD_XF16), residual_p16=res_p16,
+                                              want_mask=want_mask, residual_bn=res_bn)
+        relu_bits = rest[0] if want_mask else None
+        out = (out2d if fp32_out else of).view(g.N, g.OH, g.OW, g.K)
+    if want_p16:
+        attach_packed(out, of.view(out.shape), ob.view(out.shape) if ob is not None else None, p16_only=not fp32_out)
+    if relu_bits is not None and sole_consumer_is_identity_unit and BN_FUSE:
+        _act_tag(out).bn_ctx_bits = (y2d, mean, rstd, bn.gamma.value, bn.beta.value, relu_bits)
+        if res_bn is not None and BN_FUSE2:     # a stage's first unit: its sum(g * xhat0) rides the same epilogue
+            _act_tag(out).bn_ctx_bits2 = (res2d, res_bn[0], res_bn[1])
+    if not fp32_out and residual is None and BN_FUSE:
+        _act_tag(out).bn_ctx = (y2d, mean, rstd, bn.gamma.value, bn.beta.value, relu)
+    res_shape = residual.shape if residual is not None else None
+
+    def backward(g_out, acc=None):
+        if not _p16_active():
+            # the backward runs under another arithmetic policy than the forward did (Model.replay_backward('fp32')): the fp32 kernels,
+            # on the tensors this forward saved
+            x32 = as_fp32(x)
+            out32 = out2d if (out2d is not None or not (relu and residual is not None)) else _2d(as_fp32(out))
+            return _conv_bn_backward_fp32(g_out, acc, x32, w, b, bn, g, relu, res_shape, True, x_needs_grad, y2d, mean, rstd, out32)
+        dyb, dres = _p16_bn_backward(g_out, bn, g, relu, res_shape, res_bn, y2d, mean, rstd, out2d, relu_bits, ob)
+        dyb4 = dyb.view(g.N, g.OH, g.OW, g.K)
+        # the weight gradient's x operand: a bf16 pair copy where the producer wrote one, else the forward's f16 pair
+        xw, xw_f16 = (xb, False) if xb is not None else (xf, True)
+        _param_grads_task(w, b, lambda dw, pz: K.p16_conv2d_bwd_weight(xw, dyb4, g, dw=dw, prezeroed=pz, x_f16=xw_f16), None, xw, dyb)
+        return (_p16_input_grad(dyb4, w, g, act_info(x), acc) if x_needs_grad else None), dres
+
+    backward.wants_acc = True
+    backward.accepts_lazy = True
+    _rec([out], [x, residual], backward)       # the Tape keys gradients by the handles their producers returned
+    return out
+
+
+def _p16_bn_backward(g_out, bn: BNState, g, relu: bool, res_shape, res_bn, y2d, mean, rstd, out2d, relu_bits, ob):
+    """BatchNorm(+residual, +ReLU) backward of a pre-split unit: (dy as its bf16 pair, the residual's gradient | None).  Reads the
+    gradient tags its kernel knows (engine.GradInfo) and materialises the rest."""
+    want_res, omap = res_shape is not None, (g.N, g.OH, g.OW)
+    # A gradient that exists at the pixels (2i, 2j) only arrives as the compact [N, OH/2, OW/2, K] tensor its producers - the next stage's
+    # stride-2 1x1 backward-data products (_p16_input_grad) - wrote densely: no zero-filled dense tensor, no scatter.  A residual unit reads
+    # it through the pixel map in both of its consumers (this BatchNorm backward and the skip merge of the unit's first convolution);
+    # every other case gets the dense form.
+    gi = info(g_out)
+    compact = gi.compact_even
+    if compact is not None and not (relu and want_res and relu_bits is not None and LAZY_SKIP and compact == omap and gi.owned
+                                    and gi.lazy_mask is None and gi.bnb_parts is None and g_out.is_contiguous()):
+        g_out, compact = materialise(g_out), None
+        gi = info(g_out)
+    # g_out still needs its producer's ReLU mask (see lazy_skip below): only a BatchNorm with neither a ReLU nor a residual of its own
+    # (a projection shortcut's) applies it in its kernel
+    lazy_bits = gi.lazy_mask
+    if lazy_bits is not None and (relu or want_res):
+        g_out, lazy_bits = materialise(g_out), None
+    g2d = _2d(g_out.contiguous())
+    sg, sb = GradSink(bn.gamma), GradSink(bn.beta)
+    # ReLU mask: recomputed from y when there is no residual, else the forward output (fp32), or - when that was never materialised in
+    # fp32 - the bit mask bn_apply wrote (else the hi halves of the bf16 pair copy)
+    mask_src, mode = None, 0
+    if relu and want_res:
+        mask_src, mode = (out2d, 0) if out2d is not None else ((relu_bits, 2) if relu_bits is not None else (ob, 1))
+        assert mask_src is not None, "a residual unit without an fp32 output keeps its ReLU bit mask"
+    pre = gi.bnb_parts                          # the reduction came with the gradient (fused into the consumer's epilogue)
+    # The skip gradient of a residual unit is g_out * mask.  With the bit mask at hand it is not written out: the incoming gradient
+    # tensor itself is handed to the shortcut's producer tagged with the mask, and the consumers that know the tag (the 1x1
+    # backward-data of _p16_input_grad, the projection shortcut's BatchNorm backward) fold the mask into their own kernels - one
+    # 4-byte-per-element write per unit less (engine.materialise is the fallback).
+    lazy_skip = want_res and mode == 2 and LAZY_SKIP and gi.owned and lazy_bits is None and g_out.is_contiguous()
+    bn_relu = relu
+    if lazy_bits is not None:                   # this BatchNorm has no ReLU of its own: apply the incoming mask instead
+        mask_src, mode, bn_relu = lazy_bits, 2, True
+    even = gi.even_pixels if (EVEN_PIXELS and gi.even_pixels == omap) else None      # zero off the even pixels: a quarter-size reduction pass
+    if compact is not None:
+        assert lazy_skip and pre is None, "a compact even-pixel gradient is handed on to the skip merge as it is"
+        even = compact
+    dyb, _, _, _, dres = K.bn_bwd_p16(g2d, mask_src, y2d, mean, rstd, bn.gamma.value, bn_relu, False, want_residual_grad=want_res and not lazy_skip,
+                                      dgamma=sg.buf, dbeta=sb.buf, beta=bn.beta.value, out_p16=mode, pre=pre, even_pixels=even,
+                                      dout_compact=compact is not None)
+    if lazy_skip:
+        dres = own(g_out.view(res_shape) if compact is None else g_out)      # (compact: keeps its `compact_even` tag)
+        ri = tag(dres)
+        ri.lazy_mask = relu_bits
+        if gi.bnb_parts_shortcut is not None and res_bn is not None:
+            ri.bnb_parts = gi.bnb_parts_shortcut      # the shortcut's BatchNorm backward finds its reduction done (it reads them as `pre`)
+    elif want_res:
+        dres = own(dres.view(res_shape))
+    sg.commit()
+    sb.commit()
+    return dyb, (dres if want_res else None)
+
+
+def _p16_input_grad(dyb4, w: Variable, g, xa: ActInfo, acc):
+    """Input gradient of a pre-split convolution.  Which backward-data kernel runs depends on what is already accumulated for x
+    (acc[0], offered by the Tape: accumulate into it, or put the tensor that replaces it there) and on what the handle of x (`xa`)
+    asks its consumer's epilogue to reduce.  The ORDER of the cases is part of the behaviour."""
+    N, H, W, Cin = g.N, g.H, g.W, g.C
+    imap = (N, H, W)
+    one = g.R == 1 and g.S == 1 and g.pad == 0
+    s1, s2 = one and g.stride == 1, one and g.stride == 2
+    # a stride-2 1x1 convolution's input gradient lives at the pixels (2i, 2j): on an even map it is produced as the compact
+    # [N, H/2, W/2, C] tensor - a plain dense product over the OUTPUT grid - and tagged; see _p16_bn_backward
+    s2c = s2 and COMPACT_S2 and H % 2 == 0 and W % 2 == 0
+    gc = K.ConvGeom(N, g.OH, g.OW, Cin, g.K, 1, 1, 1, 0) if s2c else None
+    keep_even = imap if s2 else None            # (an even-pixel tag survives further stride-2 1x1 contributions on its map)
+    _, wt = _PACKED.get(w)
+    have = acc[0] if acc is not None else None
+    hi = info(have)
+    if hi.compact_even is not None:
+        if s2c and hi.compact_even == imap and hi.lazy_mask is None:
+            # the other stride-2 consumer of x was first: add into its compact tensor
+            K.p16_conv2d_bwd_data(dyb4, wt, gc, dx=have.view(N, g.OH, g.OW, Cin), accumulate=True)
+            return have
+        if hi.lazy_mask is not None and s1 and hi.compact_even == imap and xa.bn_ctx_bits2 is None:
+            # the skip merge of a stage's last unit: conv_transpose(dy) + expand(compact gradient) * mask into a FRESH dense tensor
+            # (+ the previous unit's BatchNorm-backward sums, when its handle asks for them)
+            dx = acc[0] = own(K.empty(N, H, W, Cin, like=dyb4))
+            r = K.p16_conv2d_bwd_data_masked_accum(dyb4, wt, g, dx, hi.lazy_mask, bn_ctx=xa.bn_ctx_bits, old_even=have)
+            if xa.bn_ctx_bits is not None:
+                tag(dx).bnb_parts = r[1]
+            return dx
+        # a compact tensor meets anything else: the dense form (a new tensor), then the plain accumulate
+        dx = acc[0] = materialise(have)
+        K.p16_conv2d_bwd_data(dyb4, wt, g, dx=dx.view(N, H, W, Cin), accumulate=True)
+        dense_contribution(dx, keep_even)
+        return dx
+    if have is not None:
+        dense_contribution(have, keep_even)
+        if hi.lazy_mask is not None and s1:
+            # masked accumulate: the skip merge of a residual unit in this epilogue.  Where it completes the previous unit's output
+            # gradient it does that unit's BatchNorm-backward sums too, and those of its projection shortcut's BatchNorm
+            r = K.p16_conv2d_bwd_data_masked_accum(dyb4, wt, g, have.view(N, H, W, Cin), hi.lazy_mask, bn_ctx=xa.bn_ctx_bits,
+                                                   bn_ctx2=xa.bn_ctx_bits2)
+            if xa.bn_ctx_bits is not None:
+                hi.bnb_parts = r[1]
+                if xa.bn_ctx_bits2 is not None:
+                    hi.bnb_parts_shortcut = r[2]
+            hi.lazy_mask = None
+        else:
+            K.p16_conv2d_bwd_data(dyb4, wt, g, dx=materialise(have).view(N, H, W, Cin), accumulate=True)
+        return have
+    if xa.bn_ctx is not None and g.stride == 1:
+        # fresh, with the BatchNorm-backward sums of the producer of x
+        dx, parts = K.p16_conv2d_bwd_data_bnstats(dyb4, wt, g, *xa.bn_ctx)
+        tag(dx).bnb_parts = parts
+    elif s2c:
+        dx = K.p16_conv2d_bwd_data(dyb4, wt, gc)
+        tag(dx).compact_even = imap
+    else:
+        # a dense stride-2 1x1 gradient is zero-filled, then written at the pixels (2i, 2j) only: the tag lets the producer's BatchNorm
+        # backward reduce over those pixels alone
+        dx = K.p16_conv2d_bwd_data(dyb4, wt, g)
+        if s2:
+            tag(dx).even_pixels = imap
+    return own(dx)
 
 
 def conv_act(x: torch.Tensor, w: Variable, b: Variable, stride: int, pad: int, act: int) -> torch.Tensor:
@@ -490,18 +553,8 @@ def conv_act(x: torch.Tensor, w: Variable, b: Variable, stride: int, pad: int, a
             dpre = K.relu_bwd(y, g_out)
         else:
             dpre = g_out
-        if w.needs_grad or b.needs_grad:
-            def param_grads(dpre=dpre):
-                if w.needs_grad:
-                    s = GradSink(w)
-                    K.conv2d_bwd_weight(x, dpre, g, dw=s.buf, prezeroed=s.mode == "direct")
-                    s.commit()
-                if b.needs_grad:
-                    s = GradSink(b)
-                    K.colsum(_2d(dpre), out=s.buf, prezeroed=s.mode == "direct")
-                    s.commit()
-            side_task(param_grads, x, dpre)
-        return (_own(K.conv2d_bwd_data(dpre, w.value, g)),)
+        _param_grads_task(w, b, lambda dw, pz: K.conv2d_bwd_weight(x, dpre, g, dw=dw, prezeroed=pz), _2d(dpre), x, dpre)
+        return (own(K.conv2d_bwd_data(dpre, w.value, g)),)
 
     _rec([y], [x], backward)
     return y
@@ -517,7 +570,7 @@ def batchnorm(x: torch.Tensor, bn: BNState, training: bool, bessel: bool) -> tor
 
     def backward(g_out):
         dx, _ = _bn_backward(_2d(g_out.contiguous()), None, x2d, mean, rstd, bn, False, not training, False)
-        return (_own(dx.view(x.shape)),)
+        return (own(dx.view(x.shape)),)
 
     _rec([out], [x], backward)
     return out
@@ -525,7 +578,7 @@ def batchnorm(x: torch.Tensor, bn: BNState, training: bool, bessel: bool) -> tor
 
 def maxpool(x: torch.Tensor) -> torch.Tensor:
     y = K.maxpool_fwd(x)
-    _rec([y], [x], lambda g: (_own(K.maxpool_bwd(x, y, g.contiguous())),))
+    _rec([y], [x], lambda g: (own(K.maxpool_bwd(x, y, g.contiguous())),))
     return y
 
 
@@ -552,14 +605,14 @@ def conv_bn_relu_maxpool(x: torch.Tensor, w: Variable, b: Variable, bn: BNState,
     _, out, tap = K.stem_pool_fwd(y, mean, rstd, bn.gamma.value, bn.beta.value)
     # `out` IS the f16 pair copy.  The alias must not lead back to `out`: `out` itself is a cycle through its own __dict__ (freed only by
     # the cyclic GC: 105 MB per step at batch 16), and a VIEW is worse - its C-level `_base` edge is invisible to the GC, so the cycle
-    # out -> view -> out is never collected (round 5's first fix leaked 100 MB per eager step: profiles/r05_soak_2000steps_eager_leak.txt).
+    # out -> view -> out is never collected (that leaked 100 MB per eager step: profiles/r05_soak_2000steps_eager_leak.txt).
     # detach() shares the storage and holds no reference to the tensor object.
-    out._p16f, out._p16b, out._p16_only = out.detach(), None, True
+    attach_packed(out, out.detach(), p16_only=True)
 
     def backward(g_out):
         sg, sb = GradSink(bn.gamma), GradSink(bn.beta)
         # The weight gradient of the 7x7 / stride-2 / pad-3 stem over a 4-channel image with even sides runs on the pre-split XX kernel
-        # through a space-to-depth view (kernels.stem_bwd_weight_s2d, round 5): it is the LAST kernel of the backward pass, alone on the chip
+        # through a space-to-depth view (kernels.stem_bwd_weight_s2d): it is the LAST kernel of the backward pass, alone on the chip
         # with the optimizer waiting for it.  dy is then written as its bf16 pair.  Gradient products under 'split' are bf16 pairs on
         # both paths; any other backward policy, deterministic mode and other geometries keep igemm.hip's kernel.
         s2d = (STEM_S2D and w.needs_grad and (R, S, stride, pad, Cin) == (7, 7, 2, 3, 4) and H % 2 == 0 and W % 2 == 0 and Kout % 64 == 0
@@ -568,21 +621,10 @@ def conv_bn_relu_maxpool(x: torch.Tensor, w: Variable, b: Variable, bn: BNState,
                                    dy_p16=s2d)
         sg.commit()
         sb.commit()
-        if w.needs_grad or b.needs_grad:
-            def param_grads(dy=dy):
-                if w.needs_grad:
-                    s = GradSink(w)
-                    if s2d:
-                        K.stem_bwd_weight_s2d(x32, dy, s.buf)
-                    else:
-                        K.conv2d_bwd_weight(x32, dy, g, dw=s.buf, prezeroed=s.mode == "direct")
-                    s.commit()
-                if b.needs_grad:
-                    s = GradSink(b)             # exactly zero in front of a batch-statistics BatchNorm (see conv_bn)
-                    if s.mode != "direct":
-                        K.zero_(s.buf)
-                    s.commit()
-            side_task(param_grads, x32, dy)
+        if s2d:
+            _param_grads_task(w, b, lambda dw, pz: K.stem_bwd_weight_s2d(x32, dy, dw), None, x32, dy)
+        else:
+            _param_grads_task(w, b, lambda dw, pz: K.conv2d_bwd_weight(x32, dy, g, dw=dw, prezeroed=pz), None, x32, dy)
         return (None,)
 
     _rec([out], [x], backward)
@@ -604,25 +646,14 @@ def dense(x: torch.Tensor, w: Variable, b: Variable, act: int = K.ACT_NONE) -> t
             g2d = K.relu_bwd(y2d, g2d)
         elif act == K.ACT_TANH:
             g2d = K.tanh_bwd(y2d, g2d)
-        if w.needs_grad or b.needs_grad:
-            def param_grads(g2d=g2d):
-                if w.needs_grad:
-                    s = GradSink(w)
-                    K.linear_bwd_weight(g2d, x2d, dw=s.buf, prezeroed=s.mode == "direct")
-                    s.commit()
-                if b.needs_grad:
-                    s = GradSink(b)
-                    K.colsum(g2d, out=s.buf, prezeroed=s.mode == "direct")
-                    s.commit()
-            side_task(param_grads, x2d, g2d)
+        _param_grads_task(w, b, lambda dw, pz: K.linear_bwd_weight(g2d, x2d, dw=dw, prezeroed=pz), g2d, x2d, g2d)
         have = acc[0] if acc is not None else None
         if have is not None and have.is_contiguous() and have.shape == x.shape:
             # another consumer's gradient of x is already there: add into it in the GEMM epilogue (no separate axpy pass)
             K.linear_bwd_data(g2d, w.value, dx=_2d(materialise(have)), accumulate=True)
-            if hasattr(have, "_even_pixels"):
-                del have._even_pixels
+            dense_contribution(have)
             return (have,)
-        return (_own(K.linear_bwd_data(g2d, w.value).view(x.shape)),)
+        return (own(K.linear_bwd_data(g2d, w.value).view(x.shape)),)
 
     backward.wants_acc = True
     _rec([y], [x], backward)
@@ -668,7 +699,7 @@ def dense_group(xs, ws, bs):
         if any(w.needs_grad or b.needs_grad for w, b in zip(ws, bs)):
             side_task(param_grads, *x2, *g2)
         dxs = K.linear_bwd_data_group(g2, [w.value for w in ws])
-        return tuple(_own(dx.view(x.shape)) for dx, x in zip(dxs, xs))
+        return tuple(own(dx.view(x.shape)) for dx, x in zip(dxs, xs))
 
     _rec(ys, list(xs), backward)
     return ys
@@ -732,9 +763,7 @@ def reshape(x: torch.Tensor, shape) -> torch.Tensor:
 
     def backward(g):
         r = g.contiguous().view(x.shape)
-        if getattr(g, "_bdetr_owned", False):
-            r._bdetr_owned = True
-        return (r,)
+        return (own(r) if info(g).owned else r,)
 
     _rec([y], [x], backward)
     return y
@@ -755,7 +784,7 @@ def attention_core(Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, heads: in
 
         def backward_fused(gO):
             dQ, dK, dV = K.attention_bwd(Q, Kt, V, O, gO.contiguous(), lse, heads, scale)
-            return _own(dQ), _own(dK), _own(dV)
+            return own(dQ), own(dK), own(dV)
 
         _rec([O], [Q, Kt, V], backward_fused)
         return O
@@ -780,7 +809,7 @@ def attention_core(Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, heads: in
         K.gemm_raw(q, d, kk, dS, kk, True, Kt, D, False, dQ, D, nb0=B, nb1=heads, sa=sP, sb=(kk * D, d), sc=(q * D, d), grad=True)
         dK = K.empty(B, kk, D, like=Q)
         K.gemm_raw(kk, d, q, dS, kk, False, Q, D, False, dK, D, nb0=B, nb1=heads, sa=sP, sb=(q * D, d), sc=(kk * D, d), grad=True)
-        return _own(dQ), _own(dK), _own(dV)
+        return own(dQ), own(dK), own(dV)
 
     _rec([O], [Q, Kt, V], backward)
     return O
@@ -805,7 +834,7 @@ def add_dropout_layernorm(x: torch.Tensor, y: torch.Tensor, gamma: Variable, bet
                                                    dgamma=sg.buf, dbeta=sb.buf, seed_base=base)
         sg.commit()
         sb.commit()
-        return _own(dx.view(x.shape)), _own(dy.view(y.shape))
+        return own(dx.view(x.shape)), own(dy.view(y.shape))
 
     _rec([out], [x, y], backward)
     return out
@@ -823,37 +852,14 @@ def rowchain_active(width: int) -> bool:
     return ROWCHAIN[0] and width == K.ROWCHAIN_WIDTH and K.get_gemm_precision() == "split"
 
 
-class _RowchainPacks:
-    """Forward (f16 pairs of 2^8 W, MFMA fragment order) and backward (bf16 pairs of W^T) copies of every Dense kernel on a row
-    chain, in persistent buffers, refreshed by ONE multi-matrix launch the first time a copy is asked for after the weights changed
-    (the same scheme as _PackedWeights for the conv kernels)."""
-
-    def __init__(self):
-        self.rows, self.table, self.version = [], None, -1
-
-    def get(self, w: Variable):
-        import weakref
-        c = getattr(w, "_rc", None)
-        if c is None or c[0].data_ptr() != w.value.data_ptr():
-            from . import _lib
-            n = int(_lib.lib().bdetr_rowchain_pack_elems())
-            dev = w.value.device
-            c = (w.value, torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
-            w._rc = c
-            self.rows = [r for r in self.rows if r[0]() is not None and r[0]() is not w]
-            self.rows.append((weakref.ref(w),) + c)
-            self.table, self.version = None, -1
-        if self.version != WEIGHTS_VERSION[0]:
-            if self.table is None:
-                import numpy as np
-                rows = np.array([[v.data_ptr(), f.data_ptr(), b.data_ptr()] for _, v, f, b in self.rows], np.int64)
-                self.table = torch.from_numpy(rows).to(w.value.device)
-            K.rowchain_pack_weights(self.table)
-            self.version = WEIGHTS_VERSION[0]
-        return c[1], c[2]
+def _rowchain_pack_buffers(v: torch.Tensor):
+    n = int(_lib.lib().bdetr_rowchain_pack_elems())
+    return torch.empty(n, dtype=torch.float32, device=v.device), torch.empty(n, dtype=torch.float32, device=v.device)
 
 
-_RC_PACKED = _RowchainPacks()
+# Dense kernels on a row chain: (f16 pairs of 2^8 W in MFMA fragment order, bf16 pairs of W^T)
+_RC_PACKED = _PackCache(_rowchain_pack_buffers, lambda v, f, t: [v.data_ptr(), f.data_ptr(), t.data_ptr()],
+                        K.rowchain_pack_weights)
 
 
 def attention_out_chain(ctx: torch.Tensor, resid: torch.Tensor, out_proj, ln1, ffn, eps: float, rate: float, training: bool) -> torch.Tensor:
@@ -899,15 +905,8 @@ def attention_out_chain(ctx: torch.Tensor, resid: torch.Tensor, out_proj, ln1, f
         dctx = K.linear_bwd_data(da, Wo.value)
         todo.append((Wo, bo, da, ctx2d))
         for w, b, g, x in todo:
-            if w.needs_grad:
-                s_ = GradSink(w)
-                K.linear_bwd_weight(g, x, dw=s_.buf, prezeroed=s_.mode == "direct")
-                s_.commit()
-            if b.needs_grad:
-                s_ = GradSink(b)
-                K.colsum(g, out=s_.buf, prezeroed=s_.mode == "direct")
-                s_.commit()
-        return _own(dctx.view(ctx.shape)), _own(dres.view(resid.shape))
+            _write_param_grads(w, b, lambda dw, pz, g=g, x=x: K.linear_bwd_weight(g, x, dw=dw, prezeroed=pz), g)
+        return own(dctx.view(ctx.shape)), own(dres.view(resid.shape))
 
     def backward(g_out):
         if K.get_gemm_precision() != "split":
@@ -930,7 +929,7 @@ def attention_out_chain(ctx: torch.Tensor, resid: torch.Tensor, out_proj, ln1, f
                 for t in todo:
                     t[3].commit()
         side_task(param_grads, partials, *G, *xs)
-        return _own(dctx.view(ctx.shape)), _own(dres.view(resid.shape))
+        return own(dctx.view(ctx.shape)), own(dres.view(resid.shape))
 
     _rec([out], [ctx, resid], backward)
     return out
@@ -941,18 +940,18 @@ def attention_out_chain(ctx: torch.Tensor, resid: torch.Tensor, out_proj, ln1, f
 # ----------------------------------------------------------------------------------------
 def softmax_lastdim(x: torch.Tensor) -> torch.Tensor:
     p = K.softmax_rows_fwd(_2d(x), 1.0).view(x.shape)
-    _rec([p], [x], lambda g: (_own(K.softmax_rows_bwd(_2d(p), _2d(g.contiguous()), 1.0).view(x.shape)),))
+    _rec([p], [x], lambda g: (own(K.softmax_rows_bwd(_2d(p), _2d(g.contiguous()), 1.0).view(x.shape)),))
     return p
 
 
 def sigmoid(x: torch.Tensor) -> torch.Tensor:
     y = K.sigmoid_fwd(x)
-    _rec([y], [x], lambda g: (_own(K.sigmoid_bwd(y, g.contiguous())),))
+    _rec([y], [x], lambda g: (own(K.sigmoid_bwd(y, g.contiguous())),))
     return y
 
 
 def box_sigmoid(x: torch.Tensor) -> torch.Tensor:
     """3*sigmoid(x/100) - 1  (prediction_heads.py:44)."""
     y = K.boxsigmoid_fwd(x)
-    _rec([y], [x], lambda g: (_own(K.boxsigmoid_bwd(y, g.contiguous())),))
+    _rec([y], [x], lambda g: (own(K.boxsigmoid_bwd(y, g.contiguous())),))
     return y

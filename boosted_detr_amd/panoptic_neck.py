@@ -19,7 +19,7 @@ import torch
 
 from . import kernels as K
 from .engine import Layer, current_tape, side_task
-from .ops import GradSink, _own, _rec
+from .ops import GradSink, own, _rec
 
 LN_EPS = 1e-3            # tf.keras.layers.LayerNormalization default
 LEAKY = 0.01             # ReLU(negative_slope=.01)
@@ -56,7 +56,7 @@ def conv_packed(x: torch.Tensor, kernel, bias, transpose: bool, stride: int, pad
                     if sink is not None:
                         sink.commit()
             side_task(param_grads, x, g, w)
-        return (_own(K.conv2d_bwd_data(g, w, geom)),)
+        return (own(K.conv2d_bwd_data(g, w, geom)),)
 
     _rec([y], [x], backward)
     return y
@@ -72,7 +72,7 @@ def layernorm_act(y: torch.Tensor, C: int, gamma, beta, slope: float) -> torch.T
         dy, _, _ = K.layernorm_act_bwd(y, C, gamma.value, beta.value, LN_EPS, slope, g.contiguous(), dgamma=sg.buf, dbeta=sb.buf)
         sg.commit()
         sb.commit()
-        return (_own(dy),)
+        return (own(dy),)
 
     _rec([out], [y], backward)
     return out
@@ -80,7 +80,7 @@ def layernorm_act(y: torch.Tensor, C: int, gamma, beta, slope: float) -> torch.T
 
 def resize_bilinear(x: torch.Tensor, H: int, W: int) -> torch.Tensor:
     y = K.resize_bilinear(x, H, W)
-    _rec([y], [x], lambda g: (_own(K.resize_bilinear_bwd(g.contiguous(), x.shape[1], x.shape[2])),))
+    _rec([y], [x], lambda g: (own(K.resize_bilinear_bwd(g.contiguous(), x.shape[1], x.shape[2])),))
     return y
 
 
@@ -106,7 +106,7 @@ def concat(parts):
             d = K.empty(*t.shape, like=g)
             if t.shape[-1] != c:
                 K.zero_(d)
-            gins.append(_own(K.copy_cols(g, c, d, 0, src_col0=col)))
+            gins.append(own(K.copy_cols(g, c, d, 0, src_col0=col)))
             col += c
         return tuple(gins)
 
@@ -117,7 +117,7 @@ def concat(parts):
 def nhwc_to_nchw(y: torch.Tensor, C: int) -> torch.Tensor:
     N, H, W, ld = y.shape
     out = K.nhwc_to_nchw(y, C)
-    _rec([out], [y], lambda g: (_own(K.nchw_to_nhwc(g.contiguous(), H, W, ld)),))
+    _rec([out], [y], lambda g: (own(K.nchw_to_nhwc(g.contiguous(), H, W, ld)),))
     return out
 
 

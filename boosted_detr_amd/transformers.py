@@ -361,7 +361,7 @@ class PanopticAttention(Layer):
             dvalue = K.linear_bwd_data(dv, Vp.kernel.value)
             K.linear_bwd_data(dk, Kp.kernel.value, dx=dvalue, accumulate=True)
             K.linear_bwd_data(dq, Qp.kernel.value, dx=dvalue, accumulate=True)
-            return (ops._own(dvalue),)
+            return (ops.own(dvalue),)
 
         tape.record([y], [value], backward)
         return y

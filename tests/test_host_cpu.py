@@ -75,6 +75,42 @@ def test_variable_layout_roundtrip(monkeypatch):
     assert tuple(d.value.shape) == (9, 5) and np.array_equal(d.numpy(), w)
 
 
+def test_gradient_tag_rules_of_a_dense_contribution():
+    """engine.GradInfo: a dense contribution added to an accumulated gradient ends its BatchNorm partial sums (both kinds) and its
+    even-pixel tag - except that a further stride-2 1x1 contribution on the same (N, H, W) keeps the tag - and leaves ownership and a
+    lazy mask alone; reading the record of an untagged tensor allocates nothing on it."""
+    import torch
+    from boosted_detr_amd.engine import GradInfo, dense_contribution, info, own, tag
+    plain = torch.zeros(2, 4, 4, 8)
+    empty = info(plain)
+    assert empty is info(None) and empty is info(torch.zeros(1)) and "_grad_info" not in plain.__dict__
+    assert (empty.owned, empty.lazy_mask, empty.compact_even, empty.even_pixels, empty.bnb_parts, empty.bnb_parts_shortcut) == (False,) + (None,) * 5
+    dense_contribution(plain)                       # nothing to drop, and the shared empty record stays empty and unattached
+    assert "_grad_info" not in plain.__dict__ and info(plain) is empty and empty.even_pixels is None and empty.bnb_parts is None
+
+    def tagged():
+        g = own(torch.zeros(2, 4, 4, 8))
+        r = tag(g)
+        assert isinstance(r, GradInfo) and r is info(g) and r is tag(g) and r is not empty
+        r.lazy_mask, r.even_pixels, r.bnb_parts, r.bnb_parts_shortcut = torch.ones(4, dtype=torch.int64), (2, 4, 4), ("g", "gx", 3), ("s",)
+        return g, r
+
+    g, r = tagged()
+    mask = r.lazy_mask
+    dense_contribution(g)
+    assert r.bnb_parts is None and r.bnb_parts_shortcut is None and r.even_pixels is None
+    assert r.owned is True and r.lazy_mask is mask and info(g) is r
+    g, r = tagged()
+    mask = r.lazy_mask
+    dense_contribution(g, keep_even=(2, 4, 4))      # a stride-2 1x1 contribution on the same map writes the even pixels only
+    assert r.even_pixels == (2, 4, 4) and r.bnb_parts is None and r.bnb_parts_shortcut is None and r.owned is True and r.lazy_mask is mask
+    g, r = tagged()
+    dense_contribution(g, keep_even=(2, 8, 8))      # ... on another map it is a dense contribution like any other
+    assert r.even_pixels is None and r.bnb_parts is None and r.bnb_parts_shortcut is None
+    with pytest.raises(AttributeError):
+        r.lazy_msak = None                          # a misspelt field is an error, not a silently ignored tag
+
+
 def test_initializers_statistics():
     from boosted_detr_amd.engine import initializer
     w = initializer("glorot_normal")("x", (256, 256))

@@ -97,7 +97,7 @@ def test_stem_op_fused_equals_unfused(cuda, B, H):
                 tape = Tape()
                 with recording(tape):
                     out = ops.conv_bn_relu_maxpool(x, st.kernel, st.bias, st.bn, st.stride, st.pad, True, True)
-                assert bool(getattr(out, "_p16_only", False)) == fused
+                assert ops.is_p16_only(out) == fused
                 tape.backward({id(out): gout.clone()})
                 join_side_stream()
                 torch.cuda.synchronize()
