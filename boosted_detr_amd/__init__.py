@@ -78,7 +78,10 @@ def __getattr__(name):
     if name == "BoostedDETR":
         from .boosted_model import BoostedDETR
         return BoostedDETR
-    if name in ("SGD", "AdamW", "Adam", "CosineDecayRestarts", "ModelCheckpoint", "TerminateOnNaN", "TensorBoard", "latest_checkpoint"):
+    if name in ("SGD", "AdamW", "Adam", "CosineDecayRestarts", "ModelCheckpoint", "TerminateOnNaN", "TensorBoard", "latest_checkpoint", "DetectionAP"):
         from . import training
         return getattr(training, name)
+    if name == "DetectionEvaluator":
+        from .evaluation import DetectionEvaluator
+        return DetectionEvaluator
     raise AttributeError(name)

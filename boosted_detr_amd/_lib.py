@@ -191,6 +191,8 @@ SIGNATURES = {
     "bdetr_sgd_slab_elems": (I, []),
     "bdetr_sgd_nesterov_clipnorm": (I, [P, P, I, P, P, I, P, P, P, F, F, F, P, P]),
     "bdetr_adamw_clipnorm": (I, [P, P, I, P, P, I, P, P, P, P, F, F, F, F, F, F, F, P, P]),
+    "bdetr_det_postprocess": (I, [P, I, I, I, P, P, P]),
+    "bdetr_det_match": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P]),
 }
 
 

@@ -8,7 +8,7 @@ the matcher + loss run on the cumulative predictions of every learner (232-243).
 from __future__ import annotations
 
 from . import backbone, losses_and_metrics, ops, prediction_heads, tokenizers, transformers
-from .model import DETR, _image, _prepare_targets
+from .model import DETR, _image, _inference_outputs, _prepare_targets
 from .training import Model
 
 
@@ -60,7 +60,7 @@ class BoostedDETR(Model):
     get_config = DETR.get_config
     _register = DETR._register
 
-    def call(self, inputs, training=False):
+    def call(self, inputs, training=False, raw=False):
         focused_training_layer = None          # hard-coded in the reference (boosted_model.py:171)
         image = _image(inputs)
         if training:
@@ -95,8 +95,7 @@ class BoostedDETR(Model):
         if training:
             self._register(loss_terms, metrics_i)
             return y_pred
-        category, attributes = self.InverseTokenization([cat_preds, attribute_preds], training=training)
-        return category, attributes, box_coord_preds
+        return _inference_outputs(self, cat_preds, attribute_preds, box_coord_preds, raw)
 
     def citation(self):
         print("Boosted-ensemble adaptation of DETR for object detection and fine-grained classification; "

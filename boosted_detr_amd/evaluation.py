@@ -1,0 +1,143 @@
+"""COCO-style box average precision for DETR / BoostedDETR.
+
+The reference trains and never evaluates; this is the missing half of the Keras surface (``Model.evaluate``).  The per-image work -
+turning queries into detections, ranking them, matching them to the ground truths at every IoU threshold - runs on the GPU
+(csrc/detmetric.hip, include/bdetr.h K14) and leaves a few bytes per detection in HBM; ``DetectionEvaluator.update`` reads
+nothing back.  ``result`` copies what was kept to the host once and runs COCOeval's ``accumulate`` there in NumPy fp64.
+
+Deviations from pycocotools' COCOeval: no crowd regions (``iscrowd``), no area ranges (everything is "all"), one ``max_dets``.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+
+KEEP_BIT = 0x8000
+MAX_THRESHOLDS = 15
+RECALL_POINTS = np.linspace(0.0, 1.0, 101)
+
+
+def accumulate(records: Sequence[tuple], gt_count, iou_thresholds) -> Dict[str, object]:
+    """COCOeval.accumulate over what the matching kernel left.
+
+    records: per batch, in arrival order, ``(score f32 [B,N], label i32 [B,N], tp_bits u16 [B,N], order i32 [B,N])`` host arrays;
+    gt_count: ground truths per class [C]; iou_thresholds: the T thresholds the bits of ``tp_bits`` stand for.
+    Per class the detections are lined up image by image, each image's in the kernel's ``order``, and sorted by descending
+    score with a stable sort; a class without ground truth takes part in no mean."""
+    thr = np.asarray(iou_thresholds, np.float64).reshape(-1)
+    gt_count = np.asarray(gt_count, np.int64).reshape(-1)
+    T, C = thr.size, gt_count.size
+    scores, labels, bits = [], [], []
+    for score, label, tp_bits, order in records:
+        order = np.asarray(order, np.int64)
+        ok = order >= 0
+        idx = np.where(ok, order, 0)
+        s = np.take_along_axis(np.asarray(score, np.float32), idx, 1)[ok]
+        l = np.take_along_axis(np.asarray(label, np.int64), idx, 1)[ok]
+        t = np.take_along_axis(np.asarray(tp_bits).astype(np.int64) & 0xFFFF, idx, 1)[ok]      # row-major: image by image, ranked
+        kept = (t & KEEP_BIT) != 0
+        scores.append(s[kept]); labels.append(l[kept]); bits.append(t[kept])
+    scores = np.concatenate(scores) if scores else np.zeros(0, np.float32)
+    labels = np.concatenate(labels) if labels else np.zeros(0, np.int64)
+    bits = np.concatenate(bits) if bits else np.zeros(0, np.int64)
+
+    R = RECALL_POINTS.size
+    precision = np.full((T, R, C), -1.0)
+    recall = np.full((T, C), -1.0)
+    eps = np.spacing(1.0)
+    for c in np.flatnonzero(gt_count > 0):
+        sel = labels == c
+        rank = np.argsort(-scores[sel].astype(np.float64), kind="stable")
+        b = bits[sel][rank]
+        tp = ((b[None, :] >> np.arange(T)[:, None]) & 1).astype(np.float64)       # [T, D]
+        tp_sum, fp_sum = np.cumsum(tp, axis=1), np.cumsum(1.0 - tp, axis=1)
+        nd = b.size
+        rc = tp_sum / float(gt_count[c])
+        pr = tp_sum / (tp_sum + fp_sum + eps)
+        pr = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]                  # the right-to-left monotone envelope
+        recall[:, c] = rc[:, -1] if nd else 0.0
+        for t in range(T):
+            at = np.searchsorted(rc[t], RECALL_POINTS, side="left")
+            q = np.zeros(R)
+            inside = at < nd
+            q[inside] = pr[t, at[inside]]
+            precision[t, :, c] = q
+    valid = gt_count > 0
+
+    def mean_ap(rows) -> float:
+        p = precision[rows][:, :, valid]
+        return float(p.mean()) if p.size else float("nan")
+
+    def at_threshold(value: float) -> float:
+        hit = np.flatnonzero(np.isclose(thr, value, rtol=0.0, atol=1e-9))
+        return mean_ap(hit[:1]) if hit.size else float("nan")
+
+    per_class = np.full(C, np.nan)
+    if T:
+        per_class[valid] = precision[:, :, valid].mean(axis=(0, 1))
+    r = recall[:, valid]
+    return {"AP": mean_ap(np.arange(T)), "AP50": at_threshold(0.5), "AP75": at_threshold(0.75),
+            "AR": float(r.mean()) if r.size else float("nan"),
+            "per_class_AP": per_class, "num_detections": int(bits.size), "num_ground_truths": int(gt_count[valid].sum()),
+            "num_images": int(sum(np.asarray(rec[0]).shape[0] for rec in records)), "gt_count": gt_count.copy()}
+
+
+class DetectionEvaluator:
+    """Running COCO-style box AP.  ``update`` launches bdetr_det_postprocess and bdetr_det_match on the current stream and keeps the
+    per-batch score / label / tp_bits / order tensors and the running per-class ground-truth count in HBM; it reads nothing back.
+    ``result`` makes one device-to-host copy and accumulates on the host (a few bytes per detection, once per evaluation)."""
+
+    def __init__(self, num_classes: int, iou_thresholds=None, max_dets: int = 100):
+        thr = np.linspace(0.5, 0.95, 10) if iou_thresholds is None else np.asarray(iou_thresholds, np.float64).reshape(-1)
+        if not 1 <= thr.size <= MAX_THRESHOLDS:
+            raise ValueError(f"1 to {MAX_THRESHOLDS} IoU thresholds, got {thr.size}")
+        if num_classes < 3:
+            raise ValueError("num_classes counts <PAD> and <OOV>: at least 3")
+        if max_dets < 1:
+            raise ValueError("max_dets must be positive")
+        self.num_classes, self.iou_thresholds, self.max_dets = int(num_classes), thr.astype(np.float64), int(max_dets)
+        self.reset()
+
+    def reset(self) -> None:
+        self._kept: List[tuple] = []          # per batch: (score, label, tp_bits, order) device tensors
+        self._gt_count = None                 # int32 [C] in HBM, allocated by the first update
+        self.last_matched_gt = None           # int32 [B,T,N] of the last batch (inspection / tests)
+
+    def update(self, cat_pred, box_pred, cat_ids, bbox, num_objects) -> None:
+        """cat_pred [B,N,C] probabilities and box_pred [B,N,4] from ``Model.predict_raw``; cat_ids int32 [B,M], bbox f32 [B,M,4]
+        (normalised COCO [x,y,w,h], -10 padding) and num_objects int32 [B] as ``_prepare_targets`` returns them.  All in HBM."""
+        import torch
+        from . import kernels as K
+        if cat_pred.shape[-1] != self.num_classes:
+            raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {self.num_classes}")
+        if self._gt_count is None:
+            self._gt_count = torch.zeros(self.num_classes, dtype=torch.int32, device=cat_pred.device)
+        score, label = K.det_postprocess(cat_pred.contiguous())
+        order, tp_bits, matched = K.det_match(score, label, box_pred.contiguous(), cat_ids.contiguous(), bbox.contiguous(),
+                                              num_objects.reshape(-1).contiguous(), self.iou_thresholds, self.num_classes, self.max_dets,
+                                              self._gt_count)
+        self._kept.append((score, label, tp_bits, order))
+        self.last_matched_gt = matched
+
+    def _to_host(self):
+        """One device-to-host copy: every kept tensor and the ground-truth counts, packed as int32 words."""
+        import torch
+        if not self._kept:
+            return [], np.zeros(self.num_classes, np.int64)
+        parts = []
+        for score, label, tp_bits, order in self._kept:
+            parts += [score.view(torch.int32).reshape(-1), label.reshape(-1), tp_bits.to(torch.int32).reshape(-1), order.reshape(-1)]
+        parts.append(self._gt_count)
+        flat = torch.cat(parts).cpu().numpy()
+        records, o = [], 0
+        for score, *_ in self._kept:
+            shape, n = tuple(score.shape), score.numel()
+            s, l, t, r = (flat[o + k * n: o + (k + 1) * n].reshape(shape) for k in range(4))
+            records.append((s.view(np.float32), l, (t & 0xFFFF).astype(np.uint16), r))
+            o += 4 * n
+        return records, flat[o:].astype(np.int64)
+
+    def result(self) -> Dict[str, object]:
+        records, gt_count = self._to_host()
+        return accumulate(records, gt_count, self.iou_thresholds)

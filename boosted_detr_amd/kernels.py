@@ -10,6 +10,7 @@ import ctypes as C
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1005,6 +1006,40 @@ def set_loss(d: LossDesc, cat_pred, att_pred, box_pred, cat_ids, att_hot, bbox, 
     check(_lib.lib().bdetr_set_loss(C.byref(d), _p(cat_pred), _p(att_pred), _p(box_pred), _p(cat_ids), _p(att_hot), _p(bbox), _p(num_objects),
                                     _p(match), _p(losses), _p(d_cat), _p(d_att), _p(d_box), float(loss_scale), _stream()), "set_loss")
     return losses, d_cat, d_att, d_box
+
+
+# --------------------------------------------------------------------------------------
+# detection metric - csrc/detmetric.hip
+# --------------------------------------------------------------------------------------
+def det_postprocess(cat_pred):
+    """cat_pred [B,N,C] probabilities -> (score f32 [B,N], label int32 [B,N]): first-max argmax over classes 2 .. C-1."""
+    _chk(cat_pred)
+    B, N, Cc = cat_pred.shape
+    score = empty(B, N, like=cat_pred)
+    label = empty(B, N, like=cat_pred, dtype=torch.int32)
+    check(_lib.lib().bdetr_det_postprocess(_p(cat_pred), B, N, Cc, _p(score), _p(label), _stream()), "det_postprocess")
+    return score, label
+
+
+def det_match(score, label, box_pred, gt_label, gt_box, num_objects, thresholds, num_classes: int, max_dets: int, gt_count):
+    """COCOeval's matching of one batch (include/bdetr.h, K14).  thresholds: host fp64 values; gt_count: int32 [num_classes] in HBM,
+    the batch's per-class ground-truth counts are added to it.  Returns (order int32 [B,N], tp_bits int16 [B,N] - the uint16 bit
+    pattern, torch has no arithmetic on uint16 - and matched_gt int32 [B,T,N])."""
+    _chk(score, box_pred, gt_box)
+    _chk(label, gt_label, num_objects, gt_count, dtype=torch.int32)
+    B, N = score.shape
+    M = gt_label.shape[1]
+    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
+    T = int(thr.size)
+    if tuple(label.shape) != (B, N) or tuple(box_pred.shape) != (B, N, 4) or tuple(gt_label.shape) != (B, M) or tuple(gt_box.shape) != (B, M, 4) \
+            or num_objects.numel() != B or gt_count.numel() != num_classes:
+        raise _lib.BdetrError("det_match: operand shapes disagree")
+    order = empty(B, N, like=score, dtype=torch.int32)
+    tp_bits = empty(B, N, like=score, dtype=torch.int16)
+    matched = empty(B, max(T, 1), N, like=score, dtype=torch.int32)
+    check(_lib.lib().bdetr_det_match(_p(score), _p(label), _p(box_pred), _p(gt_label), _p(gt_box), _p(num_objects), thr.ctypes.data, B, N, M,
+                                     int(num_classes), T, int(max_dets), _p(order), _p(tp_bits), _p(matched), _p(gt_count), _stream()), "det_match")
+    return order, tp_bits, matched
 
 
 # --------------------------------------------------------------------------------------

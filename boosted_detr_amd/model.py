@@ -34,6 +34,15 @@ def _prepare_masks(inputs, B: int, M: int) -> torch.Tensor:
     return to_device(masks).reshape(B, M, MASK_GRID * MASK_GRID).contiguous()
 
 
+def _inference_outputs(model, cat_preds, attribute_preds, box_coord_preds, raw: bool = False):
+    """The tail of call(training=False), shared by DETR and BoostedDETR: the decoded strings of the reference, or
+    with raw=True the three prediction tensors as they sit in HBM (Model.predict_raw)."""
+    if raw:
+        return [cat_preds, attribute_preds, box_coord_preds]
+    category, attributes = model.InverseTokenization([cat_preds, attribute_preds], training=False)
+    return category, attributes, box_coord_preds
+
+
 def _image(inputs):
     img = inputs["image"]
     return to_device(img if isinstance(img, torch.Tensor) else np.asarray(img, np.float32))
@@ -119,7 +128,7 @@ class DETR(Model):
                                                  "panoptic_dim", "vocab_dict")})
         return c
 
-    def call(self, inputs, training=False):
+    def call(self, inputs, training=False, raw=False):
         image = _image(inputs)
         if training:
             y_true = _prepare_targets(self, inputs)
@@ -162,8 +171,7 @@ class DETR(Model):
         cat_preds = self.CategoryPredictionHead([decoder_features], training=training)
         attribute_preds = self.AttributePredictionHead([decoder_features], training=training)
         box_coord_preds = self.BoxPredictionHead([decoder_features], training=training)
-        category, attributes = self.InverseTokenization([cat_preds, attribute_preds], training=training)
-        return category, attributes, box_coord_preds
+        return _inference_outputs(self, cat_preds, attribute_preds, box_coord_preds, raw)
 
     def _register(self, loss_terms, metrics_i, mask_loss=None):
         """model.py:206-221.  Per-learner loss vectors are kept as a list (summed on the host when

@@ -640,6 +640,25 @@ class TensorBoard(Callback):
             f.write(json.dumps({"epoch": epoch, **{k: float(v) for k, v in (logs or {}).items()}}) + "\n")
 
 
+class DetectionAP(Callback):
+    """COCO-style box AP on a held-out set at the end of an epoch: Model.evaluate over `validation_data` (at most `steps` batches),
+    every `every` epochs; adds val_AP, val_AP50, val_AP75 and val_AR to that epoch's logs.  Unlike fit(validation_data=...), whose
+    test_step trains (the reference's quirk), this leaves the model as it found it.  Put it before the callbacks that write the logs."""
+
+    def __init__(self, validation_data, every: int = 1, steps: Optional[int] = None, evaluator=None):
+        self.validation_data, self.every, self.steps, self.evaluator = validation_data, max(1, int(every)), steps, evaluator
+        self.history: List[dict] = []
+
+    def on_epoch_end(self, epoch, logs=None):
+        if (epoch + 1) % self.every:
+            return
+        res = self.model.evaluate(self.validation_data, steps=self.steps, evaluator=self.evaluator)
+        vals = {f"val_{k}": float(res[k]) for k in ("AP", "AP50", "AP75", "AR")}
+        self.history.append({"epoch": epoch, **vals})
+        if logs is not None:
+            logs.update(vals)
+
+
 def latest_checkpoint(checkpoint_dir: str) -> Optional[str]:
     files = sorted(glob.glob(os.path.join(checkpoint_dir, "*.safetensors")), key=os.path.getmtime)
     return files[-1] if files else None
@@ -1144,6 +1163,47 @@ class Model(Layer):
 
     def test_step(self, data):
         return self.train_step(data)        # model.py:235-236: validation also trains (quirk kept)
+
+    # -- inference and evaluation ------------------------------------------------------------
+    def predict_raw(self, inputs: dict) -> List[torch.Tensor]:
+        """[cat_preds [B,N,C], attribute_preds [B,N,A], box_preds [B,N,4]] of an inference-mode forward pass, left in HBM (call(training=
+        False) decodes them to strings on the host).  Needs inputs["image"] only."""
+        return self(inputs, training=False, raw=True)
+
+    def detections(self, inputs: dict) -> Dict[str, torch.Tensor]:
+        """Every query as a detection, in HBM: scores f32 [B,N] and labels int32 [B,N] (the most probable class among the vocabulary's,
+        ids >= 2: never <PAD> or <OOV>), boxes f32 [B,N,4] normalised COCO [x,y,w,h]."""
+        cat_preds, _, box_preds = self.predict_raw(inputs)
+        scores, labels = K.det_postprocess(cat_preds.contiguous())
+        return {"scores": scores, "labels": labels, "boxes": box_preds}
+
+    def evaluate(self, x: Iterable[dict], steps: Optional[int] = None, evaluator=None, return_dict: bool = True, verbose: int = 0):
+        """COCO-style box AP over the batches of `x` (dicts as for training: strings or pre-tokenised ids).  Per batch: an inference-mode
+        forward pass and the two kernels of csrc/detmetric.hip, nothing read back; one device-to-host copy at the end (evaluation.py).
+        Changes nothing: weights, moving statistics, optimizer slots and counters, the step seed and captured steps stay as they were.
+        evaluator: a DetectionEvaluator (other thresholds / max_dets); it is reset first.  Returns its result() dict, or with
+        return_dict=False the list [AP, AP50, AP75, AR]."""
+        from .evaluation import DetectionEvaluator
+        from .model import _prepare_targets
+        ev = evaluator if evaluator is not None else DetectionEvaluator(self.num_categories)
+        ev.reset()
+        keep_panoptic = self.__dict__.get("_panoptic_inputs")
+        t0, n = time.time(), 0
+        try:
+            for step, batch in enumerate(x):
+                if steps is not None and step >= steps:
+                    break
+                cat_preds, _, box_preds = self.predict_raw(batch)
+                cat_ids, _, bbox, num_objects = _prepare_targets(self, batch)
+                ev.update(cat_preds, box_preds, cat_ids, bbox, num_objects)
+                n += 1
+        finally:
+            if "_panoptic_inputs" in self.__dict__:
+                self._panoptic_inputs = keep_panoptic      # panoptic_masks() keeps answering for the last call the user made
+        res = ev.result()
+        if verbose:
+            print(f"evaluate - {time.time() - t0:.1f}s - {n} steps - " + " - ".join(f"{k}: {res[k]:.4f}" for k in ("AP", "AP50", "AP75", "AR")))
+        return res if return_dict else [res[k] for k in ("AP", "AP50", "AP75", "AR")]
 
     def step_logs(self) -> Dict[str, list]:
         """name -> list of per-image [B] device tensors (one per weak learner).  Nothing is copied to

@@ -635,6 +635,39 @@ int bdetr_adamw_clipnorm(const uint64_t* ptrs, const int64_t* sizes, int ntensor
                          float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float epsilon,
                          float clipnorm, float grad_scale, int* skip_flag, void* stream);
 
+/* ------------------------------------------------------------------------
+ * K14  detection metric: COCO-style box AP without a host hop per batch (csrc/detmetric.hip; evaluation.py accumulates).
+ *   The reference has no evaluation at all; the rule restated here is pycocotools' COCOeval.evaluateImg for the no-crowd,
+ *   all-areas case with one max_dets.
+ *   bdetr_det_postprocess : cat_pred [B,N,C] probabilities -> label[B,N] = first-max argmax over classes 2 .. C-1 (0 = <PAD>, "no
+ *                           object", and 1 = <OOV> are never a detection's label), score[B,N] = that class's probability (copied).
+ *                           Every query is a detection (DETR's convention).
+ *   bdetr_det_match       : one workgroup per image, one wave per threshold.  box_pred [B,N,4], gt_box [B,M,4]: normalised COCO
+ *                           [x,y,w,h]; gt_label int32 [B,M]; num_objects int32 [B].  thresholds: T doubles in HOST memory, read
+ *                           during the call (they travel as kernel arguments).
+ *       order      : detections in descending score, equal scores in ascending query index (stable);  order[B,N] int32
+ *       truncation : a detection whose rank among the detections of its own class in its image is >= max_dets matches nothing
+ *                    (keep bit 0)
+ *       IoU        : fp64 from the fp32 inputs, every operation rounded on its own (no fused multiply-add):
+ *                    w, h = max(w, 0), max(h, 0); corners x, x + w, y, y + h; iw, ih = max(min(hi) - max(lo), 0);
+ *                    inter = iw * ih; union = (w_d * h_d + w_g * h_g) - inter; iou = union > 0 ? inter / union : 0
+ *       valid gts  : rows m < num_objects[b] whose label is in [2, C)
+ *       matching   : per threshold t, walking the kept detections in `order`: among the ground truths of the detection's label
+ *                    not yet matched at t with iou >= min(thresholds[t], 1 - 1e-10), the one with the largest IoU; on equal IoU
+ *                    the LARGER ground-truth index (COCOeval's `if ious < iou: continue` scan); a matched ground truth is
+ *                    consumed for that t only
+ *       tp_bits    : uint16 [B,N] in query order: bit t = true positive at threshold t, bit 15 = keep
+ *       matched_gt : int32 [B,T,N], the matched ground-truth row or -1
+ *       gt_count   : int32 [C], caller-owned and caller-zeroed: the valid ground truths of every image are ADDED per class
+ *                    (integer atomics: the running total over an evaluation)
+ *   Limits: N <= 1024, M <= 1024, 3 <= C <= 65536, 1 <= T <= 15, max_dets >= 1; anything else returns -1 (bdetr_last_error)
+ *   without a launch.  Inputs are expected to be free of NaN.
+ * ---------------------------------------------------------------------- */
+int bdetr_det_postprocess(const float* cat_pred, int B, int N, int C, float* score, int32_t* label, void* stream);
+int bdetr_det_match(const float* score, const int32_t* label, const float* box_pred, const int32_t* gt_label, const float* gt_box,
+                    const int32_t* num_objects, const double* thresholds, int B, int N, int M, int C, int T, int max_dets,
+                    int32_t* order, uint16_t* tp_bits, int32_t* matched_gt, int32_t* gt_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

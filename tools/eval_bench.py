@@ -1,0 +1,92 @@
+"""Per-batch time of Model.evaluate at the headline config (configs[1]: batch 16, 640 x 640, 6 + 6 layers, 100 queries, COCO
+vocabulary) next to a forward-only predict_raw loop over the same device-resident batches.
+
+Three loops per repetition, each closed by one device synchronisation:
+  forward   predict_raw only
+  update    predict_raw + target preparation + DetectionEvaluator.update (the two detmetric kernels; no host read)
+  evaluate  Model.evaluate: the update loop + result() (one device-to-host copy, host accumulate)
+If update() read anything back per batch, `update` would sit above `forward` by a synchronisation per batch; it should not.
+
+    python tools/eval_bench.py [--batches 8] [--reps 5] [--batch 16] [--image 640] [--layers 6] [--queries 100]
+    rocprofv3 --kernel-trace --stats -d DIR -o eval -- python tools/eval_bench.py --reps 1     # det_* rows: the kernels' own times
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def make_batch(B, H, W, M, C, seed):
+    rng = np.random.Generator(np.random.PCG64(seed))
+    num_objects = np.clip(1 + rng.poisson(6.3, size=B), 1, M).astype(np.int32)
+    category, attribute = np.zeros((B, M), np.int32), np.zeros((B, M, 3), np.int32)
+    bbox = np.full((B, M, 4), -10.0, np.float32)
+    for b in range(B):
+        n = int(num_objects[b])
+        category[b, :n] = rng.integers(2, C, size=n)
+        bbox[b, :n, 0:2] = rng.uniform(0.0, 0.6, size=(n, 2))
+        bbox[b, :n, 2:4] = rng.uniform(0.05, 0.4, size=(n, 2))
+    host = {"image": rng.random((B, H, W, 3), dtype=np.float32), "category": category, "attribute": attribute, "bbox": bbox,
+            "num_objects": num_objects}
+    return {k: torch.from_numpy(v).cuda() for k, v in host.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, default=8)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--image", type=int, default=640)
+    ap.add_argument("--layers", type=int, default=6)
+    ap.add_argument("--queries", type=int, default=100)
+    args = ap.parse_args()
+    from boosted_detr_amd import parameters
+    from boosted_detr_amd.evaluation import DetectionEvaluator
+    from boosted_detr_amd.model import DETR, _prepare_targets
+    model = DETR(num_object_preds=args.queries, image_size=(args.image, args.image), num_encoder_blocks=args.layers, num_encoder_heads=8,
+                 encoder_dim=256, num_decoder_blocks=args.layers, num_decoder_heads=8, decoder_dim=256, num_panoptic_heads=1, panoptic_dim=32,
+                 vocab_dict=parameters.COCO_VOCAB, attribute_weight=0.0)
+    batches = [make_batch(args.batch, args.image, args.image, 100, model.num_categories, 1234 + i) for i in range(args.batches)]
+    ev = DetectionEvaluator(model.num_categories)
+
+    def forward():
+        for b in batches:
+            model.predict_raw(b)
+
+    def update():
+        ev.reset()
+        for b in batches:
+            cat, _, box = model.predict_raw(b)
+            ids, _, bbox, nobj = _prepare_targets(model, b)
+            ev.update(cat, box, ids, bbox, nobj)
+
+    def evaluate():
+        model.evaluate(batches, evaluator=ev)
+
+    loops = {"forward": forward, "update": update, "evaluate": evaluate}
+    for fn in loops.values():            # build-by-first-call, allocator warm-up
+        fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in loops}
+    for _ in range(args.reps):
+        for k, fn in loops.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms[k].append((time.perf_counter() - t0) * 1e3 / args.batches)
+    out = {"config": vars(args), "ms_per_batch": {k: [round(x, 3) for x in v] for k, v in ms.items()},
+           "median_ms_per_batch": {k: round(float(np.median(v)), 3) for k, v in ms.items()},
+           "spread_ms_per_batch": {k: round(float(max(v) - min(v)), 3) for k, v in ms.items()},
+           "result": {k: v for k, v in ev.result().items() if k in ("AP", "AR", "num_detections", "num_ground_truths", "num_images")}}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
