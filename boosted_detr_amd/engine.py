@@ -312,6 +312,15 @@ class Tape:
 _TAPE: Optional[Tape] = None
 _CAPTURE = [None]            # the SegmentedCapture in progress (defined below), or None
 
+
+def capture() -> Optional["SegmentedCapture"]:
+    """The segmented capture in progress, or None."""
+    return _CAPTURE[0]
+
+
+def set_capture(cap: Optional["SegmentedCapture"]) -> None:
+    _CAPTURE[0] = cap
+
 # ----------------------------------------------------------------------------------------
 # side stream: weight-gradient GEMMs run off the critical path
 # ----------------------------------------------------------------------------------------
@@ -521,6 +530,15 @@ def _debug_cut(extra) -> None:
     log.emit("M", ops._live_flat_grad[0])
     log.emit("S", ops._live_flat_grad[0])
     log.eager_pending = 0
+
+
+def cut_after_backward() -> None:
+    """Behind a step's backward pass: close the capture's last backward segment (its side tasks need this step's gradient sinks);
+    in an eager step under the debug log, the diagnostic twin of that cut."""
+    if _CAPTURE[0] is not None:
+        _CAPTURE[0].cut()
+    elif _DEBUG_LOG[0] is not None:
+        _debug_cut(None)
 
 
 class SegmentedCapture:

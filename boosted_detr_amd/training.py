@@ -9,17 +9,20 @@ load_weights(latest_checkpoint)); semantics SURVEY S14/S15.
 """
 from __future__ import annotations
 
+import contextlib
 import glob
 import math
 import os
 import sys
 import time
-from typing import Dict, Iterable, List, Optional
+from dataclasses import dataclass
+from typing import Dict, Iterable, List, NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
+from . import engine
 from . import kernels as K
 from . import ops
 from .engine import Layer, Tape, Variable, bump_weights_version, device, join_side_stream, recording, to_device
@@ -369,6 +372,7 @@ class DataParallel:
         self._flat = None
         self._expected = None            # contributions per variable and step (learnt from the first step on a flat buffer)
         self._comm_stream = None
+        self._active, self._handles, self._captured_buckets = False, [], 0      # a step is armed (begin_step), its async handles, buckets captured into graphs
         self.profile = False             # bench.py: time every bucket's all-reduce with events on the communication stream
         self._prof_events: List[tuple] = []
         self.prof_steps: List[dict] = []
@@ -427,8 +431,7 @@ class DataParallel:
         self._launched = [False] * len(self._bounds)
         self._handles = []
         self._main, self._side = main_stream, side_stream
-        from . import engine as _engine
-        capturing = _engine._CAPTURE[0] is not None
+        capturing = engine.capture() is not None
         if self._comm_stream is None and self._flat.is_cuda and not capturing:
             self._comm_stream = torch.cuda.Stream(device=self._flat.device)
         self._prof_events = []
@@ -440,8 +443,7 @@ class DataParallel:
     def _launch(self, b: int, inline: bool = False) -> None:
         lo, hi = self._bounds[b]
         self._launched[b] = True
-        from . import engine as _engine
-        cap = _engine._CAPTURE[0]
+        cap = engine.capture()
         if cap is not None:
             # The step is being captured as a chain of hipGraphs (Model._graph_step): the collective is captured too - RCCL kernels
             # are graph nodes like any other.  A bucket completed by a main-segment kernel goes into the side graph that replays
@@ -454,7 +456,7 @@ class DataParallel:
                 fn()
             else:
                 cap.pending.append(fn)
-            self._captured_buckets = getattr(self, "_captured_buckets", 0) + 1
+            self._captured_buckets += 1
             return
         if self._flat.is_cuda:
             # the bucket's gradients were written on the main stream (normalisation / bias gradients) and on the side
@@ -484,7 +486,7 @@ class DataParallel:
         """One gradient contribution to `var` has been enqueued.  A variable may receive several per step (shared layers:
         the re-tiled decoder queries of BoostedDETR); its bucket may only go out after the last one, so the first step
         after (re)building the buffer runs without early launches and records how many each variable gets."""
-        if not getattr(self, "_active", False):
+        if not self._active:
             return
         k = id(var)
         self._seen[k] = self._seen.get(k, 0) + 1
@@ -509,7 +511,7 @@ class DataParallel:
         """All-reduce whatever ``grad_ready`` did not launch, then make the current stream wait for every bucket."""
         if not self.active:
             return
-        if getattr(self, "_active", False) and flat is not self._flat:
+        if self._active and flat is not self._flat:
             # The step was armed on another buffer (the optimizer was rebuilt between begin_step and here).  Buckets already
             # in flight reduce a retired buffer: wait for them, then refuse - reducing `flat` again on top would double-count
             # whatever was copied out of the old one.  Model.forward_backward rebuilds the optimizer BEFORE arming the step, so
@@ -520,14 +522,13 @@ class DataParallel:
             self._handles, self._active = [], False
             if launched:
                 raise RuntimeError("data-parallel step: the optimizer's gradient buffer changed while bucket all-reduces were in flight")
-        if not getattr(self, "_active", False) or flat is not self._flat:
+        if not self._active or flat is not self._flat:
             self.allreduce_(flat)
             return
         self._active = False
         if self._expected is None:
             self._expected = dict(self._seen)
-        from . import engine as _engine
-        capturing = _engine._CAPTURE[0] is not None
+        capturing = engine.capture() is not None
         for b in range(len(self._bounds)):
             if not self._launched[b]:
                 self._launch(b, inline=True)
@@ -545,7 +546,7 @@ class DataParallel:
         before a data-parallel step is captured (Model._graph_step): a capture must not begin with eager collectives in flight - their
         completion events are polled by the backend's watchdog thread (see engine.SegmentedCapture.CAPTURE_ERROR_MODE) and their
         kernels would run concurrently with the capture's allocator warm-up."""
-        for h in getattr(self, "_handles", []):
+        for h in self._handles:
             h.wait()
         self._handles = []
         if torch.cuda.is_available():
@@ -665,6 +666,237 @@ def latest_checkpoint(checkpoint_dir: str) -> Optional[str]:
 
 
 # ----------------------------------------------------------------------------------------
+# step control: the range guard of the 'split' policy, the side stream's placement under data parallelism
+# ----------------------------------------------------------------------------------------
+class GuardEntry(NamedTuple):
+    """A guarded step whose flag snapshot the host has not looked at yet."""
+    batch: dict
+    ordinal: int         # the step's ordinal in the pinned flag log
+    event: object        # recorded behind the step
+    versions: tuple      # ((key, tensor._version), ...) of the batch's tensors when it was queued
+
+
+class RangeGuard:
+    """Range guard of the 'split' policy: the f16 pairs of its forward products hold |x| < 65504, the reference's fp32 does not
+    overflow there.  Producers raise a device flag instead of feeding NaN downstream; while it is up the optimizer applies nothing
+    and moving statistics stay put.  The host learns of it WITHOUT synchronising: every step ends with a one-lane kernel that logs
+    the flag in pinned memory (`snapshot`), and a later step looks at the entries that have landed (`poll`).  Every batch from the
+    one that raised the flag on is then redone on the exact-fp32 forward ('mixed') and the step / learning-rate counters are rolled
+    back for the update-free attempts (`redo`), so no batch is lost and the schedule does not run ahead.
+
+    owner: whose policy is guarded and whose counters a redo rolls back (train_gemm_precision, use_graph, steps_done,
+    optimizer.iterations: the Model); step_once(batch) -> logs runs one training step of it."""
+
+    LAG = 2              # steps between a snapshot and the host's look at it
+    DEMOTE_AFTER = 3     # consecutive redos after which the policy falls back to 'mixed' for good (redo)
+    RING = 8             # per-step entries of the pinned log (> LAG + 1, the most that are ever pending)
+
+    def __init__(self, owner, step_once):
+        self.owner, self.step_once = owner, step_once
+        self.check_every = 1            # 0 disables the host side of the guard
+        self.redos = 0                  # guarded steps that were redone on the exact-fp32 forward
+        self.skipped = 0                # ... how many update-free attempts that covered (counters rolled back for each)
+        self.redo_streak = 0            # consecutive guarded steps that had to be redone (redo: persistent demotion)
+        self.resolve_at_once = False    # look at every step's snapshot right behind it (fit() reads the logs on the host anyway)
+        self.pending: List[GuardEntry] = []
+        self.was_on: Optional[bool] = None
+        self.launched = 0               # snapshots enqueued so far = the ordinal of the latest
+        self.host = self.ordinal = self.events = None      # pinned log, device-resident ordinal, one event per ring entry (_allocate)
+
+    def on(self) -> bool:
+        return (self.owner.train_gemm_precision or K.get_gemm_precision()) == "split"
+
+    def begin_step(self) -> None:
+        on = self.on()
+        if self.was_on is not None and self.was_on != on:
+            K.overflow_flag().zero_()            # a flag left up by a step under another policy must not freeze this one's statistics
+            self.pending = []
+        self.was_on = on
+        K.set_guard_active(on)                   # BatchNorm statistics watch the flag only while somebody reads and clears it
+
+    def _allocate(self) -> None:
+        self.host = torch.zeros(1 + self.RING, dtype=torch.int32).pin_memory()
+        self.ordinal = torch.zeros(1, dtype=torch.int32, device="cuda")
+        self.events = [torch.cuda.Event() for _ in range(self.RING)]
+
+    def snapshot(self) -> None:
+        """Last launch of a guarded step: log the flag against the device-resident step ordinal in pinned memory (K.flag_snapshot).
+        Inside the step - and so inside the captured optimizer segment under use_graph - rather than between steps: see
+        bdetr_flag_snapshot (include/bdetr.h) for what an operation that reads the flag between graph launches did."""
+        if not (self.on() and self.check_every):
+            return
+        if self.host is None:
+            self._allocate()
+        K.flag_snapshot(self.ordinal, self.host)
+        if engine.capture() is None:
+            self.launched += 1                   # (a capture only records the launch; each replay counts: replayed)
+
+    def replayed(self) -> None:
+        """A replay of the captured step has just launched one snapshot (its optimizer segment ends with the kernel)."""
+        if self.on() and self.check_every:
+            self.launched += 1
+
+    def poll(self, batch: dict, logs):
+        """Host side of the range guard without stalling the device, behind every guarded step: step t looks at the entry of step
+        t - LAG, which has long landed (the wait on its event only bounds how far the host runs ahead).  A fixed lag, not a poll, so
+        that data-parallel replicas - whose flags agree after the step's MAX all-reduce - take the same decision at the same step.
+        A raised entry names the step that left the fp16 range; that batch and the later ones ran without an update (the optimizer
+        skips while the flag is up), so all of them are redone.  resolve_at_once: every outstanding entry is resolved now."""
+        if not (self.on() and self.check_every) or self.host is None:
+            return logs                          # (off, or no guarded step has run yet)
+        ev = self.events[self.launched % self.RING]
+        ev.record()
+        # The batch is kept BY REFERENCE until its snapshot has been examined (LAG + 1 steps): a redo trains on these tensors
+        # again, so an input pipeline must not overwrite them in place before then.  Their version counters are noted here and
+        # checked in redo - a reused buffer is an error there, not a silently different batch.
+        self.pending.append(GuardEntry(batch, self.launched, ev, tuple((k, v._version) for k, v in batch.items() if isinstance(v, torch.Tensor))))
+        return self._resolve(logs, 0 if self.resolve_at_once else self.LAG)
+
+    def _resolve(self, logs, keep: int):
+        host = self.host
+        while len(self.pending) > keep:
+            k, e = self.pending[0].ordinal, self.pending[0].event
+            if int(host[0]) < k:                     # (not landed yet: normally it has, LAG steps later)
+                e.synchronize()
+                if int(host[0]) < k:
+                    raise RuntimeError(f"range guard: step ordinal {k} finished but its snapshot is missing (log at {int(host[0])})")
+            if int(host[1 + k % self.RING]) != 0:
+                return self.redo(logs)
+            self.pending.pop(0)
+            self.redo_streak = 0                     # a guarded step went through clean
+        return logs
+
+    def flush(self):
+        """Resolve the snapshots still in flight (end of a run / before reading counters).  Returns the redone step's logs or None."""
+        return self._resolve(None, 0) if self.on() and self.pending else None
+
+    def redo(self, logs):
+        """The head of `pending` raised the flag: redo it and every later pending batch on the exact-fp32 forward."""
+        owner = self.owner
+        torch.cuda.synchronize()                             # rare: every later attempt has finished (none of them applied an update)
+        for p in self.pending:
+            stale = [k for k, ver in p.versions if p.batch[k]._version != ver]
+            if stale:
+                raise RuntimeError(f"range guard: the batch of step ordinal {p.ordinal} must be redone, but its tensors {stale} were modified in place since "
+                                   f"(an input pipeline has to leave a batch untouched for GUARD_LAG + 1 = {self.LAG + 1} steps under the 'split' policy)")
+        batches, self.pending = [p.batch for p in self.pending], []
+        K.overflow_flag().zero_()
+        n = len(batches)
+        self.redos += 1
+        self.skipped += n
+        owner.steps_done -= n                                # update-free attempts are not steps: dropout seeds and the
+        owner.optimizer.iterations -= n                      # learning-rate schedule continue from the last applied update
+        print(f"[boosted_detr_amd] step {owner.steps_done}: the split-fp16 forward left its range (|x| >= 65504) or went non-finite; "
+              f"no update was applied since - redoing {n} batch(es) on the exact-fp32 forward", file=sys.stderr)
+        keep, owner.train_gemm_precision = owner.train_gemm_precision, "mixed"
+        keep_graph, owner.use_graph = owner.use_graph, False  # the redone batches run eagerly: no fresh capture (and no second private pool) mid-training
+        try:
+            for d in batches:
+                logs = self.step_once(d)
+        finally:
+            owner.train_gemm_precision = keep
+            owner.use_graph = keep_graph
+        K.overflow_flag().zero_()                            # (bn_stats may have re-raised it for a genuinely non-finite batch statistic)
+        # A model whose weights or activations sit outside the f16 pair's range for good (e.g. a conv weight beyond 65504 / P16_W_SCALE)
+        # would run, skip and redo EVERY step - three times the cost behind a stderr line.  After DEMOTE_AFTER redos without a
+        # clean guarded step in between, the exact-fp32 forward ('mixed') becomes the model's policy and says so once.
+        self.redo_streak += 1
+        if self.redo_streak >= self.DEMOTE_AFTER and owner.train_gemm_precision == "split":
+            owner.train_gemm_precision = "mixed"
+            print(f"[boosted_detr_amd] {self.redo_streak} consecutive range-guard redos: train_gemm_precision is now 'mixed' (exact-fp32 forward) "
+                  "for the rest of this model's life; set it back to 'split' by hand if the cause was transient", file=sys.stderr)
+        return logs
+
+
+@dataclass
+class SideTuneToken:
+    """One timed eager step of the placement schedule."""
+    candidate: Optional[int]      # None: nothing to choose from - the schedule still runs its length (rank-independent)
+    rep: int                      # step within the candidate's slot; 0 is discarded
+    begin: object = None          # timing event at the step's start
+    joined: object = None         # ... behind the join of the side stream (mark_joined)
+
+
+class SidePlacementTuner:
+    """Placement of the side stream under data parallelism.  engine.side_stream() measures its candidates against the critical
+    path's stream and keeps the first good one; that settles the single-process case (one of the four hardware queues a low-priority
+    stream can land on costs 80 % of the step, the other three are equal).  With collectives in flight two more of the four become
+    10 % slower (measured over a one-rank RCCL communicator: 24.9 / 28.0 / 28.0 ms on the three "good" queues - presumably the ones
+    that share a dispatch pipe with the communication stream and with RCCL's own stream, whose barrier packets wait for the side
+    stream's events), and which ones cannot be seen before the collectives run.  So a data-parallel model times its first eager steps
+    on each good candidate (STEPS per slot, the first of a slot discarded; GPU time between two events on the step's stream: step
+    begin -> the join of the side stream behind the backward pass, i.e. BEFORE the step waits for its collectives - a rank times its
+    own streams, not the slowest replica's) and keeps the fastest.  The schedule has a FIXED length - SLOTS slots from step FROM on,
+    whatever the number of good candidates (they are cycled) - so that every rank leaves it at the same step."""
+
+    FROM, SLOTS, STEPS = 3, 4, 3
+
+    def __init__(self, dp: Optional[DataParallel]):
+        self.dp = dp                              # None: no data parallelism, nothing to settle
+        self.good: Optional[list] = None          # the good candidates (measured when the schedule starts)
+        self.ms: Dict[int, list] = {}             # candidate -> timed steps
+        self.k = 0                                # steps of the schedule taken so far
+        self.done = False
+        self.token: Optional[SideTuneToken] = None
+
+    def pending(self) -> bool:
+        return self.dp is not None and self.dp.active and not self.done and os.environ.get("BDETR_SIDE_TUNE", "1") != "0"
+
+    def begin(self, steps_done: int) -> Optional[SideTuneToken]:
+        """In front of an eager step: select the slot's candidate and start the clock."""
+        self.token = None
+        if not self.pending() or steps_done < self.FROM:
+            return None
+        if self.good is None:
+            self.good = engine.side_stream_expand() if engine.side_stream_placement() is not None else []      # measures the remaining candidates
+            self.ms = {c: [] for c in self.good}
+        slot, rep = divmod(self.k, self.STEPS)
+        if len(self.good) < 2:
+            self.token = SideTuneToken(None, rep)
+        else:
+            c = self.good[slot % len(self.good)]
+            if rep == 0:
+                engine.side_stream_select(c)
+            self.token = SideTuneToken(c, rep, torch.cuda.Event(enable_timing=True))
+            self.token.begin.record()
+        return self.token
+
+    def mark_joined(self) -> None:
+        """The side stream has been joined and the step has not yet waited for its collectives: the timed interval ends HERE."""
+        tok = self.token
+        if tok is not None and tok.begin is not None:
+            tok.joined = torch.cuda.Event(enable_timing=True)
+            tok.joined.record()
+
+    def end(self) -> None:
+        """Behind the step that `begin` opened: note its time; at the end of the schedule keep the fastest candidate."""
+        tok, self.token = self.token, None
+        if tok is None:
+            return
+        c = tok.candidate
+        if c is not None:
+            if tok.joined is None:
+                tok.joined = torch.cuda.Event(enable_timing=True)
+                tok.joined.record()
+            tok.joined.synchronize()
+            if tok.rep > 0:
+                self.ms[c].append(tok.begin.elapsed_time(tok.joined))
+        self.k += 1
+        if self.k >= self.SLOTS * self.STEPS:
+            if c is not None:
+                best = min((c for c in self.good if self.ms[c]), key=lambda c: min(self.ms[c]))
+                engine.side_stream_select(best)
+                engine.side_stream_placement()["step_ms"] = {c: round(min(v), 3) for c, v in self.ms.items() if v}
+            if engine.side_stream_placement() is not None:
+                engine.side_stream_release()               # the candidates not chosen are destroyed (idle queues are not free)
+            self.done = True
+
+
+def _forwarded(obj: str, name: str) -> property:
+    return property(lambda self: getattr(getattr(self, obj), name), lambda self, value: setattr(getattr(self, obj), name, value))
+
+
+# ----------------------------------------------------------------------------------------
 # Model
 # ----------------------------------------------------------------------------------------
 class Model(Layer):
@@ -675,7 +907,10 @@ class Model(Layer):
         self._step_losses: List[torch.Tensor] = []      # [B] vectors handed to add_loss
         self._loss_roots: List[torch.Tensor] = []       # tape roots whose backward seeds the step
         self._step_metrics: Dict[str, torch.Tensor] = {}
+        self._kept_tape: Optional[Tape] = None          # forward_backward(keep_tape=True) -> replay_backward
+        self.loss_fn = self.mask_weight = self._panoptic_inputs = None      # the subclasses': matching loss, MaskLoss weight, what call() leaves for panoptic_masks()
         self._dp: Optional[DataParallel] = None
+        self._dp_synced = True                          # (distribute: False until the replicas hold rank 0's values)
         self.steps_done = 0
         # Arithmetic of the conv/GEMM family during a training step (include/bdetr.h): 'split' = split-fp16
         # forward + split-bf16 gradient products.  The fp16 halves need |operand| < 65504, which the batch-
@@ -685,32 +920,29 @@ class Model(Layer):
         self.train_gemm_precision = None if os.environ.get("BDETR_GEMM_PRECISION") else "split"
         self.train_grad_precision = None      # None: the backward pass runs under train_gemm_precision too
         self.validate_matching = False      # fit() turns this on: it synchronises every step anyway (host logging)
-        # Range guard of the 'split' policy: the f16 pairs of its forward products hold |x| < 65504, the reference's
-        # fp32 does not overflow there.  Producers raise a device flag instead of feeding NaN downstream; while it is
-        # up the optimizer applies nothing and moving statistics stay put.  The host learns of it WITHOUT synchronising:
-        # every step ends with a one-lane kernel that logs the flag in pinned memory, and a later step looks at the
-        # entries that have landed (`_guard_poll`).  Every batch from the one that raised the flag on is then
-        # redone on the exact-fp32 forward ('mixed') and the step / learning-rate counters are rolled back for the
-        # update-free attempts, so no batch is lost and the schedule does not run ahead.
-        self.guard_check_every = 1       # 0 disables the host side of the guard
-        self.range_redos = 0             # guarded steps that were redone on the exact-fp32 forward
-        self.range_skipped = 0           # ... how many update-free attempts that covered (counters rolled back for each)
-        self._guard_count = 0
-        self._guard_pending: List[tuple] = []      # (step's batch, its ordinal in the pinned flag log, the event recorded behind it)
-        self._guard_was = None
+        self.guard = RangeGuard(self, self._train_step_once)
+        self.side_tuner = SidePlacementTuner(None)
         self._graphs, self._graph_warm = {}, {}
+        self._graph_refused = False         # the refusal of _graph_signature has been printed
+        self._graph_census = None           # node census of the latest capture (engine.SegmentedCapture.CENSUS)
         self.use_graph = os.environ.get("BDETR_GRAPH", "0") == "1"      # capture train_step as a hipGraph (see _graph_step)
-        self.range_redo_streak = 0       # consecutive guarded steps that had to be redone (see _guard_redo: persistent demotion)
+
+    GUARD_LAG, GUARD_DEMOTE_AFTER, GUARD_RING = RangeGuard.LAG, RangeGuard.DEMOTE_AFTER, RangeGuard.RING
+    SIDE_TUNE_FROM, SIDE_TUNE_SLOTS, SIDE_TUNE_STEPS = SidePlacementTuner.FROM, SidePlacementTuner.SLOTS, SidePlacementTuner.STEPS
+    guard_check_every = _forwarded("guard", "check_every")
+    range_redos = _forwarded("guard", "redos")
+    range_skipped = _forwarded("guard", "skipped")
+    range_redo_streak = _forwarded("guard", "redo_streak")
 
     @property
     def use_graph(self) -> bool:
-        return self.__dict__.get("_use_graph", False)
+        return self._use_graph
 
     @use_graph.setter
     def use_graph(self, on: bool) -> None:
         # (no environment write here: since round 4 the replay is sound on the runtime's default packet path - the captured chain holds
         # kernel nodes only; boosted_detr_amd.enable_graph_replay() remains as an explicit opt-in to DEBUG_CLR_GRAPH_PACKET_CAPTURE=0)
-        self.__dict__["_use_graph"] = bool(on)
+        self._use_graph = bool(on)
 
     # -- Keras bookkeeping -----------------------------------------------------------------
     def add_loss(self, loss) -> None:
@@ -743,7 +975,7 @@ class Model(Layer):
         self._dp = DataParallel()
         self.loss_fn.loss_scale = 1.0 / self._dp.world     # S14: per-replica loss scaled by 1/num_replicas
         self._dp_synced = False                            # variables are broadcast from rank 0 once they exist (first step)
-        self._side_tune = None                             # the side stream's placement is settled again under the collectives (_side_tune_begin)
+        self.side_tuner = SidePlacementTuner(self._dp)     # the side stream's placement is settled again under the collectives
         return self
 
     # -- one step ----------------------------------------------------------------------------
@@ -752,37 +984,43 @@ class Model(Layer):
         rank = self._dp.rank if self._dp is not None else 0
         return 0x5EED + self.steps_done + 0x9E3779B1 * rank
 
+    @contextlib.contextmanager
+    def _backward_scope(self):
+        """What a backward pass runs inside (forward_backward, replay_backward): gradients reset, the optimizer's flat buffer zeroed and
+        live for the in-place gradient sinks, the launch stream pinned; behind it the side stream is joined."""
+        for v in self.variables:
+            v.reset_grad()
+        live = getattr(self.optimizer, "flat_grad", None)
+        if live is not None:
+            live.zero_()                         # ONE memset for all gradients (split-K GEMMs accumulate into zeros)
+        ops.set_live_flat_grad(live)             # in-place gradient sinks are valid for slices of THIS buffer only
+        prev = K.set_launch_stream(torch.cuda.current_stream().cuda_stream)     # pin the launch stream for the step
+        try:
+            yield
+        finally:
+            K.set_launch_stream(prev)
+            ops.set_live_flat_grad(None)
+            ops.set_grad_ready_hook(None)
+        join_side_stream()                       # weight-gradient GEMMs ran on the side stream
+
     def forward_backward(self, data: dict, stage_seed: bool = True, keep_tape: bool = False):
         """forward + matcher + loss + backward.  Leaves gradients in Variable.grad.
         keep_tape: keep the recorded tape so that ``replay_backward`` can run the backward pass again."""
         self._step_losses, self._loss_roots, self._step_metrics = [], [], {}
         ops.set_dropout_seed(self._step_seed(), write=stage_seed)
-        for v in self.variables:
-            v.reset_grad()
-        live = None
-        if self.optimizer is not None and getattr(self.optimizer, "flat_grad", None) is not None:
+        if getattr(self.optimizer, "flat_grad", None) is not None:
             # The trainable set changed since the buffer was built (layer.trainable = False / True between steps): rebuild
             # NOW, before the buffer is zeroed and before the data-parallel step is armed on it - otherwise early bucket
             # all-reduces would run on a buffer that stage_gradients is about to retire (and be repeated on the new one).
             tv_ids = [id(v) for v in self.trainable_variables]
             if self.optimizer._built_for is not None and self.optimizer._built_for != tv_ids:
                 self.optimizer.build(self.trainable_variables)
-            live = self.optimizer.flat_grad
-            live.zero_()                         # ONE memset for all gradients (split-K GEMMs accumulate into zeros)
-        ops.set_live_flat_grad(live)             # in-place gradient sinks are valid for slices of THIS buffer only
-        guarded = self._guarded()
-        if self._guard_was is not None and self._guard_was != guarded:
-            K.overflow_flag().zero_()            # a flag left up by a step under another policy must not freeze this one's statistics
-            self._guard_pending = []
-        self._guard_was = guarded
-        K.set_guard_active(guarded)              # BatchNorm statistics watch the flag only while somebody reads and clears it
-        if self._dp is not None:
-            from .engine import side_stream
-            self._dp.begin_step(self.optimizer, torch.cuda.current_stream(), side_stream())
-            ops.set_grad_ready_hook(self._dp.grad_ready)
-        tape = Tape()
-        prev = K.set_launch_stream(torch.cuda.current_stream().cuda_stream)     # pin the launch stream for the step
-        try:
+        with self._backward_scope():
+            self.guard.begin_step()
+            if self._dp is not None:
+                self._dp.begin_step(self.optimizer, torch.cuda.current_stream(), engine.side_stream())
+                ops.set_grad_ready_hook(self._dp.grad_ready)
+            tape = Tape()
             with K.gemm_precision(self.train_gemm_precision):
                 with recording(tape):
                     y_pred = self(data, training=True)
@@ -790,44 +1028,21 @@ class Model(Layer):
                 # at 2^-22 or better; the backward closures pick their kernels by the policy in force when they run: ops.conv_bn)
                 with K.gemm_precision(self.train_grad_precision):
                     tape.backward({id(t): t for t in self._loss_roots})     # parameter gradients land in Variable.grad (ops.GradSink)
-                    from . import engine as _engine
-                    if _engine._CAPTURE[0] is not None:
-                        _engine._CAPTURE[0].cut()        # segmented capture: close the backward's last segment (its side tasks need this step's sinks)
-                    elif _engine._DEBUG_LOG[0] is not None:
-                        _engine._debug_cut(None)         # (diagnostic twin of that cut in an eager step)
+                    engine.cut_after_backward()
             self._kept_tape = tape if keep_tape else None
-        finally:
-            K.set_launch_stream(prev)
-            ops.set_live_flat_grad(None)
-            ops.set_grad_ready_hook(None)
-        join_side_stream()                                      # weight-gradient GEMMs ran on the side stream
         return y_pred
 
     def _guarded(self) -> bool:
-        return (self.train_gemm_precision or K.get_gemm_precision()) == "split"
+        return self.guard.on()
 
     def replay_backward(self, gemm_precision: str) -> None:
         """Diagnostic: run the backward pass of the last ``forward_backward(..., keep_tape=True)`` again from the SAME
         saved forward (same activations, same ReLU / dropout masks, same match) under another GEMM arithmetic policy.
         Differences between two replays are then the arithmetic of the gradient products alone."""
-        tape = getattr(self, "_kept_tape", None)
-        if tape is None:
+        if self._kept_tape is None:
             raise RuntimeError("replay_backward needs forward_backward(data, keep_tape=True) first")
-        for v in self.variables:
-            v.reset_grad()
-        live = None
-        if self.optimizer is not None and getattr(self.optimizer, "flat_grad", None) is not None:
-            live = self.optimizer.flat_grad
-            live.zero_()
-        ops.set_live_flat_grad(live)
-        prev = K.set_launch_stream(torch.cuda.current_stream().cuda_stream)
-        try:
-            with K.gemm_precision(gemm_precision):
-                tape.backward({id(t): t for t in self._loss_roots})
-        finally:
-            K.set_launch_stream(prev)
-            ops.set_live_flat_grad(None)
-        join_side_stream()
+        with self._backward_scope(), K.gemm_precision(gemm_precision):
+            self._kept_tape.backward({id(t): t for t in self._loss_roots})
 
     # -- the step as a chain of hipGraphs ------------------------------------------------------------------
     # ~1500 kernel launches, ~1300 allocator calls and the Python tape make up 20 ms of host work per step.  With
@@ -842,14 +1057,13 @@ class Model(Layer):
     def _graph_signature(self, data: dict):
         if not self.use_graph or self.validate_matching:
             return None
-        if self._dp is not None and (not getattr(self, "_dp_synced", True) or (self._dp.active and self._dp.overlap and self._dp._expected is None)):
+        if self._dp is not None and (not self._dp_synced or (self._dp.active and self._dp.overlap and self._dp._expected is None)):
             return None          # replicas not yet broadcast / the bucket table not yet calibrated (its first eager step): not now
         if self.side_tuning_pending():
-            return None          # the side stream's placement is still being settled by timing eager steps (_side_tune_begin)
+            return None          # the side stream's placement is still being settled by timing eager steps (SidePlacementTuner)
         from . import graph_replay_is_safe
         if not graph_replay_is_safe():
-            if not getattr(self, "_graph_refused", False):
-                import sys
+            if not self._graph_refused:
                 self._graph_refused = True
                 print("[boosted_detr_amd] use_graph: BDETR_ZERO_MEMSET=1 puts hipMemset nodes back into the captured step; those are only sound with "
                       "DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 in force when the HIP runtime initialised (export it) - running eager steps", file=sys.stderr)
@@ -863,9 +1077,8 @@ class Model(Layer):
         buffers were built for, the trainable set, dropout rates and loss weights.  A change makes a new signature, i.e. a
         fresh capture (after two eager steps) - never a replay that keeps training frozen layers or updates a retired buffer."""
         from . import transformers
-        lf = getattr(self, "loss_fn", None)
-        loss = tuple(getattr(lf, k, None) for k in ("category_weight", "attribute_weight", "box_weight", "exist_weight", "loss_scale")) + \
-            (getattr(self, "mask_weight", None),)
+        loss = tuple(getattr(self.loss_fn, k, None) for k in ("category_weight", "attribute_weight", "box_weight", "exist_weight", "loss_scale")) + \
+            (self.mask_weight,)
         opt = self.optimizer
         hyper = opt.hyper() if opt is not None else ()
         dp = self._dp
@@ -873,11 +1086,10 @@ class Model(Layer):
                 tuple(getattr(opt, "_built_for", None) or ()), tuple(id(v) for v in self.trainable_variables),
                 bool(self.guard_check_every), transformers.AttentionBlock.dropout_rate, transformers.FeedForwardBlock.dropout_rate, loss, hyper)
 
-    def _device_step(self, data: dict, stage_scalars: bool) -> Dict[str, list]:
-        """Everything of a training step that runs on the device; no host synchronisation."""
-        self.forward_backward(data, stage_seed=stage_scalars)
-        tv = self.trainable_variables
-        self.optimizer.stage_gradients(tv)
+    def _finish_step(self, stage_scalars: bool) -> Dict[str, list]:
+        """A step behind its backward pass, eager or captured: stage the gradients, raise the guard for a non-finite loss, finish the
+        collectives, apply the update, log the guard's flag.  stage_scalars=False: the learning rate is already on the device."""
+        self.optimizer.stage_gradients(self.trainable_variables)
         guard = None
         if self._guarded():
             for root in self._loss_roots:
@@ -888,9 +1100,14 @@ class Model(Layer):
             if guard is not None:
                 self._dp.any_(guard)
         self.optimizer.apply_gradients(skip_flag=guard, stage_lr=stage_scalars)
-        self._guard_snapshot()
+        self.guard.snapshot()
         self.steps_done += 1
         return self.step_logs()
+
+    def _device_step(self, data: dict, stage_scalars: bool) -> Dict[str, list]:
+        """Everything of a training step that runs on the device; no host synchronisation."""
+        self.forward_backward(data, stage_seed=stage_scalars)
+        return self._finish_step(stage_scalars)
 
     def _graph_step(self, data: dict, sig) -> Optional[Dict[str, list]]:
         entry = self._graphs.get(sig)
@@ -906,11 +1123,10 @@ class Model(Layer):
             # The step is captured as a chain of graphs (engine.SegmentedCapture): main segments cut between tape nodes of the
             # backward pass, the weight-gradient tasks of each in a side graph that replays on the low-priority stream while
             # the next main segment runs, the optimizer in the last main segment behind the join.
-            from . import engine as _engine
-            if getattr(self, "_dp", None) is not None:
+            if self._dp is not None:
                 self._dp.drain()                             # no eager collective in flight when the first segment's capture opens
-            cap = _engine.SegmentedCapture()
-            _engine._CAPTURE[0] = cap
+            cap = engine.SegmentedCapture()
+            engine.set_capture(cap)
             prev_launch = K.set_launch_stream(None)
             try:
                 cap.begin_main()
@@ -922,7 +1138,7 @@ class Model(Layer):
                 self.steps_done, self.optimizer.iterations = keep
                 raise
             finally:
-                _engine._CAPTURE[0] = None
+                engine.set_capture(None)
                 K.set_launch_stream(prev_launch)
             cap.done = []                                    # the deferred closures kept the crossing tensors alive during the capture
             if cap.CENSUS:
@@ -936,177 +1152,23 @@ class Model(Layer):
                 static[k].copy_(v)
         ops.set_dropout_seed(self._step_seed())
         self.optimizer.stage_lr()
-        from .engine import side_stream
-        cap.replay(side_stream() if os.environ.get("BDETR_GRAPH_SIDE", "1") != "0" else None)
+        cap.replay(engine.side_stream() if os.environ.get("BDETR_GRAPH_SIDE", "1") != "0" else None)
         self._step_losses, self._loss_roots, self._step_metrics = list(book[0]), list(book[1]), dict(book[2])
         self.steps_done += 1
         self.optimizer.iterations += 1
-        if self._guarded() and self.guard_check_every:
-            self._guard_launched += 1                # the replayed optimizer segment ended with the snapshot kernel
+        self.guard.replayed()                                # the replayed optimizer segment ended with the snapshot kernel
         bump_weights_version()
         return logs
 
     def train_step(self, data: dict) -> Dict[str, torch.Tensor]:
-        logs = self._train_step_once(data)
-        if self._guarded() and self.guard_check_every:
-            logs = self._guard_poll(data, logs, force=getattr(self, "_guard_force", False))
-        return logs
-
-    GUARD_LAG = 2        # steps between a snapshot and the host's look at it
-    GUARD_DEMOTE_AFTER = 3   # consecutive redos after which the policy falls back to 'mixed' for good (_guard_redo)
-    GUARD_RING = 8       # per-step entries of the pinned log (> GUARD_LAG + 1, the most that are ever pending)
-
-    def _guard_snapshot(self) -> None:
-        """Last launch of a guarded step: log the flag against the device-resident step ordinal in pinned memory (K.flag_snapshot).
-        Inside the step - and so inside the captured optimizer segment under use_graph - rather than between steps: see
-        bdetr_flag_snapshot (include/bdetr.h) for what an operation that reads the flag between graph launches did."""
-        if not (self._guarded() and self.guard_check_every):
-            return
-        if self.__dict__.get("_guard_host") is None:
-            self._guard_host = torch.zeros(1 + self.GUARD_RING, dtype=torch.int32).pin_memory()
-            self._guard_ordinal = torch.zeros(1, dtype=torch.int32, device="cuda")
-            self._guard_events = [torch.cuda.Event() for _ in range(self.GUARD_RING)]
-            self._guard_launched = 0
-        K.flag_snapshot(self._guard_ordinal, self._guard_host)
-        from . import engine as _engine
-        if _engine._CAPTURE[0] is None:
-            self._guard_launched += 1              # (a capture only records the launch; each replay counts, in _graph_step)
-
-    def _guard_poll(self, data: dict, logs, force: bool = False):
-        """Host side of the range guard without stalling the device: every guarded step ends with a one-lane kernel that logs the
-        flag in pinned memory (`_guard_snapshot`); step t looks at the entry of step t - GUARD_LAG, which has long landed (the
-        wait on its event only bounds how far the host runs ahead).  A fixed lag, not a poll, so that data-parallel replicas -
-        whose flags agree after the step's MAX all-reduce - take the same decision at the same step.  A raised entry names the
-        step that left the fp16 range; that batch and the later ones ran without an update (the optimizer skips while the flag
-        is up), so all of them are redone on the exact-fp32 forward and the counters are rolled back for the update-free
-        attempts.  force: resolve every outstanding entry now (fit() reads the logs on the host anyway)."""
-        if self.__dict__.get("_guard_host") is None:
-            return logs                            # (no guarded step has run yet)
-        ev = self._guard_events[self._guard_launched % self.GUARD_RING]
-        ev.record()
-        # The batch is kept BY REFERENCE until its snapshot has been examined (GUARD_LAG + 1 steps): a redo trains on these tensors
-        # again, so an input pipeline must not overwrite them in place before then.  Their version counters are noted here and
-        # checked in _guard_redo - a reused buffer is an error there, not a silently different batch.
-        self._guard_pending.append((data, self._guard_launched, ev, tuple((k, v._version) for k, v in data.items() if isinstance(v, torch.Tensor))))
-        return self._guard_resolve(logs, 0 if force else self.GUARD_LAG)
-
-    def _guard_resolve(self, logs, keep: int):
-        host = self._guard_host
-        while len(self._guard_pending) > keep:
-            _, k, e = self._guard_pending[0][:3]
-            if int(host[0]) < k:                     # (not landed yet: normally it has, GUARD_LAG steps later)
-                e.synchronize()
-                if int(host[0]) < k:
-                    raise RuntimeError(f"range guard: step ordinal {k} finished but its snapshot is missing (log at {int(host[0])})")
-            if int(host[1 + k % self.GUARD_RING]) != 0:
-                return self._guard_redo(0, logs)
-            self._guard_pending.pop(0)
-            self.range_redo_streak = 0               # a guarded step went through clean
-        return logs
+        return self.guard.poll(data, self._train_step_once(data))
 
     def guard_flush(self):
-        """Resolve the snapshots still in flight (end of a run / before reading counters).  Returns the redone step's logs or None."""
-        if self._guarded() and self._guard_pending:
-            return self._guard_resolve(None, 0)
-        return None
-
-    def _guard_redo(self, first_bad: int, logs):
-        import sys
-        torch.cuda.synchronize()                             # rare: every later attempt has finished (none of them applied an update)
-        batches = [p[0] for p in self._guard_pending[first_bad:]]
-        for p in self._guard_pending[first_bad:]:
-            stale = [k for k, ver in (p[3] if len(p) > 3 else ()) if p[0][k]._version != ver]
-            if stale:
-                raise RuntimeError(f"range guard: the batch of step ordinal {p[1]} must be redone, but its tensors {stale} were modified in place since "
-                                   f"(an input pipeline has to leave a batch untouched for GUARD_LAG + 1 = {self.GUARD_LAG + 1} steps under the 'split' policy)")
-        self._guard_pending = []
-        K.overflow_flag().zero_()
-        n = len(batches)
-        self.range_redos += 1
-        self.range_skipped += n
-        self.steps_done -= n                                 # update-free attempts are not steps: dropout seeds and the
-        self.optimizer.iterations -= n                       # learning-rate schedule continue from the last applied update
-        print(f"[boosted_detr_amd] step {self.steps_done}: the split-fp16 forward left its range (|x| >= 65504) or went non-finite; "
-              f"no update was applied since - redoing {n} batch(es) on the exact-fp32 forward", file=sys.stderr)
-        keep, self.train_gemm_precision = self.train_gemm_precision, "mixed"
-        keep_graph, self.use_graph = self.use_graph, False   # the redone batches run eagerly: no fresh capture (and no second private pool) mid-training
-        try:
-            for d in batches:
-                logs = self._train_step_once(d)
-        finally:
-            self.train_gemm_precision = keep
-            self.use_graph = keep_graph
-        K.overflow_flag().zero_()                            # (bn_stats may have re-raised it for a genuinely non-finite batch statistic)
-        # A model whose weights or activations sit outside the f16 pair's range for good (e.g. a conv weight beyond 65504 / P16_W_SCALE)
-        # would run, skip and redo EVERY step - three times the cost behind a stderr line.  After GUARD_DEMOTE_AFTER redos without a
-        # clean guarded step in between, the exact-fp32 forward ('mixed') becomes the model's policy and says so once.
-        self.range_redo_streak += 1
-        if self.range_redo_streak >= self.GUARD_DEMOTE_AFTER and self.train_gemm_precision == "split":
-            self.train_gemm_precision = "mixed"
-            print(f"[boosted_detr_amd] {self.range_redo_streak} consecutive range-guard redos: train_gemm_precision is now 'mixed' (exact-fp32 forward) "
-                  "for the rest of this model's life; set it back to 'split' by hand if the cause was transient", file=sys.stderr)
-        return logs
-
-    # -- placement of the side stream under data parallelism -------------------------------------------------------------------
-    # engine.side_stream() measures its candidates against the critical path's stream and keeps the first good one; that settles the
-    # single-process case (one of the four hardware queues a low-priority stream can land on costs 80 % of the step, the other three are equal).  With
-    # collectives in flight two more of the four become 10 % slower (measured over a one-rank RCCL communicator: 24.9 / 28.0 / 28.0 ms on the
-    # three "good" queues - presumably the ones that share a dispatch pipe with the communication stream and with RCCL's own stream, whose
-    # barrier packets wait for the side stream's events), and which ones cannot be seen before the collectives run.  So a data-parallel model
-    # times its first eager steps on each good candidate (SIDE_TUNE_STEPS per slot, the first of a slot discarded; GPU time between two events
-    # on the step's stream: step begin -> the join of the side stream behind the backward pass, i.e. BEFORE the step waits for its
-    # collectives - a rank times its own streams, not the slowest replica's) and keeps the fastest.  The schedule has a FIXED length - SIDE_TUNE_SLOTS slots from
-    # step SIDE_TUNE_FROM on, whatever the number of good candidates (they are cycled) - so that every rank leaves it at the same step.
-    SIDE_TUNE_FROM, SIDE_TUNE_SLOTS, SIDE_TUNE_STEPS = 3, 4, 3
+        """Resolve the guard's snapshots still in flight (end of a run / before reading counters).  Returns the redone step's logs or None."""
+        return self.guard.flush()
 
     def side_tuning_pending(self) -> bool:
-        return (self._dp is not None and self._dp.active and getattr(self, "_side_tune", None) != "done"
-                and os.environ.get("BDETR_SIDE_TUNE", "1") != "0")
-
-    def _side_tune_begin(self):
-        if not self.side_tuning_pending() or self.steps_done < self.SIDE_TUNE_FROM:
-            return None
-        from . import engine as _engine
-        st = getattr(self, "_side_tune", None)
-        if st is None:
-            good = _engine.side_stream_expand() if _engine.side_stream_placement() is not None else []      # measures the remaining candidates
-            st = self._side_tune = {"good": good, "k": 0, "ms": {c: [] for c in good}}
-        slot, rep = divmod(st["k"], self.SIDE_TUNE_STEPS)
-        if slot >= self.SIDE_TUNE_SLOTS:
-            return None
-        if len(st["good"]) < 2:
-            return ("idle", None, None, [None])       # nothing to choose from: the schedule still runs its length (rank-independent)
-        c = st["good"][slot % len(st["good"])]
-        if rep == 0:
-            _engine.side_stream_select(c)
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
-        return (c, rep, ev0, [None])
-
-    def _side_tune_end(self, tok) -> None:
-        if tok is None:
-            return
-        from . import engine as _engine
-        st = self._side_tune
-        c, rep, ev0, end = tok
-        self._side_tune_tok = None
-        if c != "idle":
-            ev1 = end[0]
-            if ev1 is None:
-                ev1 = torch.cuda.Event(enable_timing=True)
-                ev1.record()
-            ev1.synchronize()
-            if rep > 0:
-                st["ms"][c].append(ev0.elapsed_time(ev1))
-        st["k"] += 1
-        if st["k"] >= self.SIDE_TUNE_SLOTS * self.SIDE_TUNE_STEPS:
-            if c != "idle":
-                best = min((c for c in st["good"] if st["ms"][c]), key=lambda c: min(st["ms"][c]))
-                _engine.side_stream_select(best)
-                _engine.side_stream_placement()["step_ms"] = {c: round(min(v), 3) for c, v in st["ms"].items() if v}
-            if _engine.side_stream_placement() is not None:
-                _engine.side_stream_release()              # the candidates not chosen are destroyed (idle queues are not free)
-            self._side_tune = "done"
+        return self.side_tuner.pending()
 
     def _train_step_once(self, data: dict) -> Dict[str, torch.Tensor]:
         if self.optimizer is None:
@@ -1116,23 +1178,18 @@ class Model(Layer):
             logs = self._graph_step(data, sig)
             if logs is not None:
                 return logs
-        tune = self._side_tune_tok = self._side_tune_begin()
+        self.side_tuner.begin(self.steps_done)
         logs = self._eager_step(data)
-        self._side_tune_end(tune)
+        self.side_tuner.end()
         return logs
 
     def _eager_step(self, data: dict) -> Dict[str, torch.Tensor]:
-        if self._dp is not None and not getattr(self, "_dp_synced", True) and self.built_variables():
+        if self._dp is not None and not self._dp_synced and self.built_variables():
             self._dp.broadcast_variables(self.variables)
             self._dp_synced = True
         self.forward_backward(data)
-        tok = getattr(self, "_side_tune_tok", None)
-        if tok is not None and tok[2] is not None:
-            # placement tuning: the timed interval ends HERE - behind the join of the side stream, before the step waits for its collectives
-            # (a rank must time its own streams, not the slowest replica's)
-            tok[3][0] = torch.cuda.Event(enable_timing=True)
-            tok[3][0].record()
-        if self._dp is not None and not getattr(self, "_dp_synced", True):
+        self.side_tuner.mark_joined()
+        if self._dp is not None and not self._dp_synced:
             # build-by-first-call just created the variables: replicas adopt rank 0's initial values before any update
             self._dp.broadcast_variables(self.variables)
             self._dp_synced = True
@@ -1141,21 +1198,7 @@ class Model(Layer):
             # tf.numpy_function then fails the step); the GPU solver leaves such rows at -1.
             from .losses_and_metrics import MatchingAssignment
             MatchingAssignment.validate(self.loss_fn.last_match, self.loss_fn.last_num_objects, self.num_object_preds)
-        tv = self.trainable_variables
-        self.optimizer.stage_gradients(tv)
-        guard = None
-        if self._guarded():
-            for root in self._loss_roots:
-                K.flag_nonfinite(root)
-            guard = K.overflow_flag()
-        if self._dp is not None:
-            self._dp.finish(self.optimizer.flat_grad)       # buckets not already in flight since the backward pass + join
-            if guard is not None:
-                self._dp.any_(guard)
-        self.optimizer.apply_gradients(skip_flag=guard)
-        self._guard_snapshot()
-        self.steps_done += 1
-        return self.step_logs()
+        return self._finish_step(stage_scalars=True)
 
     def built_variables(self) -> bool:
         """True once build-by-first-call has created every variable (the loss layer is the last one to run)."""
@@ -1187,7 +1230,7 @@ class Model(Layer):
         from .model import _prepare_targets
         ev = evaluator if evaluator is not None else DetectionEvaluator(self.num_categories)
         ev.reset()
-        keep_panoptic = self.__dict__.get("_panoptic_inputs")
+        keep_panoptic = self._panoptic_inputs
         t0, n = time.time(), 0
         try:
             for step, batch in enumerate(x):
@@ -1198,8 +1241,7 @@ class Model(Layer):
                 ev.update(cat_preds, box_preds, cat_ids, bbox, num_objects)
                 n += 1
         finally:
-            if "_panoptic_inputs" in self.__dict__:
-                self._panoptic_inputs = keep_panoptic      # panoptic_masks() keeps answering for the last call the user made
+            self._panoptic_inputs = keep_panoptic      # panoptic_masks() keeps answering for the last call the user made
         res = ev.result()
         if verbose:
             print(f"evaluate - {time.time() - t0:.1f}s - {n} steps - " + " - ".join(f"{k}: {res[k]:.4f}" for k in ("AP", "AP50", "AP75", "AR")))
@@ -1226,7 +1268,7 @@ class Model(Layer):
         self.stop_training = False
         self.validate_matching = True
         self.guard_check_every = 1
-        self._guard_force = True              # every step ends in a host read of the logs anyway: resolve the guard snapshot at once
+        self.guard.resolve_at_once = True     # every step ends in a host read of the logs anyway: resolve the guard snapshot at once
         for epoch in range(epochs):
             t0, n, sums = time.time(), 0, {}
             for step, batch in enumerate(x):

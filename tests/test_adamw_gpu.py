@@ -149,7 +149,7 @@ def test_skip_flag_and_non_finite_gradient_leave_w_m_v_untouched(cuda):
     assert int(flag.item()) == 1                           # the norm pass raised it ...
     assert _identical(before, opt)                         # ... and no tensor was touched, not even those with a clean gradient
     # like SGD.apply_gradients, the call counts an iteration whether or not the device applied it: the host side of the range guard
-    # (Model._guard_redo) rolls `iterations` back for update-free attempts, and with it Adam's bias correction
+    # (RangeGuard.redo) rolls `iterations` back for update-free attempts, and with it Adam's bias correction
     assert opt.iterations == 3
     opt.iterations = 1
     flag.zero_()

@@ -261,7 +261,7 @@ def test_bench_multi_rank_code_path_over_one_rank_rccl(cuda, launch):
     assert ar and ar["buckets_per_step"] >= 3 and 120e6 < ar["bytes_per_step"] < 130e6 and ar["allreduce_ms_per_step"] > 0, ar       # 31.0 M fp32 gradients
     assert line["range_guard"]["overflow_flag_after_run"] == 0 and line["range_guard"]["range_redos_in_timed_region"] == 0
     # the weight-gradient stream was PLACED: four candidate hardware queues measured against the critical path's stream, then the good ones
-    # settled by timed data-parallel steps during set-up (engine.side_stream, training.Model._side_tune_begin)
+    # settled by timed data-parallel steps during set-up (engine.side_stream, training.SidePlacementTuner)
     pl = line["config"]["side_stream_placement"]
     assert len(pl["tick_ms"]) == 4 and pl["picked"] in pl["good"] and pl["tick_ms"][pl["picked"]] < 3 * pl["unloaded_ms"], pl
     assert len(pl["good"]) < 2 or (pl["step_ms"] and pl["step_ms"][str(pl["picked"])] == min(pl["step_ms"].values())), pl

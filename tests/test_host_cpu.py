@@ -371,7 +371,7 @@ def test_data_parallel_cuda_branch_with_fake_streams(monkeypatch):
 
 @pytest.mark.parametrize("good, step_ms, want", [([0, 1, 2], {0: 28.0, 1: 25.0, 2: 28.5}, 1), ([1, 3], {1: 27.0, 3: 24.9}, 3), ([2], {}, 2), ([], {}, None)])
 def test_side_stream_tuning_schedule_has_a_fixed_length_and_keeps_the_fastest_candidate(monkeypatch, good, step_ms, want):
-    """training.Model._side_tune_begin / _side_tune_end (the data-parallel model settles between the good side-stream candidates by timing its
+    """training.SidePlacementTuner (the data-parallel model settles between the good side-stream candidates by timing its
     first eager steps) with fakes for the engine and the events: whatever the number of good candidates, tuning ends at the SAME step - every
     rank must leave it together: the captured step and bench.py's set-up loop key on it - the first step of a slot is not counted, the
     fastest candidate is selected and the others released."""
@@ -391,26 +391,146 @@ def test_side_stream_tuning_schedule_has_a_fixed_length_and_keeps_the_fastest_ca
     monkeypatch.setattr(engine, "side_stream_expand", lambda: list(good))
     monkeypatch.setattr(engine, "side_stream_select", lambda c: (sel.append(c), placement.__setitem__("picked", c)))
     monkeypatch.setattr(engine, "side_stream_release", lambda: released.append(True))
-    m = training.Model.__new__(training.Model)
-    m._dp = types.SimpleNamespace(active=True)
-    m._side_tune, m.steps_done = None, 0
+    tuner = training.SidePlacementTuner(types.SimpleNamespace(active=True))
     first_done = None
     for step in range(30):
-        pending = m.side_tuning_pending()
-        tok = m._side_tune_tok = m._side_tune_begin()
-        if tok is not None and tok[2] is not None:
-            clock[0] += step_ms[tok[0]] + (7.0 if tok[1] == 0 else 0.0)       # the first step of a slot is slower (and must not count)
-            tok[3][0] = FakeEvent(); tok[3][0].record()
-        m._side_tune_end(tok)
-        m.steps_done += 1
-        if pending and not m.side_tuning_pending() and first_done is None:
-            first_done = m.steps_done
+        pending = tuner.pending()
+        tok = tuner.begin(step)
+        if tok is not None and tok.begin is not None:
+            clock[0] += step_ms[tok.candidate] + (7.0 if tok.rep == 0 else 0.0)       # the first step of a slot is slower (and must not count)
+            tuner.mark_joined()
+        tuner.end()
+        if pending and not tuner.pending() and first_done is None:
+            first_done = step + 1
+    assert training.SidePlacementTuner(None).pending() is False                        # no data parallelism: nothing to settle
     assert first_done == training.Model.SIDE_TUNE_FROM + training.Model.SIDE_TUNE_SLOTS * training.Model.SIDE_TUNE_STEPS, first_done
     if len(good) >= 2:
         assert placement["picked"] == want and sel[-1] == want and released, (placement, sel)
         assert placement["step_ms"] == {c: step_ms[c] for c in good}, placement
     else:
         assert not sel, sel
+
+
+class _GuardRig:
+    """training.RangeGuard over fakes (none of this is product code): a CPU tensor as the pinned flag log, events that do nothing, a
+    flag_snapshot that does on the host what bdetr_flag_snapshot does on the device, and a step that raises the flag - which then stays
+    up, as on the device - for a batch marked "bad" while the owner's policy is 'split'."""
+
+    def __init__(self, monkeypatch, **guard_attrs):
+        import types
+        import torch
+        from boosted_detr_amd import training
+        self.flag = torch.zeros(1, dtype=torch.int32)
+        self.calls = []                      # (batch name, policy, use_graph, steps_done on entry) of every step
+
+        class FakeEvent:
+            def record(self): pass
+            def synchronize(self): pass
+
+        def flag_snapshot(ordinal, host):
+            ordinal += 1
+            host[1 + int(ordinal) % (host.numel() - 1)] = self.flag[0]
+            host[0] = ordinal[0]
+
+        def allocate(guard):
+            guard.host = torch.zeros(1 + guard.RING, dtype=torch.int32)
+            guard.ordinal = torch.zeros(1, dtype=torch.int32)
+            guard.events = [FakeEvent() for _ in range(guard.RING)]
+        monkeypatch.setattr(training.torch, "cuda", types.SimpleNamespace(Event=FakeEvent, synchronize=lambda: None))
+        monkeypatch.setattr(training.K, "overflow_flag", lambda: self.flag)
+        monkeypatch.setattr(training.K, "flag_snapshot", flag_snapshot)
+        monkeypatch.setattr(training.RangeGuard, "_allocate", allocate)
+        self.owner = types.SimpleNamespace(train_gemm_precision="split", use_graph=True, steps_done=0, optimizer=types.SimpleNamespace(iterations=0))
+        self.guard = training.RangeGuard(self.owner, self.step_once)
+        for k, v in guard_attrs.items():
+            setattr(self.guard, k, v)
+
+    def step_once(self, batch):
+        o = self.owner
+        self.calls.append((batch["name"], o.train_gemm_precision, o.use_graph, o.steps_done))
+        if batch.get("bad") and o.train_gemm_precision == "split":
+            self.flag[0] = 1
+        self.guard.snapshot()
+        o.steps_done += 1
+        o.optimizer.iterations += 1
+        return ("logs", batch["name"], o.train_gemm_precision)
+
+    def train_step(self, name, bad=False, **tensors):
+        batch = {"name": name, "bad": bad, **tensors}
+        return self.guard.poll(batch, self.step_once(batch))
+
+
+def test_range_guard_examines_an_entry_exactly_lag_steps_late_and_redoes_everything_since(monkeypatch, capsys):
+    rig = _GuardRig(monkeypatch)
+    g, o = rig.guard, rig.owner
+    LAG = g.LAG
+    assert LAG == 2 and g.flush() is None                                            # nothing pending: nothing to resolve
+    for t in range(1, 4):                                                            # clean steps: entry t leaves when step t + LAG has run
+        assert rig.train_step(f"b{t}") == ("logs", f"b{t}", "split")
+        assert [p.ordinal for p in g.pending] == list(range(max(1, t - LAG + 1), t + 1))
+    assert rig.train_step("b4", bad=True) == ("logs", "b4", "split")                 # raised here ...
+    for t in range(5, 4 + LAG):
+        rig.train_step(f"b{t}")
+        assert g.redos == 0                                                          # ... not looked at before its turn
+    n_calls = len(rig.calls)
+    logs = rig.train_step(f"b{4 + LAG}")                                             # ... but exactly LAG steps later
+    redone = rig.calls[n_calls + 1:]
+    assert [c[0] for c in redone] == [f"b{t}" for t in range(4, 5 + LAG)]            # that batch and every later pending one
+    assert all(c[1] == "mixed" and c[2] is False for c in redone)                    # on the exact-fp32 forward, eagerly
+    assert redone[0][3] == 3                                                         # both counters rolled back by LAG + 1 first
+    assert logs == ("logs", f"b{4 + LAG}", "mixed")                                  # the caller gets the last redone step's logs
+    assert (o.steps_done, o.optimizer.iterations) == (4 + LAG, 4 + LAG)              # no batch lost, the schedule not ahead
+    assert (g.redos, g.skipped, g.redo_streak) == (1, LAG + 1, 1) and not g.pending and int(rig.flag) == 0
+    assert (o.train_gemm_precision, o.use_graph) == ("split", True)                  # both restored behind the redo
+    err = capsys.readouterr().err
+    assert err == ("[boosted_detr_amd] step 3: the split-fp16 forward left its range (|x| >= 65504) or went non-finite; "
+                   f"no update was applied since - redoing {LAG + 1} batch(es) on the exact-fp32 forward\n")
+    rig.train_step("c1"), rig.train_step("c2", bad=True)
+    assert [p.ordinal for p in g.pending] == [g.launched - 1, g.launched] and g.redos == 1
+    assert g.flush() == ("logs", "c2", "mixed") and g.redos == 2 and g.skipped == LAG + 2      # flush: the clean one passes, the raised one is redone
+    assert g.flush() is None and not g.pending
+
+
+def test_range_guard_ring_index_wraps(monkeypatch):
+    rig = _GuardRig(monkeypatch)
+    g = rig.guard
+    RING = g.RING
+    for t in range(1, 2 * RING + 2):
+        rig.train_step(f"b{t}", bad=(t == RING + 1))                                 # its flag lands in ring entry (RING + 1) % RING = 1
+        assert g.launched == t and (not g.pending or g.pending[-1].event is g.events[t % RING])
+        assert g.redos == (1 if t >= RING + 1 + g.LAG else 0), t
+    assert int(g.host[0]) == g.launched == 2 * RING + 1                              # (the redone steps ran under 'mixed': unguarded, no snapshot)
+    # the raised entry of step RING + 1 has been overwritten by step 2 RING + 1's clean one; the LAG attempts behind it (flag still up) not yet
+    assert rig.owner.steps_done == 2 * RING + 1 and g.host[1:].tolist() == [int(2 <= i <= 1 + g.LAG) for i in range(RING)]
+
+
+def test_range_guard_refuses_to_redo_a_batch_modified_in_place(monkeypatch):
+    import torch
+    rig = _GuardRig(monkeypatch)
+    image, boxes = torch.zeros(4), torch.zeros(4)
+    rig.train_step("b1", bad=True, image=image, bbox=boxes)
+    image.add_(1.0)                                                                  # an input pipeline reusing its buffer
+    rig.train_step("b2")
+    with pytest.raises(RuntimeError, match=r"step ordinal 1 must be redone, but its tensors \['image'\] were modified in place"):
+        rig.train_step("b3")
+
+
+def test_range_guard_demotes_after_consecutive_redos_only(monkeypatch, capsys):
+    rig = _GuardRig(monkeypatch, resolve_at_once=True)
+    g, o = rig.guard, rig.owner
+    assert g.DEMOTE_AFTER == 3
+    for i, bad in enumerate([True, True, False, True, True]):                        # a clean step in between resets the streak
+        rig.train_step(f"b{i}", bad=bad)
+    assert (g.redos, g.redo_streak, o.train_gemm_precision) == (4, 2, "split")
+    assert "consecutive" not in capsys.readouterr().err
+    rig.train_step("b5", bad=True)
+    assert (g.redos, g.redo_streak, o.train_gemm_precision) == (5, 3, "mixed")       # for good ...
+    assert capsys.readouterr().err.endswith(
+        "[boosted_detr_amd] 3 consecutive range-guard redos: train_gemm_precision is now 'mixed' (exact-fp32 forward) "
+        "for the rest of this model's life; set it back to 'split' by hand if the cause was transient\n")
+    n = len(rig.calls)
+    assert rig.train_step("b6", bad=True) == ("logs", "b6", "mixed") and len(rig.calls) == n + 1 and g.redos == 5      # ... and the guard is off
+    assert (o.steps_done, o.optimizer.iterations) == (7, 7)
 
 
 def test_every_kernel_switch_is_forced_by_some_test():

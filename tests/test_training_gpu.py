@@ -246,7 +246,7 @@ def test_range_guard_redoes_an_overflowing_step_on_the_fp32_forward(cuda):
         m.forward_backward(batch)                       # build (on the range-safe policy)
         m.set_weights_dict(params)
         m.train_gemm_precision = policy
-        m._guard_force = True                           # resolve the step's flag snapshot at once (what fit() does)
+        m.guard.resolve_at_once = True                  # resolve the step's flag snapshot at once (what fit() does)
         return m
 
     k.read_and_clear_overflow()
@@ -271,7 +271,7 @@ def test_range_guard_redoes_an_overflowing_step_on_the_fp32_forward(cuda):
     # since the flag rose ran without an update; all of them are redone and the counters are rolled back - three overflowing
     # steps end exactly where three 'mixed' steps end (no batch lost, the learning-rate schedule not ahead).
     ref3, lag = fresh("mixed"), fresh("split")
-    lag._guard_force = False
+    lag.guard.resolve_at_once = False
     for _ in range(3):
         w3 = ref3.logs_to_host(ref3.train_step(batch))
         g3 = lag.train_step(batch)

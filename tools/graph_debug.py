@@ -49,17 +49,17 @@ def run(graph, steps=8):
         elif os.environ.get("BETWEEN") == "other":        # ... that reads another tensor the graphs touch (the learning rate)
             keep = m.optimizer.d_lr.clone()
         torch.cuda.synchronize()
-        out.append((round(m.logs_to_host(logs)["loss"], 4), int(K.overflow_flag().item()), m.range_redos, [p[1] for p in m._guard_pending]))
+        out.append((round(m.logs_to_host(logs)["loss"], 4), int(K.overflow_flag().item()), m.range_redos, [p.ordinal for p in m.guard.pending]))
         if not m.guard_check_every:
             K.overflow_flag().zero_()
     if os.environ.get("LAG"):
-        m.GUARD_LAG = int(os.environ["LAG"])
+        m.guard.LAG = int(os.environ["LAG"])
     if not graph:
         REF.update(state(m))
     elif REF:
         def trip(*a, **k):
             raise Tripped()
-        m._guard_redo = trip
+        m.guard.redo = trip
     t0 = time.perf_counter()
     try:
         for i in range(10):
@@ -73,7 +73,7 @@ def run(graph, steps=8):
                 m.logs_to_host(logs_i) if False else [t.cpu() for t in m._step_losses]
     except Tripped:
         torch.cuda.synchronize()
-        print("guard tripped in the unsynchronised loop at step", m.steps_done, "log", m._guard_host.tolist(), "pending", [p[1] for p in m._guard_pending])
+        print("guard tripped in the unsynchronised loop at step", m.steps_done, "log", m.guard.host.tolist(), "pending", [p.ordinal for p in m.guard.pending])
         compare(m)
         return out, 0.0
     torch.cuda.synchronize()
