@@ -81,7 +81,7 @@ def __getattr__(name):
     if name in ("SGD", "AdamW", "Adam", "CosineDecayRestarts", "ModelCheckpoint", "TerminateOnNaN", "TensorBoard", "latest_checkpoint", "DetectionAP"):
         from . import training
         return getattr(training, name)
-    if name == "DetectionEvaluator":
-        from .evaluation import DetectionEvaluator
-        return DetectionEvaluator
+    if name in ("DetectionEvaluator", "MaskEvaluator"):
+        from . import evaluation
+        return getattr(evaluation, name)
     raise AttributeError(name)

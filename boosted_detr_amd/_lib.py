@@ -193,6 +193,8 @@ SIGNATURES = {
     "bdetr_adamw_clipnorm": (I, [P, P, I, P, P, I, P, P, P, P, F, F, F, F, F, F, F, P, P]),
     "bdetr_det_postprocess": (I, [P, I, I, I, P, P, P]),
     "bdetr_det_match": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P]),
+    "bdetr_mask_binarize": (I, [P, L, I, F, P, P, P]),
+    "bdetr_mask_match": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P]),
 }
 
 

@@ -1,11 +1,15 @@
-"""COCO-style box average precision for DETR / BoostedDETR.
+"""COCO-style box and mask average precision for DETR / BoostedDETR.
 
 The reference trains and never evaluates; this is the missing half of the Keras surface (``Model.evaluate``).  The per-image work -
 turning queries into detections, ranking them, matching them to the ground truths at every IoU threshold - runs on the GPU
-(csrc/detmetric.hip, include/bdetr.h K14) and leaves a few bytes per detection in HBM; ``DetectionEvaluator.update`` reads
-nothing back.  ``result`` copies what was kept to the host once and runs COCOeval's ``accumulate`` there in NumPy fp64.
+(csrc/detmetric.hip, include/bdetr.h K14; for masks csrc/maskmetric.hip, K15) and leaves a few bytes per detection in HBM;
+``DetectionEvaluator.update`` and ``MaskEvaluator.update`` read nothing back.  ``result`` copies what was kept to the host once and
+runs COCOeval's ``accumulate`` there in NumPy fp64; ``results`` does so for several evaluators with one copy between them.
 
-Deviations from pycocotools' COCOeval: no crowd regions (``iscrowd``), no area ranges (everything is "all"), one ``max_dets``.
+Deviations from pycocotools' COCOeval, for boxes and masks alike: no crowd regions (``iscrowd``), no area ranges (everything is
+"all"), one ``max_dets``.  Masks (``iouType="segm"``) are compared on the panoptic head's own 23 x 23 output grid, prediction
+logits cut at 0 and [0,1] targets at 0.5 - not upsampled to image resolution, not RLE; a query's mask shares its box's class and
+score (DETR's convention).
 """
 from __future__ import annotations
 
@@ -120,24 +124,87 @@ class DetectionEvaluator:
         self._kept.append((score, label, tp_bits, order))
         self.last_matched_gt = matched
 
-    def _to_host(self):
-        """One device-to-host copy: every kept tensor and the ground-truth counts, packed as int32 words."""
+    def _device_parts(self) -> list:
+        """What result() needs, as flat int32 device tensors: per batch score (bit pattern), label, tp_bits, order; then gt_count."""
         import torch
-        if not self._kept:
-            return [], np.zeros(self.num_classes, np.int64)
         parts = []
         for score, label, tp_bits, order in self._kept:
             parts += [score.view(torch.int32).reshape(-1), label.reshape(-1), tp_bits.to(torch.int32).reshape(-1), order.reshape(-1)]
         parts.append(self._gt_count)
-        flat = torch.cat(parts).cpu().numpy()
+        return parts
+
+    def _from_flat(self, flat: np.ndarray):
+        """The host copy of _device_parts(), concatenated -> (records, gt_count) for accumulate."""
         records, o = [], 0
         for score, *_ in self._kept:
             shape, n = tuple(score.shape), score.numel()
             s, l, t, r = (flat[o + k * n: o + (k + 1) * n].reshape(shape) for k in range(4))
             records.append((s.view(np.float32), l, (t & 0xFFFF).astype(np.uint16), r))
             o += 4 * n
-        return records, flat[o:].astype(np.int64)
+        return records, flat[o:o + self.num_classes].astype(np.int64)
+
+    def _to_host(self):
+        """One device-to-host copy: every kept tensor and the ground-truth counts, packed as int32 words."""
+        import torch
+        if not self._kept:
+            return [], np.zeros(self.num_classes, np.int64)
+        return self._from_flat(torch.cat(self._device_parts()).cpu().numpy())
+
+    def result_from(self, records: Sequence[tuple], gt_count) -> Dict[str, object]:
+        """The host half alone: accumulate over records as the kernels leave them (see ``accumulate``)."""
+        return accumulate(records, gt_count, self.iou_thresholds)
 
     def result(self) -> Dict[str, object]:
         records, gt_count = self._to_host()
-        return accumulate(records, gt_count, self.iou_thresholds)
+        return self.result_from(records, gt_count)
+
+
+class MaskEvaluator(DetectionEvaluator):
+    """Running COCO-style mask AP (iouType="segm") on the panoptic head's grid.  ``update`` launches bdetr_det_postprocess, two
+    bdetr_mask_binarize (logits at 0, targets at 0.5) and bdetr_mask_match on the current stream; what it keeps, and ``result``, are
+    DetectionEvaluator's: the same records, the same ``accumulate``.  It reads nothing back per batch."""
+
+    LOGIT_THRESHOLD, TARGET_THRESHOLD = 0.0, 0.5
+
+    def update(self, cat_pred, mask_logits, cat_ids, masks, num_objects) -> None:
+        """cat_pred [B,N,C] probabilities from ``Model.predict_raw``; mask_logits f32 [B,N,P] (or [B,N,h,w]) from ``panoptic_masks``;
+        cat_ids int32 [B,M]; masks f32 [B,M,P] (or [B,M,h,w]) targets in [0,1], row m belonging to cat_ids row m; num_objects
+        int32 [B].  All in HBM."""
+        import torch
+        from . import kernels as K
+        if cat_pred.shape[-1] != self.num_classes:
+            raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {self.num_classes}")
+        if cat_pred.dim() != 3 or mask_logits.dim() not in (3, 4) or masks.dim() not in (3, 4) or cat_ids.dim() != 2:
+            raise ValueError("expected cat_pred [B,N,C], mask_logits [B,N,P], cat_ids [B,M], masks [B,M,P]")
+        B, N = cat_pred.shape[:2]
+        M = cat_ids.shape[1]
+        mask_logits, masks = mask_logits.reshape(B, mask_logits.shape[1], -1), masks.reshape(masks.shape[0], masks.shape[1], -1)
+        if tuple(mask_logits.shape[:2]) != (B, N) or tuple(masks.shape[:2]) != (B, M) or mask_logits.shape[2] != masks.shape[2]:
+            raise ValueError(f"mask_logits {tuple(mask_logits.shape)} and masks {tuple(masks.shape)} do not fit cat_pred [B={B},N={N},C] and "
+                             f"cat_ids [B,M={M}] with one pixel count")
+        if self._gt_count is None:
+            self._gt_count = torch.zeros(self.num_classes, dtype=torch.int32, device=cat_pred.device)
+        score, label = K.det_postprocess(cat_pred.contiguous())
+        det_bits, det_area = K.mask_binarize(mask_logits.contiguous(), self.LOGIT_THRESHOLD)
+        gt_bits, gt_area = K.mask_binarize(masks.contiguous(), self.TARGET_THRESHOLD)
+        order, tp_bits, matched = K.mask_match(score, label, det_bits, det_area, cat_ids.contiguous(), gt_bits, gt_area,
+                                               num_objects.reshape(-1).contiguous(), self.iou_thresholds, self.num_classes, self.max_dets,
+                                               self._gt_count)
+        self._kept.append((score, label, tp_bits, order))
+        self.last_matched_gt = matched
+
+
+def results(evaluators: Sequence[DetectionEvaluator]) -> List[Dict[str, object]]:
+    """result() of several evaluators with ONE device-to-host copy between them: every evaluator's kept tensors in one torch.cat."""
+    import torch
+    live = [ev for ev in evaluators if ev._kept]
+    flat = torch.cat([p for ev in live for p in ev._device_parts()]).cpu().numpy() if live else np.zeros(0, np.int32)
+    out, o = [], 0
+    for ev in evaluators:
+        if not ev._kept:
+            out.append(ev.result_from([], np.zeros(ev.num_classes, np.int64)))
+            continue
+        n = sum(4 * score.numel() for score, *_ in ev._kept) + ev.num_classes
+        out.append(ev.result_from(*ev._from_flat(flat[o:o + n])))
+        o += n
+    return out

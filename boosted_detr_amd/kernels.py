@@ -1043,6 +1043,60 @@ def det_match(score, label, box_pred, gt_label, gt_box, num_objects, thresholds,
 
 
 # --------------------------------------------------------------------------------------
+# mask metric - csrc/maskmetric.hip
+# --------------------------------------------------------------------------------------
+def _dtypes(what: str, **named):
+    """Each operand against its dtype, by name, before anything else is looked at (the message says which one)."""
+    for name, (t, dtype) in named.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise _lib.BdetrError(f"{what}: {name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+
+
+def mask_binarize(x, threshold: float):
+    """x [..., P] fp32 -> (bits int64 [..., ceil(P/64)], area int32 [...]): bit p mod 64 of word p div 64 is x[p] > threshold (NaN:
+    false), the tail word's unused bits are zero, area = the row's set bits.  int64 holds the uint64 bit pattern (torch has no
+    arithmetic on uint64).  Mask logits are cut at 0.0 (sigmoid > 0.5), [0,1] targets at 0.5."""
+    _dtypes("mask_binarize", x=(x, torch.float32))
+    if x.dim() < 1 or x.numel() == 0:
+        raise _lib.BdetrError(f"mask_binarize: x must be [..., P] with at least one element, got {tuple(x.shape)}")
+    _chk(x)
+    P = x.shape[-1]
+    lead = tuple(x.shape[:-1])
+    bits = empty(*lead, (P + 63) // 64, like=x, dtype=torch.int64)
+    area = empty(*lead, like=x, dtype=torch.int32)
+    check(_lib.lib().bdetr_mask_binarize(_p(x), x.numel() // P, P, float(threshold), _p(bits), _p(area), _stream()), "mask_binarize")
+    return bits, area
+
+
+def mask_match(score, label, det_bits, det_area, gt_label, gt_bits, gt_area, num_objects, thresholds, num_classes: int, max_dets: int, gt_count):
+    """det_match with packed masks in place of the boxes (include/bdetr.h, K15): det_bits int64 [B,N,W] / det_area int32 [B,N] and
+    gt_bits int64 [B,M,W] / gt_area int32 [B,M] as mask_binarize returns them.  Everything else, and the returned
+    (order, tp_bits, matched_gt), as det_match."""
+    _dtypes("mask_match", score=(score, torch.float32), label=(label, torch.int32), det_bits=(det_bits, torch.int64),
+            det_area=(det_area, torch.int32), gt_label=(gt_label, torch.int32), gt_bits=(gt_bits, torch.int64), gt_area=(gt_area, torch.int32),
+            num_objects=(num_objects, torch.int32), gt_count=(gt_count, torch.int32))
+    if score.dim() != 2 or gt_label.dim() != 2 or det_bits.dim() != 3:
+        raise _lib.BdetrError("mask_match: operand shapes disagree (score [B,N], gt_label [B,M], det_bits [B,N,W])")
+    B, N = score.shape
+    M, W = gt_label.shape[1], det_bits.shape[2]
+    if tuple(label.shape) != (B, N) or tuple(det_bits.shape) != (B, N, W) or tuple(det_area.shape) != (B, N) or tuple(gt_label.shape) != (B, M) \
+            or tuple(gt_bits.shape) != (B, M, W) or tuple(gt_area.shape) != (B, M) or num_objects.numel() != B or gt_count.numel() != num_classes:
+        raise _lib.BdetrError("mask_match: operand shapes disagree")
+    _chk(score)
+    _chk(label, det_area, gt_label, gt_area, num_objects, gt_count, dtype=torch.int32)
+    _chk(det_bits, gt_bits, dtype=torch.int64)
+    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
+    T = int(thr.size)
+    order = empty(B, N, like=score, dtype=torch.int32)
+    tp_bits = empty(B, N, like=score, dtype=torch.int16)
+    matched = empty(B, max(T, 1), N, like=score, dtype=torch.int32)
+    check(_lib.lib().bdetr_mask_match(_p(score), _p(label), _p(det_bits), _p(det_area), _p(gt_label), _p(gt_bits), _p(gt_area), _p(num_objects),
+                                      thr.ctypes.data, B, N, M, W, int(num_classes), T, int(max_dets), _p(order), _p(tp_bits), _p(matched),
+                                      _p(gt_count), _stream()), "mask_match")
+    return order, tp_bits, matched
+
+
+# --------------------------------------------------------------------------------------
 # panoptic head pieces (forward) - csrc/panoptic.hip
 # --------------------------------------------------------------------------------------
 def pad4(c: int) -> int:

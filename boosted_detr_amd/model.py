@@ -111,11 +111,14 @@ class DETR(Model):
                 self.PanopticNeck.trainable = False
         self._panoptic_inputs = None
 
+    def _require_panoptic_head(self) -> None:
+        if self.PanopticAttention is None:
+            raise RuntimeError("construct the model with with_panoptic_head=True")
+
     def panoptic_masks(self):
         """[B, num_object_preds, 23 * 23] mask logits of the last call's images (transformers.py:460-559 on the image encoding +
         panoptic_neck.py:8-88), or None before the first call."""
-        if self.PanopticAttention is None:
-            raise RuntimeError("construct the model with with_panoptic_head=True")
+        self._require_panoptic_head()
         if self._panoptic_inputs is None:
             return None
         enc, dec, pos = self._panoptic_inputs

@@ -644,17 +644,24 @@ class TensorBoard(Callback):
 class DetectionAP(Callback):
     """COCO-style box AP on a held-out set at the end of an epoch: Model.evaluate over `validation_data` (at most `steps` batches),
     every `every` epochs; adds val_AP, val_AP50, val_AP75 and val_AR to that epoch's logs.  Unlike fit(validation_data=...), whose
-    test_step trains (the reference's quirk), this leaves the model as it found it.  Put it before the callbacks that write the logs."""
+    test_step trains (the reference's quirk), this leaves the model as it found it.  Put it before the callbacks that write the logs.
+    iou_types / mask_evaluator: as Model.evaluate's; with "segm" the logs gain val_mask_AP, val_mask_AP50, val_mask_AP75, val_mask_AR."""
 
-    def __init__(self, validation_data, every: int = 1, steps: Optional[int] = None, evaluator=None):
+    def __init__(self, validation_data, every: int = 1, steps: Optional[int] = None, evaluator=None, iou_types=("bbox",), mask_evaluator=None):
         self.validation_data, self.every, self.steps, self.evaluator = validation_data, max(1, int(every)), steps, evaluator
+        self.iou_types, self.mask_evaluator = Model._check_iou_types(iou_types), mask_evaluator
         self.history: List[dict] = []
 
     def on_epoch_end(self, epoch, logs=None):
         if (epoch + 1) % self.every:
             return
-        res = self.model.evaluate(self.validation_data, steps=self.steps, evaluator=self.evaluator)
-        vals = {f"val_{k}": float(res[k]) for k in ("AP", "AP50", "AP75", "AR")}
+        if self.iou_types == ("bbox",):
+            res = self.model.evaluate(self.validation_data, steps=self.steps, evaluator=self.evaluator)
+        else:
+            res = self.model.evaluate(self.validation_data, steps=self.steps, evaluator=self.evaluator, iou_types=self.iou_types,
+                                      mask_evaluator=self.mask_evaluator)
+        prefixes = [p for p, t in (("", "bbox"), ("mask_", "segm")) if t in self.iou_types]
+        vals = {f"val_{p}{k}": float(res[p + k]) for p in prefixes for k in ("AP", "AP50", "AP75", "AR")}
         self.history.append({"epoch": epoch, **vals})
         if logs is not None:
             logs.update(vals)
@@ -1220,32 +1227,85 @@ class Model(Layer):
         scores, labels = K.det_postprocess(cat_preds.contiguous())
         return {"scores": scores, "labels": labels, "boxes": box_preds}
 
-    def evaluate(self, x: Iterable[dict], steps: Optional[int] = None, evaluator=None, return_dict: bool = True, verbose: int = 0):
-        """COCO-style box AP over the batches of `x` (dicts as for training: strings or pre-tokenised ids).  Per batch: an inference-mode
+    IOU_TYPES = ("bbox", "segm")
+
+    @classmethod
+    def _check_iou_types(cls, iou_types) -> tuple:
+        types = (iou_types,) if isinstance(iou_types, str) else tuple(iou_types)
+        bad = [t for t in types if t not in cls.IOU_TYPES]
+        if bad or not types:
+            raise ValueError(f"iou_types must name one or both of {cls.IOU_TYPES}, got {iou_types!r}")
+        return tuple(t for t in cls.IOU_TYPES if t in types)
+
+    def _require_panoptic_head(self) -> None:
+        """Raises unless the model can produce masks (DETR with a panoptic head overrides this)."""
+        raise RuntimeError(f"{type(self).__name__} has no mask head: iou_types with 'segm' and segmentations() need a DETR built with "
+                           "with_panoptic_head=True or train_panoptic_head=True")
+
+    def segmentations(self, inputs: dict) -> Dict[str, torch.Tensor]:
+        """detections(inputs) plus every query's mask, in HBM: mask_logits f32 [B,N,23,23] from the panoptic head and masks int64
+        [B,N,W], the logits cut at 0 (sigmoid > 0.5) and packed 64 pixels to a word, row-major (bit p mod 64 of word p div 64;
+        W = ceil(529/64) = 9).  Afterwards panoptic_masks() answers for this call."""
+        from .panoptic_neck import MASK_GRID
+        self._require_panoptic_head()
+        out = self.detections(inputs)
+        logits = self.panoptic_masks()
+        B, N = logits.shape[:2]
+        bits, _ = K.mask_binarize(logits.contiguous(), 0.0)
+        out.update(mask_logits=logits.reshape(B, N, MASK_GRID, MASK_GRID), masks=bits)
+        return out
+
+    def evaluate(self, x: Iterable[dict], steps: Optional[int] = None, evaluator=None, return_dict: bool = True, verbose: int = 0,
+                 iou_types=("bbox",), mask_evaluator=None):
+        """COCO-style AP over the batches of `x` (dicts as for training: strings or pre-tokenised ids).  Per batch: an inference-mode
         forward pass and the two kernels of csrc/detmetric.hip, nothing read back; one device-to-host copy at the end (evaluation.py).
-        Changes nothing: weights, moving statistics, optimizer slots and counters, the step seed and captured steps stay as they were.
+        Changes nothing: weights, moving statistics, optimizer slots and counters, the step seed, captured steps and what
+        panoptic_masks() answers for stay as they were.
         evaluator: a DetectionEvaluator (other thresholds / max_dets); it is reset first.  Returns its result() dict, or with
-        return_dict=False the list [AP, AP50, AP75, AR]."""
-        from .evaluation import DetectionEvaluator
-        from .model import _prepare_targets
-        ev = evaluator if evaluator is not None else DetectionEvaluator(self.num_categories)
-        ev.reset()
+        return_dict=False the list [AP, AP50, AP75, AR].
+        iou_types: "bbox" (box AP, the default), "segm" (mask AP on the panoptic head's 23 x 23 grid) or both.  "segm" needs a DETR
+        with a panoptic head and inputs["masks"] in every batch (as train_panoptic_head does); per batch it adds the head's forward on
+        that same call's features and the kernels of csrc/maskmetric.hip.  The dict gains mask_AP, mask_AP50, mask_AP75, mask_AR and
+        per_class_mask_AP (with "segm" alone it holds those and the counts), the list the four mask numbers after the box ones;
+        still one device-to-host copy.  mask_evaluator: a MaskEvaluator, as `evaluator` is for boxes."""
+        from . import evaluation
+        from .model import _prepare_masks, _prepare_targets
+        types = self._check_iou_types(iou_types)
+        box_ev = mask_ev = None
+        if "bbox" in types:
+            box_ev = evaluator if evaluator is not None else evaluation.DetectionEvaluator(self.num_categories)
+            box_ev.reset()
+        if "segm" in types:
+            self._require_panoptic_head()
+            mask_ev = mask_evaluator if mask_evaluator is not None else evaluation.MaskEvaluator(self.num_categories)
+            mask_ev.reset()
         keep_panoptic = self._panoptic_inputs
         t0, n = time.time(), 0
         try:
             for step, batch in enumerate(x):
                 if steps is not None and step >= steps:
                     break
-                cat_preds, _, box_preds = self.predict_raw(batch)
                 cat_ids, _, bbox, num_objects = _prepare_targets(self, batch)
-                ev.update(cat_preds, box_preds, cat_ids, bbox, num_objects)
+                masks = _prepare_masks(batch, bbox.shape[0], bbox.shape[1]) if mask_ev is not None else None
+                cat_preds, _, box_preds = self.predict_raw(batch)
+                if box_ev is not None:
+                    box_ev.update(cat_preds, box_preds, cat_ids, bbox, num_objects)
+                if mask_ev is not None:
+                    mask_ev.update(cat_preds, self.panoptic_masks(), cat_ids, masks, num_objects)      # the head on this call's features
                 n += 1
         finally:
             self._panoptic_inputs = keep_panoptic      # panoptic_masks() keeps answering for the last call the user made
-        res = ev.result()
+        if mask_ev is None:
+            res = box_ev.result()
+        else:
+            parts = evaluation.results([ev for ev in (box_ev, mask_ev) if ev is not None])      # one copy for both
+            mres = parts[-1]
+            res = parts[0] if box_ev is not None else {k: mres[k] for k in ("num_detections", "num_ground_truths", "num_images", "gt_count")}
+            res.update({f"mask_{k}": mres[k] for k in ("AP", "AP50", "AP75", "AR")}, per_class_mask_AP=mres["per_class_AP"])
+        keys = [p + k for p, ev in (("", box_ev), ("mask_", mask_ev)) if ev is not None for k in ("AP", "AP50", "AP75", "AR")]
         if verbose:
-            print(f"evaluate - {time.time() - t0:.1f}s - {n} steps - " + " - ".join(f"{k}: {res[k]:.4f}" for k in ("AP", "AP50", "AP75", "AR")))
-        return res if return_dict else [res[k] for k in ("AP", "AP50", "AP75", "AR")]
+            print(f"evaluate - {time.time() - t0:.1f}s - {n} steps - " + " - ".join(f"{k}: {res[k]:.4f}" for k in keys))
+        return res if return_dict else [res[k] for k in keys]
 
     def step_logs(self) -> Dict[str, list]:
         """name -> list of per-image [B] device tensors (one per weak learner).  Nothing is copied to

@@ -668,6 +668,30 @@ int bdetr_det_match(const float* score, const int32_t* label, const float* box_p
                     const int32_t* num_objects, const double* thresholds, int B, int N, int M, int C, int T, int max_dets,
                     int32_t* order, uint16_t* tp_bits, int32_t* matched_gt, int32_t* gt_count, void* stream);
 
+/* ------------------------------------------------------------------------
+ * K15  mask metric: COCO-style mask AP (pycocotools' iouType="segm") on packed bitmasks (csrc/maskmetric.hip; evaluation.py
+ *   accumulates as for K14).  Masks are compared on the grid they are given on (the panoptic head's 23 x 23 = 529 pixels).
+ *   bdetr_mask_binarize : x [rows,P] fp32 -> bits [rows,W] uint64, W = ceil(P / 64): bit (p mod 64) of word (p div 64) is set when
+ *                         x[p] > threshold (NaN: not set); the bits of the last word at and past P are zero; area[rows] int32 =
+ *                         the row's number of set bits.  One wave per row: the wave's 64-bit ballot of the predicate IS the word.
+ *                         Mask logits are cut at 0 (sigmoid > 0.5 without the exponential), [0,1] targets at 0.5.
+ *   bdetr_mask_match    : bdetr_det_match with another IoU source.  det_bits [B,N,W], det_area [B,N], gt_bits [B,M,W], gt_area [B,M]
+ *                         as bdetr_mask_binarize leaves them, in place of the boxes; score / label / gt_label / num_objects /
+ *                         thresholds and the outputs order, tp_bits, matched_gt, gt_count exactly as in K14: the same ranking,
+ *                         truncation, valid ground truths and matching rule (on equal IoU the LARGER ground-truth index).
+ *       IoU        : inter = sum over w of popcount(d[w] & g[w]);  union = area_d + area_g - inter, in integers;
+ *                    iou = union > 0 ? (double)inter / (double)union : 0.  IEEE fp64 division of exact integers: equal rationals
+ *                    (2/4 and 3/6) are equal doubles, and an IoU of exactly 1/2 meets the threshold 0.5.
+ *   Limits: those of K14, W >= 1, and the image's staging must fit the default 64 KiB of dynamic LDS:
+ *   20 Np + 8 Mp + roundup8(Np) + 8 W (Np + Mp) bytes with Np, Mp = N, M rounded up to 4 (17.3 KiB at N = M = 100, W = 9).
+ *   Anything else returns -1 (bdetr_last_error names the limit) without a launch.
+ * ---------------------------------------------------------------------- */
+int bdetr_mask_binarize(const float* x, int64_t rows, int P, float threshold, uint64_t* bits, int32_t* area, void* stream);
+int bdetr_mask_match(const float* score, const int32_t* label, const uint64_t* det_bits, const int32_t* det_area,
+                     const int32_t* gt_label, const uint64_t* gt_bits, const int32_t* gt_area, const int32_t* num_objects,
+                     const double* thresholds, int B, int N, int M, int W, int C, int T, int max_dets,
+                     int32_t* order, uint16_t* tp_bits, int32_t* matched_gt, int32_t* gt_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,8 +7,16 @@ Three loops per repetition, each closed by one device synchronisation:
   evaluate  Model.evaluate: the update loop + result() (one device-to-host copy, host accumulate)
 If update() read anything back per batch, `update` would sit above `forward` by a synchronisation per batch; it should not.
 
-    python tools/eval_bench.py [--batches 8] [--reps 5] [--batch 16] [--image 640] [--layers 6] [--queries 100]
-    rocprofv3 --kernel-trace --stats -d DIR -o eval -- python tools/eval_bench.py --reps 1     # det_* rows: the kernels' own times
+With --segm: the same at configs[4] (batch 1, 800 x 1333, ResNet-101, 6 + 6 layers, 300 queries, the panoptic head; M = 100 padded
+objects with 23 x 23 mask targets) and two more loops:
+  head           predict_raw + panoptic_masks(): the forward pass with the mask head's
+  evaluate_segm  Model.evaluate(iou_types=("bbox", "segm")): per batch the head's forward and the kernels of csrc/maskmetric.hip
+                 on top of `evaluate`, still one device-to-host copy
+`evaluate` stays the box-only Model.evaluate.  --segm-model builds the same model and batches and runs the three box loops alone, so
+the tool can be pointed at a package without iou_types (the commit before it) for the figure to compare with.
+
+    python tools/eval_bench.py [--batches 8] [--reps 5] [--batch 16] [--image 640] [--layers 6] [--queries 100] [--segm | --segm-model]
+    rocprofv3 --kernel-trace --stats -d DIR -o eval -- python tools/eval_bench.py --reps 1     # det_* / mask_* rows: the kernels' own times
 """
 import argparse
 import json
@@ -22,7 +30,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def make_batch(B, H, W, M, C, seed):
+def make_batch(B, H, W, M, C, seed, masks=False):
     rng = np.random.Generator(np.random.PCG64(seed))
     num_objects = np.clip(1 + rng.poisson(6.3, size=B), 1, M).astype(np.int32)
     category, attribute = np.zeros((B, M), np.int32), np.zeros((B, M, 3), np.int32)
@@ -34,6 +42,8 @@ def make_batch(B, H, W, M, C, seed):
         bbox[b, :n, 2:4] = rng.uniform(0.05, 0.4, size=(n, 2))
     host = {"image": rng.random((B, H, W, 3), dtype=np.float32), "category": category, "attribute": attribute, "bbox": bbox,
             "num_objects": num_objects}
+    if masks:
+        host["masks"] = (rng.random((B, M, 23, 23)) > 0.6).astype(np.float32)
     return {k: torch.from_numpy(v).cuda() for k, v in host.items()}
 
 
@@ -45,14 +55,21 @@ def main():
     ap.add_argument("--image", type=int, default=640)
     ap.add_argument("--layers", type=int, default=6)
     ap.add_argument("--queries", type=int, default=100)
+    ap.add_argument("--segm", action="store_true", help="configs[4] with the panoptic head; adds the head and evaluate_segm loops")
+    ap.add_argument("--segm-model", action="store_true", help="the model and batches of --segm, the box-only loops alone")
     args = ap.parse_args()
+    head = args.segm or args.segm_model
+    if head:
+        args.batch, args.queries, H, W, extra = 1, 300, 800, 1333, {"backbone_name": "ResNet101", "with_panoptic_head": True}
+    else:
+        H, W, extra = args.image, args.image, {}
     from boosted_detr_amd import parameters
     from boosted_detr_amd.evaluation import DetectionEvaluator
     from boosted_detr_amd.model import DETR, _prepare_targets
-    model = DETR(num_object_preds=args.queries, image_size=(args.image, args.image), num_encoder_blocks=args.layers, num_encoder_heads=8,
+    model = DETR(num_object_preds=args.queries, image_size=(H, W), num_encoder_blocks=args.layers, num_encoder_heads=8,
                  encoder_dim=256, num_decoder_blocks=args.layers, num_decoder_heads=8, decoder_dim=256, num_panoptic_heads=1, panoptic_dim=32,
-                 vocab_dict=parameters.COCO_VOCAB, attribute_weight=0.0)
-    batches = [make_batch(args.batch, args.image, args.image, 100, model.num_categories, 1234 + i) for i in range(args.batches)]
+                 vocab_dict=parameters.COCO_VOCAB, attribute_weight=0.0, **extra)
+    batches = [make_batch(args.batch, H, W, 100, model.num_categories, 1234 + i, masks=head) for i in range(args.batches)]
     ev = DetectionEvaluator(model.num_categories)
 
     def forward():
@@ -69,7 +86,19 @@ def main():
     def evaluate():
         model.evaluate(batches, evaluator=ev)
 
+    def head_forward():
+        for b in batches:
+            model.predict_raw(b)
+            model.panoptic_masks()
+
+    segm = {}
+
+    def evaluate_segm():
+        segm.update(model.evaluate(batches, evaluator=ev, iou_types=("bbox", "segm")))
+
     loops = {"forward": forward, "update": update, "evaluate": evaluate}
+    if args.segm:
+        loops.update(head=head_forward, evaluate_segm=evaluate_segm)
     for fn in loops.values():            # build-by-first-call, allocator warm-up
         fn()
     torch.cuda.synchronize()
@@ -85,6 +114,8 @@ def main():
            "median_ms_per_batch": {k: round(float(np.median(v)), 3) for k, v in ms.items()},
            "spread_ms_per_batch": {k: round(float(max(v) - min(v)), 3) for k, v in ms.items()},
            "result": {k: v for k, v in ev.result().items() if k in ("AP", "AR", "num_detections", "num_ground_truths", "num_images")}}
+    if args.segm:
+        out["result"].update({k: segm[k] for k in ("mask_AP", "mask_AR")})
     print(json.dumps(out))
 
 
