@@ -195,6 +195,8 @@ SIGNATURES = {
     "bdetr_det_match": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P]),
     "bdetr_mask_binarize": (I, [P, L, I, F, P, P, P]),
     "bdetr_mask_match": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P]),
+    "bdetr_det_match_coco": (I, [P] * 11 + [I] * 7 + [P] * 7),
+    "bdetr_mask_match_coco": (I, [P] * 13 + [I] * 8 + [P] * 7),
 }
 
 

@@ -6,9 +6,12 @@ turning queries into detections, ranking them, matching them to the ground truth
 ``DetectionEvaluator.update`` and ``MaskEvaluator.update`` read nothing back.  ``result`` copies what was kept to the host once and
 runs COCOeval's ``accumulate`` there in NumPy fp64; ``results`` does so for several evaluators with one copy between them.
 
-Deviations from pycocotools' COCOeval, for boxes and masks alike: no crowd regions (``iscrowd``), no area ranges (everything is
-"all"), one ``max_dets``.  Masks (``iouType="segm"``) are compared on the panoptic head's own 23 x 23 output grid, prediction
-logits cut at 0 and [0,1] targets at 0.5 - not upsampled to image resolution, not RLE; a query's mask shares its box's class and
+``DetectionEvaluator`` / ``MaskEvaluator`` are the short form: no crowd regions (``iscrowd``), no area ranges (everything is "all"),
+one ``max_dets``.  ``CocoEvaluator`` / ``CocoMaskEvaluator`` are the full protocol (K16 / K17): crowd regions are *ignore*, every
+area range is matched on its own (a ground truth outside the range is *ignore*), and the accumulate runs per (range, max_det) -
+the 12 numbers of pycocotools' ``summarize``.  What remains different from pycocotools: masks (``iouType="segm"``) are compared on
+the panoptic head's own 23 x 23 output grid, prediction logits cut at 0 and [0,1] targets at 0.5 - not upsampled to image
+resolution, not RLE (a mask's area is its share of the grid times the image's H x W); a query's mask shares its box's class and
 score (DETR's convention).
 """
 from __future__ import annotations
@@ -143,11 +146,19 @@ class DetectionEvaluator:
             o += 4 * n
         return records, flat[o:o + self.num_classes].astype(np.int64)
 
+    def _flat_size(self) -> int:
+        """Words in _device_parts()."""
+        return sum(4 * score.numel() for score, *_ in self._kept) + self.num_classes
+
+    def _nothing(self):
+        """(records, gt_count) of an evaluator that saw no batch."""
+        return [], np.zeros(self.num_classes, np.int64)
+
     def _to_host(self):
         """One device-to-host copy: every kept tensor and the ground-truth counts, packed as int32 words."""
         import torch
         if not self._kept:
-            return [], np.zeros(self.num_classes, np.int64)
+            return self._nothing()
         return self._from_flat(torch.cat(self._device_parts()).cpu().numpy())
 
     def result_from(self, records: Sequence[tuple], gt_count) -> Dict[str, object]:
@@ -194,6 +205,233 @@ class MaskEvaluator(DetectionEvaluator):
         self.last_matched_gt = matched
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the full COCO protocol: crowd regions, area ranges, several max_dets (K16 / K17)
+# ---------------------------------------------------------------------------------------------------------------------
+MAX_AREA_RANGES = 4
+COCO_AREA_RANGES = {"all": (0.0, 1e10), "small": (0.0, 32.0 ** 2), "medium": (32.0 ** 2, 96.0 ** 2), "large": (96.0 ** 2, 1e10)}
+
+
+def _mean_valid(a: np.ndarray) -> float:
+    """COCOeval.summarize's mean over the entries that exist (> -1), in C order; NaN (pycocotools: -1) when there is none."""
+    a = a[a > -1]
+    return float(np.mean(a)) if a.size else float("nan")
+
+
+class _Lineup:
+    """The kept detections of every record, image by image in the kernel's order: what every (range, max_det) accumulate starts from."""
+
+    def __init__(self, records: Sequence[tuple], A: int):
+        scores, labels, ranks, tps, igs = [], [], [], [], []
+        for score, label, class_rank, tp_bits, ig_bits, order in records:
+            order = np.asarray(order, np.int64)
+            ok = order >= 0
+            idx = np.where(ok, order, 0)
+            tp = np.asarray(tp_bits).astype(np.int64) & 0xFFFF                                  # [A,B,N]
+            ig = np.asarray(ig_bits).astype(np.int64) & 0xFFFF
+            kept = ok & ((np.take_along_axis(tp[0], idx, 1) & KEEP_BIT) != 0)                   # row-major: image by image, ranked
+            scores.append(np.take_along_axis(np.asarray(score, np.float32), idx, 1)[kept])
+            labels.append(np.take_along_axis(np.asarray(label, np.int64), idx, 1)[kept])
+            ranks.append(np.take_along_axis(np.asarray(class_rank, np.int64), idx, 1)[kept])
+            tps.append(np.stack([np.take_along_axis(tp[a], idx, 1)[kept] for a in range(A)]))
+            igs.append(np.stack([np.take_along_axis(ig[a], idx, 1)[kept] for a in range(A)]))
+        self.scores = np.concatenate(scores) if scores else np.zeros(0, np.float32)
+        self.labels = np.concatenate(labels) if labels else np.zeros(0, np.int64)
+        self.ranks = np.concatenate(ranks) if ranks else np.zeros(0, np.int64)
+        self.tp = np.concatenate(tps, axis=1) if tps else np.zeros((A, 0), np.int64)
+        self.ig = np.concatenate(igs, axis=1) if igs else np.zeros((A, 0), np.int64)
+
+
+def accumulate_pair(lineup: _Lineup, npig, T: int, a: int, max_det: int):
+    """COCOeval.accumulate for one area range and one max_det.  npig: the range's non-ignored ground truths per class [C].
+    Returns (precision [T,R,C], recall [T,C]); -1 for a class with npig = 0."""
+    npig = np.asarray(npig, np.int64).reshape(-1)
+    C, R = npig.size, RECALL_POINTS.size
+    precision = np.full((T, R, C), -1.0)
+    recall = np.full((T, C), -1.0)
+    eps = np.spacing(1.0)
+    within = lineup.ranks < max_det
+    shifts = np.arange(T)[:, None]
+    for c in np.flatnonzero(npig > 0):
+        sel = within & (lineup.labels == c)
+        rank = np.argsort(-lineup.scores[sel].astype(np.float64), kind="stable")
+        tpb, igb = lineup.tp[a][sel][rank], lineup.ig[a][sel][rank]
+        tp = ((tpb[None, :] >> shifts) & 1).astype(np.float64)                    # [T, D]
+        fp = 1.0 - np.maximum(tp, ((igb[None, :] >> shifts) & 1).astype(np.float64))      # fp = ~tp & ~ig
+        tp_sum, fp_sum = np.cumsum(tp, axis=1), np.cumsum(fp, axis=1)
+        nd = tpb.size
+        rc = tp_sum / float(npig[c])
+        pr = tp_sum / (fp_sum + tp_sum + eps)
+        pr = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]                  # the right-to-left monotone envelope
+        recall[:, c] = rc[:, -1] if nd else 0.0
+        for t in range(T):
+            at = np.searchsorted(rc[t], RECALL_POINTS, side="left")
+            q = np.zeros(R)
+            inside = at < nd
+            q[inside] = pr[t, at[inside]]
+            precision[t, :, c] = q
+    return precision, recall
+
+
+def accumulate_coco(records: Sequence[tuple], gt_count, iou_thresholds, max_dets, area_names) -> Dict[str, object]:
+    """COCOeval.accumulate + summarize over what the K16 / K17 kernels left.
+
+    records: per batch, in arrival order, ``(score f32 [B,N], label i32 [B,N], class_rank i32 [B,N], tp_bits u16 [A,B,N], ig_bits u16
+    [A,B,N], order i32 [B,N])`` host arrays; gt_count [A,C]: the non-ignored ground truths per range and class; max_dets ascending;
+    area_names: the A ranges' names, the first one being the base range ("all").  Only the (range, max_det) pairs that summarize
+    reads are accumulated: every max_det in the base range, the largest max_det in every other range."""
+    thr = np.asarray(iou_thresholds, np.float64).reshape(-1)
+    gt_count = np.asarray(gt_count, np.int64)
+    A, C = gt_count.shape
+    T, last = thr.size, max_dets[-1]
+    lineup = _Lineup(records, A)
+    base_p, base_r = accumulate_pair(lineup, gt_count[0], T, 0, last)
+
+    def at_threshold(value: float) -> float:
+        hit = np.flatnonzero(np.isclose(thr, value, rtol=0.0, atol=1e-9))
+        return _mean_valid(base_p[hit[0]]) if hit.size else float("nan")
+
+    res = {"AP": _mean_valid(base_p), "AP50": at_threshold(0.5), "AP75": at_threshold(0.75)}
+    ranged = [accumulate_pair(lineup, gt_count[a], T, a, last) for a in range(1, A)]
+    for name, (p, _) in zip(area_names[1:], ranged):
+        res[f"AP_{name}"] = _mean_valid(p)
+    for m in max_dets:
+        res[f"AR_{m}"] = _mean_valid(base_r if m == last else accumulate_pair(lineup, gt_count[0], T, 0, m)[1])
+    for name, (_, r) in zip(area_names[1:], ranged):
+        res[f"AR_{name}"] = _mean_valid(r)
+    res["stats"] = [res[k] for k in list(res)]
+    valid = gt_count[0] > 0
+    per_class = np.asarray([_mean_valid(base_p[:, :, c]) for c in range(C)])
+    res.update(AR=res[f"AR_{last}"], per_class_AP=per_class, num_detections=int(lineup.scores.size),
+               num_ground_truths=int(gt_count[0][valid].sum()), num_images=int(sum(np.asarray(rec[0]).shape[0] for rec in records)),
+               gt_count=gt_count[0].copy(), gt_count_per_range=gt_count.copy())
+    return res
+
+
+class CocoEvaluator(DetectionEvaluator):
+    """Running box AP by the full COCO protocol: the 12 numbers of pycocotools' summarize.  ``update`` launches
+    bdetr_det_postprocess and bdetr_det_match_coco (K16) on the current stream and reads nothing back; per batch it keeps score /
+    label / class_rank / order [B,N] and tp_bits / ig_bits [A,B,N] in HBM.  ``result`` makes one device-to-host copy.
+    area_ranges: a dict name -> (lo, hi) in pixels, the first entry being the base range (or a sequence of pairs, named all / small /
+    medium / large by position); max_dets: ascending, the last one is the per-class truncation."""
+
+    WORDS_PER_DETECTION = 4          # score, label, class_rank, order; tp_bits and ig_bits add 2 A
+
+    def __init__(self, num_classes: int, iou_thresholds=None, max_dets=(1, 10, 100), area_ranges=None):
+        md = sorted({int(m) for m in (max_dets if np.ndim(max_dets) else [max_dets])})
+        if not md or md[0] < 1:
+            raise ValueError("max_dets must be positive")
+        ranges = COCO_AREA_RANGES if area_ranges is None else area_ranges
+        if not isinstance(ranges, dict):
+            ranges = list(ranges)
+            if len(ranges) > MAX_AREA_RANGES:
+                raise ValueError(f"1 to {MAX_AREA_RANGES} area ranges, got {len(ranges)}")
+            ranges = dict(zip(list(COCO_AREA_RANGES)[:len(ranges)], ranges))
+        if not 1 <= len(ranges) <= MAX_AREA_RANGES:
+            raise ValueError(f"1 to {MAX_AREA_RANGES} area ranges, got {len(ranges)}")
+        super().__init__(num_classes, iou_thresholds, md[-1])
+        self.max_dets = tuple(md)
+        self.area_names = [str(k) for k in ranges]
+        self.area_ranges = np.asarray([[float(lo), float(hi)] for lo, hi in ranges.values()], np.float64).reshape(-1, 2)
+
+    def reset(self) -> None:
+        super().reset()
+        self._ranges_dev = None               # float64 [A,2] in HBM, allocated by the first update
+
+    def _coco_operands(self, device, B: int, M: int, iscrowd, area, image_hw):
+        """iscrowd -> uint8 [B,M] (None: no crowd), area -> f32 [B,M] or None, image_hw -> int32 [B,2] ((H, W): every image's), all in HBM."""
+        import torch
+        if self._gt_count is None:
+            self._gt_count = torch.zeros(len(self.area_names), self.num_classes, dtype=torch.int32, device=device)
+            self._ranges_dev = torch.from_numpy(self.area_ranges).to(device)
+        crowd = torch.zeros(B, M, dtype=torch.uint8, device=device) if iscrowd is None \
+            else (torch.as_tensor(iscrowd).to(device) != 0).to(torch.uint8).reshape(B, M).contiguous()
+        if area is not None:
+            area = torch.as_tensor(area).to(device=device, dtype=torch.float32).reshape(B, M).contiguous()
+        if image_hw is None:
+            raise ValueError("image_hw is needed: the images' original (height, width), one pair or int32 [B,2]")
+        hw = torch.as_tensor(image_hw).to(device=device, dtype=torch.int32)
+        hw = (hw.reshape(1, 2).expand(B, 2) if hw.numel() == 2 else hw.reshape(B, 2)).contiguous()
+        return crowd, area, hw
+
+    def update(self, cat_pred, box_pred, cat_ids, bbox, num_objects, iscrowd=None, area=None, image_hw=None) -> None:
+        """As DetectionEvaluator.update, plus iscrowd [B,M] (non-zero = crowd region; None: none), area f32 [B,M] in pixels of the
+        original image (None: from the box) and image_hw, the original (height, width): one pair for every image or int32 [B,2]."""
+        from . import kernels as K
+        if cat_pred.shape[-1] != self.num_classes:
+            raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {self.num_classes}")
+        B, M = cat_ids.shape
+        crowd, area, hw = self._coco_operands(cat_pred.device, B, M, iscrowd, area, image_hw)
+        score, label = K.det_postprocess(cat_pred.contiguous())
+        order, class_rank, tp_bits, ig_bits, matched = K.det_match_coco(
+            score, label, box_pred.contiguous(), cat_ids.contiguous(), bbox.contiguous(), crowd, area, num_objects.reshape(-1).contiguous(), hw,
+            self._ranges_dev, self.iou_thresholds, self.num_classes, self.max_dets[-1], self._gt_count)
+        self._kept.append((score, label, class_rank, tp_bits, ig_bits, order))
+        self.last_matched_gt = matched
+
+    def _device_parts(self) -> list:
+        """Flat int32 device tensors: per batch score (bit pattern), label, class_rank, order, tp_bits, ig_bits; then gt_count [A,C]."""
+        import torch
+        parts = []
+        for score, label, class_rank, tp_bits, ig_bits, order in self._kept:
+            parts += [score.view(torch.int32).reshape(-1), label.reshape(-1), class_rank.reshape(-1), order.reshape(-1),
+                      tp_bits.to(torch.int32).reshape(-1), ig_bits.to(torch.int32).reshape(-1)]
+        parts.append(self._gt_count.reshape(-1))
+        return parts
+
+    def _flat_size(self) -> int:
+        A = len(self.area_names)
+        return sum((self.WORDS_PER_DETECTION + 2 * A) * score.numel() for score, *_ in self._kept) + A * self.num_classes
+
+    def _nothing(self):
+        return [], np.zeros((len(self.area_names), self.num_classes), np.int64)
+
+    def _from_flat(self, flat: np.ndarray):
+        A = len(self.area_names)
+        records, o = [], 0
+        for score, *_ in self._kept:
+            shape, n = tuple(score.shape), score.numel()
+            s, l, c, r = (flat[o + k * n: o + (k + 1) * n].reshape(shape) for k in range(4))
+            o += 4 * n
+            t, g = (flat[o + k * A * n: o + (k + 1) * A * n].reshape((A,) + shape) for k in range(2))
+            o += 2 * A * n
+            records.append((s.view(np.float32), l, c, (t & 0xFFFF).astype(np.uint16), (g & 0xFFFF).astype(np.uint16), r))
+        return records, flat[o:o + A * self.num_classes].astype(np.int64).reshape(A, self.num_classes)
+
+    def result_from(self, records: Sequence[tuple], gt_count) -> Dict[str, object]:
+        return accumulate_coco(records, gt_count, self.iou_thresholds, self.max_dets, self.area_names)
+
+
+class CocoMaskEvaluator(CocoEvaluator):
+    """Running mask AP (iouType="segm") by the full COCO protocol on the panoptic head's grid: MaskEvaluator's kernels with
+    bdetr_mask_match_coco (K17) in place of bdetr_mask_match; what it keeps, and ``result``, are CocoEvaluator's."""
+
+    LOGIT_THRESHOLD, TARGET_THRESHOLD = MaskEvaluator.LOGIT_THRESHOLD, MaskEvaluator.TARGET_THRESHOLD
+
+    def update(self, cat_pred, mask_logits, cat_ids, masks, num_objects, iscrowd=None, area=None, image_hw=None) -> None:
+        """As MaskEvaluator.update, plus iscrowd / area / image_hw as CocoEvaluator.update takes them (area None: from the mask)."""
+        from . import kernels as K
+        if cat_pred.shape[-1] != self.num_classes:
+            raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {self.num_classes}")
+        if cat_pred.dim() != 3 or mask_logits.dim() not in (3, 4) or masks.dim() not in (3, 4) or cat_ids.dim() != 2:
+            raise ValueError("expected cat_pred [B,N,C], mask_logits [B,N,P], cat_ids [B,M], masks [B,M,P]")
+        B, N = cat_pred.shape[:2]
+        M = cat_ids.shape[1]
+        mask_logits, masks = mask_logits.reshape(B, mask_logits.shape[1], -1), masks.reshape(masks.shape[0], masks.shape[1], -1)
+        if tuple(mask_logits.shape[:2]) != (B, N) or tuple(masks.shape[:2]) != (B, M) or mask_logits.shape[2] != masks.shape[2]:
+            raise ValueError(f"mask_logits {tuple(mask_logits.shape)} and masks {tuple(masks.shape)} do not fit cat_pred [B={B},N={N},C] and "
+                             f"cat_ids [B,M={M}] with one pixel count")
+        crowd, area, hw = self._coco_operands(cat_pred.device, B, M, iscrowd, area, image_hw)
+        score, label = K.det_postprocess(cat_pred.contiguous())
+        det_bits, det_pop = K.mask_binarize(mask_logits.contiguous(), self.LOGIT_THRESHOLD)
+        gt_bits, gt_pop = K.mask_binarize(masks.contiguous(), self.TARGET_THRESHOLD)
+        order, class_rank, tp_bits, ig_bits, matched = K.mask_match_coco(
+            score, label, det_bits, det_pop, cat_ids.contiguous(), gt_bits, gt_pop, crowd, area, num_objects.reshape(-1).contiguous(), hw,
+            self._ranges_dev, self.iou_thresholds, int(mask_logits.shape[2]), self.num_classes, self.max_dets[-1], self._gt_count)
+        self._kept.append((score, label, class_rank, tp_bits, ig_bits, order))
+        self.last_matched_gt = matched
+
+
 def results(evaluators: Sequence[DetectionEvaluator]) -> List[Dict[str, object]]:
     """result() of several evaluators with ONE device-to-host copy between them: every evaluator's kept tensors in one torch.cat."""
     import torch
@@ -202,9 +440,9 @@ def results(evaluators: Sequence[DetectionEvaluator]) -> List[Dict[str, object]]
     out, o = [], 0
     for ev in evaluators:
         if not ev._kept:
-            out.append(ev.result_from([], np.zeros(ev.num_classes, np.int64)))
+            out.append(ev.result_from(*ev._nothing()))
             continue
-        n = sum(4 * score.numel() for score, *_ in ev._kept) + ev.num_classes
+        n = ev._flat_size()
         out.append(ev.result_from(*ev._from_flat(flat[o:o + n])))
         o += n
     return out

@@ -1097,6 +1097,90 @@ def mask_match(score, label, det_bits, det_area, gt_label, gt_bits, gt_area, num
 
 
 # --------------------------------------------------------------------------------------
+# the full COCO protocol - csrc/detmetric.hip (K16), csrc/maskmetric.hip (K17)
+# --------------------------------------------------------------------------------------
+def _coco_operands(what: str, B: int, M: int, gt_crowd, gt_area, image_hw, area_ranges, gt_count, num_classes: int) -> int:
+    """The operands K16 and K17 share, checked; returns A."""
+    _dtypes(what, gt_crowd=(gt_crowd, torch.uint8), image_hw=(image_hw, torch.int32), area_ranges=(area_ranges, torch.float64),
+            gt_count=(gt_count, torch.int32))
+    if gt_area is not None:
+        _dtypes(what, gt_area=(gt_area, torch.float32))
+        if tuple(gt_area.shape) != (B, M):
+            raise _lib.BdetrError(f"{what}: gt_area must be [B,M]")
+        _chk(gt_area)
+    if tuple(gt_crowd.shape) != (B, M) or tuple(image_hw.shape) != (B, 2) or area_ranges.dim() != 2 or area_ranges.shape[1] != 2:
+        raise _lib.BdetrError(f"{what}: operand shapes disagree (gt_crowd [B,M], image_hw [B,2], area_ranges [A,2])")
+    A = int(area_ranges.shape[0])
+    if gt_count.numel() != A * num_classes:
+        raise _lib.BdetrError(f"{what}: gt_count must be [A,C]")
+    _chk(gt_crowd, dtype=torch.uint8)
+    _chk(image_hw, gt_count, dtype=torch.int32)
+    _chk(area_ranges, dtype=torch.float64)
+    return A
+
+
+def det_match_coco(score, label, box_pred, gt_label, gt_box, gt_crowd, gt_area, num_objects, image_hw, area_ranges, thresholds,
+                   num_classes: int, max_dets: int, gt_count):
+    """COCOeval's matching of one batch with crowd regions and area ranges (include/bdetr.h, K16).  gt_crowd uint8 [B,M]; gt_area f32
+    [B,M] in pixels or None; image_hw int32 [B,2]; area_ranges float64 [A,2] in HBM; thresholds: host fp64 values; max_dets: the
+    largest one; gt_count int32 [A,num_classes] in HBM, added to.  Returns (order int32 [B,N], class_rank int32 [B,N], tp_bits int16
+    [A,B,N], ig_bits int16 [A,B,N] - uint16 bit patterns - and matched_gt int32 [A,B,T,N])."""
+    _chk(score, box_pred, gt_box)
+    _chk(label, gt_label, num_objects, dtype=torch.int32)
+    B, N = score.shape
+    M = gt_label.shape[1]
+    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
+    T = int(thr.size)
+    if tuple(label.shape) != (B, N) or tuple(box_pred.shape) != (B, N, 4) or tuple(gt_label.shape) != (B, M) or tuple(gt_box.shape) != (B, M, 4) \
+            or num_objects.numel() != B:
+        raise _lib.BdetrError("det_match_coco: operand shapes disagree")
+    A = _coco_operands("det_match_coco", B, M, gt_crowd, gt_area, image_hw, area_ranges, gt_count, int(num_classes))
+    order = empty(B, N, like=score, dtype=torch.int32)
+    class_rank = empty(B, N, like=score, dtype=torch.int32)
+    tp_bits = empty(max(A, 1), B, N, like=score, dtype=torch.int16)
+    ig_bits = empty(max(A, 1), B, N, like=score, dtype=torch.int16)
+    matched = empty(max(A, 1), B, max(T, 1), N, like=score, dtype=torch.int32)
+    check(_lib.lib().bdetr_det_match_coco(_p(score), _p(label), _p(box_pred), _p(gt_label), _p(gt_box), _p(gt_crowd), _p(gt_area), _p(num_objects),
+                                          _p(image_hw), _p(area_ranges), thr.ctypes.data, B, N, M, int(num_classes), T, A, int(max_dets),
+                                          _p(order), _p(class_rank), _p(tp_bits), _p(ig_bits), _p(matched), _p(gt_count), _stream()),
+          "det_match_coco")
+    return order, class_rank, tp_bits, ig_bits, matched
+
+
+def mask_match_coco(score, label, det_bits, det_pop, gt_label, gt_bits, gt_pop, gt_crowd, gt_area, num_objects, image_hw, area_ranges,
+                    thresholds, num_pixels: int, num_classes: int, max_dets: int, gt_count):
+    """det_match_coco with packed masks in place of the boxes (include/bdetr.h, K17): det_bits / det_pop and gt_bits / gt_pop as
+    mask_binarize returns them, num_pixels the masks' pixel count P.  Everything else, and what is returned, as det_match_coco."""
+    _dtypes("mask_match_coco", score=(score, torch.float32), label=(label, torch.int32), det_bits=(det_bits, torch.int64),
+            det_pop=(det_pop, torch.int32), gt_label=(gt_label, torch.int32), gt_bits=(gt_bits, torch.int64), gt_pop=(gt_pop, torch.int32),
+            num_objects=(num_objects, torch.int32))
+    if score.dim() != 2 or gt_label.dim() != 2 or det_bits.dim() != 3:
+        raise _lib.BdetrError("mask_match_coco: operand shapes disagree (score [B,N], gt_label [B,M], det_bits [B,N,W])")
+    B, N = score.shape
+    M, W = gt_label.shape[1], det_bits.shape[2]
+    P = int(num_pixels)
+    if tuple(label.shape) != (B, N) or tuple(det_bits.shape) != (B, N, W) or tuple(det_pop.shape) != (B, N) or tuple(gt_label.shape) != (B, M) \
+            or tuple(gt_bits.shape) != (B, M, W) or tuple(gt_pop.shape) != (B, M) or num_objects.numel() != B or W != (P + 63) // 64:
+        raise _lib.BdetrError("mask_match_coco: operand shapes disagree")
+    A = _coco_operands("mask_match_coco", B, M, gt_crowd, gt_area, image_hw, area_ranges, gt_count, int(num_classes))
+    _chk(score)
+    _chk(label, det_pop, gt_label, gt_pop, num_objects, dtype=torch.int32)
+    _chk(det_bits, gt_bits, dtype=torch.int64)
+    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
+    T = int(thr.size)
+    order = empty(B, N, like=score, dtype=torch.int32)
+    class_rank = empty(B, N, like=score, dtype=torch.int32)
+    tp_bits = empty(max(A, 1), B, N, like=score, dtype=torch.int16)
+    ig_bits = empty(max(A, 1), B, N, like=score, dtype=torch.int16)
+    matched = empty(max(A, 1), B, max(T, 1), N, like=score, dtype=torch.int32)
+    check(_lib.lib().bdetr_mask_match_coco(_p(score), _p(label), _p(det_bits), _p(det_pop), _p(gt_label), _p(gt_bits), _p(gt_pop), _p(gt_crowd),
+                                           _p(gt_area), _p(num_objects), _p(image_hw), _p(area_ranges), thr.ctypes.data, B, N, M, P,
+                                           int(num_classes), T, A, int(max_dets), _p(order), _p(class_rank), _p(tp_bits), _p(ig_bits),
+                                           _p(matched), _p(gt_count), _stream()), "mask_match_coco")
+    return order, class_rank, tp_bits, ig_bits, matched
+
+
+# --------------------------------------------------------------------------------------
 # panoptic head pieces (forward) - csrc/panoptic.hip
 # --------------------------------------------------------------------------------------
 def pad4(c: int) -> int:

@@ -20,16 +20,19 @@ PAD = "<PAD>"
 BOX_PAD = -10.0
 
 
-def coco_records(coco: dict, normalise: bool = True) -> List[dict]:
+def coco_records(coco: dict, normalise: bool = True, with_eval_fields: bool = False) -> List[dict]:
     """COCO-format annotations (``images``, ``annotations``, ``categories``) -> one record per image:
     {'image_id', 'file_name', 'width', 'height', 'category': [[name], ...], 'bbox': [[x,y,w,h], ...]}
     with boxes divided by [W,H,W,H] (README.md:131-158: normalised COCO format) - the per-image
-    grouping datasets.py:340-516 performs with pandas."""
+    grouping datasets.py:340-516 performs with pandas.  with_eval_fields: each record also carries 'iscrowd': [0 / 1, ...] and
+    'area': [pixels, ...] (the annotation's own, else w * h of its box), which Model.evaluate(coco=True) reads."""
     names = {c["id"]: c["name"] for c in coco["categories"]}
     by_image: Dict[int, dict] = {}
     for im in coco["images"]:
         by_image[im["id"]] = {"image_id": im["id"], "file_name": im.get("file_name", ""), "width": im["width"], "height": im["height"],
                               "category": [], "attribute": [], "bbox": []}
+        if with_eval_fields:
+            by_image[im["id"]].update(iscrowd=[], area=[])
     for a in coco["annotations"]:
         rec = by_image[a["image_id"]]
         w, h = float(rec["width"]), float(rec["height"])
@@ -37,12 +40,16 @@ def coco_records(coco: dict, normalise: bool = True) -> List[dict]:
         rec["bbox"].append([x / w, y / h, bw / w, bh / h] if normalise else [x, y, bw, bh])
         rec["category"].append([names[a["category_id"]]])
         rec["attribute"].append([str(t) for t in a.get("attribute_names", [])] or [PAD])
+        if with_eval_fields:
+            rec["iscrowd"].append(int(a.get("iscrowd", 0)))
+            rec["area"].append(float(a["area"]) if "area" in a else float(bw) * float(bh))
     return list(by_image.values())
 
 
-def pad_annotations(records: Sequence[dict], max_objects: Optional[int] = None) -> Dict[str, np.ndarray]:
+def pad_annotations(records: Sequence[dict], max_objects: Optional[int] = None, with_eval_fields: bool = False) -> Dict[str, np.ndarray]:
     """pipeline.py:139-181: ragged per-image lists -> uniform arrays.  category [B,M,1] (pad '<PAD>'),
-    attribute [B,M,Amax] (pad '<PAD>'), bbox [B,M,4] (pad -10), num_objects [B]."""
+    attribute [B,M,Amax] (pad '<PAD>'), bbox [B,M,4] (pad -10), num_objects [B].  with_eval_fields: also iscrowd int32 [B,M]
+    (pad 0), area f32 [B,M] in pixels (pad 0) and height / width int32 [B], from records of coco_records(with_eval_fields=True)."""
     B = len(records)
     n = [len(r.get("bbox", [])) for r in records]
     M = max_objects if max_objects is not None else max(max(n), 1)
@@ -56,7 +63,15 @@ def pad_annotations(records: Sequence[dict], max_objects: Optional[int] = None) 
             atts = r.get("attribute", [[PAD]] * n[b])[m]
             attribute[b, m, :len(atts)] = atts
             bbox[b, m] = r["bbox"][m]
-    return {"category": category, "attribute": attribute, "bbox": bbox, "num_objects": np.minimum(np.asarray(n, np.int32), M)}
+    out = {"category": category, "attribute": attribute, "bbox": bbox, "num_objects": np.minimum(np.asarray(n, np.int32), M)}
+    if with_eval_fields:
+        iscrowd, area = np.zeros((B, M), np.int32), np.zeros((B, M), np.float32)
+        for b, r in enumerate(records):
+            k = min(n[b], M)
+            iscrowd[b, :k], area[b, :k] = r["iscrowd"][:k], r["area"][:k]
+        out.update(iscrowd=iscrowd, area=area, height=np.asarray([r["height"] for r in records], np.int32),
+                   width=np.asarray([r["width"] for r in records], np.int32))
+    return out
 
 
 class Augmentations:

@@ -645,15 +645,28 @@ class DetectionAP(Callback):
     """COCO-style box AP on a held-out set at the end of an epoch: Model.evaluate over `validation_data` (at most `steps` batches),
     every `every` epochs; adds val_AP, val_AP50, val_AP75 and val_AR to that epoch's logs.  Unlike fit(validation_data=...), whose
     test_step trains (the reference's quirk), this leaves the model as it found it.  Put it before the callbacks that write the logs.
-    iou_types / mask_evaluator: as Model.evaluate's; with "segm" the logs gain val_mask_AP, val_mask_AP50, val_mask_AP75, val_mask_AR."""
+    iou_types / mask_evaluator: as Model.evaluate's; with "segm" the logs gain val_mask_AP, val_mask_AP50, val_mask_AP75, val_mask_AR.
+    coco=True: Model.evaluate(coco=True); the logs gain val_AP_small ... val_AR_large (every number of the COCO summary) and, with
+    "segm", the val_mask_ counterparts."""
 
-    def __init__(self, validation_data, every: int = 1, steps: Optional[int] = None, evaluator=None, iou_types=("bbox",), mask_evaluator=None):
+    def __init__(self, validation_data, every: int = 1, steps: Optional[int] = None, evaluator=None, iou_types=("bbox",), mask_evaluator=None,
+                 coco: bool = False):
         self.validation_data, self.every, self.steps, self.evaluator = validation_data, max(1, int(every)), steps, evaluator
-        self.iou_types, self.mask_evaluator = Model._check_iou_types(iou_types), mask_evaluator
+        self.iou_types, self.mask_evaluator, self.coco = Model._check_iou_types(iou_types), mask_evaluator, bool(coco)
         self.history: List[dict] = []
 
     def on_epoch_end(self, epoch, logs=None):
         if (epoch + 1) % self.every:
+            return
+        if self.coco:
+            res = self.model.evaluate(self.validation_data, steps=self.steps, evaluator=self.evaluator, iou_types=self.iou_types,
+                                      mask_evaluator=self.mask_evaluator, coco=True)
+            prefixes = [p for p, t in (("", "bbox"), ("mask_", "segm")) if t in self.iou_types]
+            vals = {f"val_{k}": float(res[k]) for p in prefixes for k in res
+                    if k.startswith(p) and (k[len(p):] in ("AP", "AP50", "AP75", "AR") or k[len(p):].startswith(("AP_", "AR_")))}
+            self.history.append({"epoch": epoch, **vals})
+            if logs is not None:
+                logs.update(vals)
             return
         if self.iou_types == ("bbox",):
             res = self.model.evaluate(self.validation_data, steps=self.steps, evaluator=self.evaluator)
@@ -1256,7 +1269,7 @@ class Model(Layer):
         return out
 
     def evaluate(self, x: Iterable[dict], steps: Optional[int] = None, evaluator=None, return_dict: bool = True, verbose: int = 0,
-                 iou_types=("bbox",), mask_evaluator=None):
+                 iou_types=("bbox",), mask_evaluator=None, coco: bool = False):
         """COCO-style AP over the batches of `x` (dicts as for training: strings or pre-tokenised ids).  Per batch: an inference-mode
         forward pass and the two kernels of csrc/detmetric.hip, nothing read back; one device-to-host copy at the end (evaluation.py).
         Changes nothing: weights, moving statistics, optimizer slots and counters, the step seed, captured steps and what
@@ -1267,10 +1280,19 @@ class Model(Layer):
         with a panoptic head and inputs["masks"] in every batch (as train_panoptic_head does); per batch it adds the head's forward on
         that same call's features and the kernels of csrc/maskmetric.hip.  The dict gains mask_AP, mask_AP50, mask_AP75, mask_AR and
         per_class_mask_AP (with "segm" alone it holds those and the counts), the list the four mask numbers after the box ones;
-        still one device-to-host copy.  mask_evaluator: a MaskEvaluator, as `evaluator` is for boxes."""
+        still one device-to-host copy.  mask_evaluator: a MaskEvaluator, as `evaluator` is for boxes.
+        coco=True (or a passed CocoEvaluator / CocoMaskEvaluator): the full COCO protocol - crowd regions, area ranges, AR at several
+        max_dets - through the kernels of K16 / K17 instead.  Optional batch keys: iscrowd [B,M] (non-zero: a crowd region, which is
+        ignored rather than matched), area [B,M] in pixels of the original image, height / width [B] the original size; missing keys
+        mean no crowd, the area of the box (or mask) and the model's image_size.  The dict gains AP_small, AP_medium, AP_large, AR_1,
+        AR_10, AR_100, AR_small, AR_medium, AR_large and stats, the 12 numbers in pycocotools' summarize order (with "segm" the
+        mask_ counterparts and mask_stats); return_dict=False returns stats, followed by mask_stats."""
         from . import evaluation
         from .model import _prepare_masks, _prepare_targets
         types = self._check_iou_types(iou_types)
+        coco = bool(coco) or isinstance(evaluator, evaluation.CocoEvaluator) or isinstance(mask_evaluator, evaluation.CocoEvaluator)
+        if coco:
+            return self._evaluate_coco(x, steps, evaluator, return_dict, verbose, types, mask_evaluator)
         box_ev = mask_ev = None
         if "bbox" in types:
             box_ev = evaluator if evaluator is not None else evaluation.DetectionEvaluator(self.num_categories)
@@ -1306,6 +1328,71 @@ class Model(Layer):
         if verbose:
             print(f"evaluate - {time.time() - t0:.1f}s - {n} steps - " + " - ".join(f"{k}: {res[k]:.4f}" for k in keys))
         return res if return_dict else [res[k] for k in keys]
+
+    def _coco_fields(self, batch: dict, B: int, M: int):
+        """(iscrowd, area, image_hw) of a batch for the COCO evaluators: the optional keys iscrowd / area [B,M] and height / width [B]."""
+        from .engine import to_device
+
+        def dev(v, dtype):
+            return to_device(v if isinstance(v, torch.Tensor) else np.asarray(v), dtype)
+
+        iscrowd = dev(batch["iscrowd"], torch.int32).reshape(B, M) if batch.get("iscrowd") is not None else None
+        area = dev(batch["area"], torch.float32).reshape(B, M) if batch.get("area") is not None else None
+        if (batch.get("height") is None) != (batch.get("width") is None):
+            raise ValueError("a batch carries both of 'height' and 'width' or neither")
+        if batch.get("height") is not None:
+            hw = torch.stack([dev(batch["height"], torch.int32).reshape(B), dev(batch["width"], torch.int32).reshape(B)], 1).contiguous()
+        else:
+            hw = tuple(int(v) for v in self.image_size[:2])
+        return iscrowd, area, hw
+
+    def _evaluate_coco(self, x, steps, evaluator, return_dict, verbose, types, mask_evaluator):
+        """evaluate(coco=True): the same loop over CocoEvaluator / CocoMaskEvaluator."""
+        from . import evaluation
+        from .model import _prepare_masks, _prepare_targets
+        box_ev = mask_ev = None
+        if "bbox" in types:
+            box_ev = evaluator if evaluator is not None else evaluation.CocoEvaluator(self.num_categories)
+            if not isinstance(box_ev, evaluation.CocoEvaluator):
+                raise ValueError("coco=True needs a CocoEvaluator as evaluator")
+            box_ev.reset()
+        if "segm" in types:
+            self._require_panoptic_head()
+            mask_ev = mask_evaluator if mask_evaluator is not None else evaluation.CocoMaskEvaluator(self.num_categories)
+            if not isinstance(mask_ev, evaluation.CocoMaskEvaluator):
+                raise ValueError("coco=True needs a CocoMaskEvaluator as mask_evaluator")
+            mask_ev.reset()
+        keep_panoptic = self._panoptic_inputs
+        t0, n = time.time(), 0
+        try:
+            for step, batch in enumerate(x):
+                if steps is not None and step >= steps:
+                    break
+                cat_ids, _, bbox, num_objects = _prepare_targets(self, batch)
+                masks = _prepare_masks(batch, bbox.shape[0], bbox.shape[1]) if mask_ev is not None else None
+                iscrowd, area, hw = self._coco_fields(batch, bbox.shape[0], bbox.shape[1])
+                cat_preds, _, box_preds = self.predict_raw(batch)
+                if box_ev is not None:
+                    box_ev.update(cat_preds, box_preds, cat_ids, bbox, num_objects, iscrowd, area, hw)
+                if mask_ev is not None:
+                    mask_ev.update(cat_preds, self.panoptic_masks(), cat_ids, masks, num_objects, iscrowd, area, hw)
+                n += 1
+        finally:
+            self._panoptic_inputs = keep_panoptic      # panoptic_masks() keeps answering for the last call the user made
+        parts = evaluation.results([ev for ev in (box_ev, mask_ev) if ev is not None])      # one copy for both
+        counts = ("num_detections", "num_ground_truths", "num_images", "gt_count", "gt_count_per_range")
+        if mask_ev is None:
+            res = parts[0]
+        else:
+            mres = parts[-1]
+            res = parts[0] if box_ev is not None else {k: mres[k] for k in counts}
+            res.update({f"mask_{k}": v for k, v in mres.items() if k not in counts and k != "per_class_AP"}, per_class_mask_AP=mres["per_class_AP"])
+        if verbose:
+            keys = [p + k for p, ev in (("", box_ev), ("mask_", mask_ev)) if ev is not None for k in ("AP", "AP50", "AP75", "AR")]
+            print(f"evaluate - {time.time() - t0:.1f}s - {n} steps - " + " - ".join(f"{k}: {res[k]:.4f}" for k in keys))
+        if return_dict:
+            return res
+        return [v for p, ev in (("", box_ev), ("mask_", mask_ev)) if ev is not None for v in res[p + "stats"]]
 
     def step_logs(self) -> Dict[str, list]:
         """name -> list of per-image [B] device tensors (one per weak learner).  Nothing is copied to

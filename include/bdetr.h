@@ -692,6 +692,53 @@ int bdetr_mask_match(const float* score, const int32_t* label, const uint64_t* d
                      const double* thresholds, int B, int N, int M, int W, int C, int T, int max_dets,
                      int32_t* order, uint16_t* tp_bits, int32_t* matched_gt, int32_t* gt_count, void* stream);
 
+/* ------------------------------------------------------------------------
+ * K16  detection metric, the full COCO protocol: K14's bdetr_det_match with crowd regions, area ranges and the class rank that
+ *   several max_dets need (csrc/detmetric.hip; evaluation.py's CocoEvaluator accumulates).  The rule restated is pycocotools'
+ *   COCOeval.evaluateImg.  bdetr_det_match itself is unchanged.  Grid (B, A): one workgroup per image and area range, one wave
+ *   per threshold; every workgroup ranks its image again.
+ *   Inputs beyond K14, all in HBM: gt_crowd uint8 [B,M] (0 / 1); gt_area float [B,M] in pixels or NULL; image_hw int32 [B,2]
+ *   (original height, width); area_ranges double [A,2] (lo, hi).  thresholds stay in HOST memory.
+ *       areas      : scale_b = (double)H_b * (double)W_b.  Detection: (w * h) * scale_b in fp64 on the clamped extents.  Ground
+ *                    truth: (double)gt_area when given, otherwise the same formula on its box.
+ *       ignore     : a valid ground truth is IGNORED in range a when it is crowd or its area is < lo_a or > hi_a (both bounds
+ *                    inclusive: an area of exactly 32^2 is small and medium)
+ *       crowd IoU  : inter / (w_d * h_d) (normalised), 0 when that is 0; every other IoU is K14's, operation for operation
+ *       matching   : ranking, truncation (at max_dets, the LARGEST of the host's max_dets) and ties as K14.  Per range a and
+ *                    threshold t, walking the kept detections in `order`: a non-crowd ground truth matched at (a,t) is
+ *                    unavailable, a crowd ground truth is always available.  The detection takes the available NON-IGNORED
+ *                    ground truth of its label with the largest IoU >= min(thresholds[t], 1 - 1e-10) (equal IoU: the larger
+ *                    row); only if there is none, the available IGNORED one with the largest IoU >= the same bound (same tie
+ *                    rule).  This is COCOeval's sort-by-ignore plus `break`.
+ *       order      : int32 [B,N] as K14
+ *       class_rank : int32 [B,N] in query order: the number of detections of the same label ranked before this one
+ *       tp_bits    : uint16 [A,B,N]: bit t = matched to a non-ignored ground truth at (a,t); bit 15 = keep
+ *       ig_bits    : uint16 [A,B,N]: bit t = the detection is ignored at (a,t): matched to an ignored ground truth, or unmatched
+ *                    with its own area outside range a.  tp and ig are mutually exclusive.
+ *       matched_gt : int32 [A,B,T,N], the matched ground-truth row or -1
+ *       gt_count   : int32 [A,C], caller-owned and caller-zeroed: the NON-IGNORED valid ground truths are added per range and class
+ *   Limits: those of K14, 1 <= A <= 4, B <= 65535; anything else returns -1 (bdetr_last_error) without a launch.
+ *
+ * K17  mask metric, the full COCO protocol: K15's bdetr_mask_match extended as K16 extends K14 (csrc/maskmetric.hip).
+ *   det_pop / gt_pop int32 are the pixel counts bdetr_mask_binarize leaves (K15's det_area / gt_area); gt_area float [B,M] in
+ *   pixels or NULL is the annotation's area; P is the masks' pixel count (W = ceil(P / 64) words per mask).
+ *       areas      : detection (double)popcount * scale_b / (double)P; ground truth gt_area when given, else the same on gt_pop
+ *       crowd IoU  : (double)inter / (double)popcount_det, 0 when that is 0; every other IoU is K15's
+ *   Everything else as K16.  Limits: those of K16, P >= 1, and 24 Np + 8 Mp + roundup8(Np + Mp) + 8 W (Np + Mp) bytes of LDS
+ *   within the default 64 KiB.
+ * ---------------------------------------------------------------------- */
+int bdetr_det_match_coco(const float* score, const int32_t* label, const float* box_pred, const int32_t* gt_label, const float* gt_box,
+                         const uint8_t* gt_crowd, const float* gt_area, const int32_t* num_objects, const int32_t* image_hw,
+                         const double* area_ranges, const double* thresholds, int B, int N, int M, int C, int T, int A, int max_dets,
+                         int32_t* order, int32_t* class_rank, uint16_t* tp_bits, uint16_t* ig_bits, int32_t* matched_gt,
+                         int32_t* gt_count, void* stream);
+int bdetr_mask_match_coco(const float* score, const int32_t* label, const uint64_t* det_bits, const int32_t* det_pop,
+                          const int32_t* gt_label, const uint64_t* gt_bits, const int32_t* gt_pop, const uint8_t* gt_crowd,
+                          const float* gt_area, const int32_t* num_objects, const int32_t* image_hw, const double* area_ranges,
+                          const double* thresholds, int B, int N, int M, int P, int C, int T, int A, int max_dets,
+                          int32_t* order, int32_t* class_rank, uint16_t* tp_bits, uint16_t* ig_bits, int32_t* matched_gt,
+                          int32_t* gt_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
