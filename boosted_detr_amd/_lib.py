@@ -137,6 +137,9 @@ SIGNATURES = {
     "bdetr_bn_apply": (I, [P, P, P, P, P, P, I, P, L, I, P]),
     "bdetr_bn_bwd_chunks": (I, [L]),
     "bdetr_bn_bwd": (I, [P, P, P, P, P, P, P, I, I, P, P, P, P, P, L, I, P]),
+    "bdetr_bn_rows_stats": (I, [P, I, L, I, F, P, P, P, P, P]),
+    "bdetr_bn_rows_apply": (I, [P, P, P, P, P, P, I, L, I, I, P, F, P, P, P, P]),
+    "bdetr_bn_rows_bwd": (I, [P, P, P, P, P, I, I, P, P, P, P, I, L, I, P]),
     "bdetr_maxpool3x3s2_fwd": (I, [P, P, I, I, I, I, I, I, P]),
     "bdetr_maxpool3x3s2_bwd": (I, [P, P, P, P, I, I, I, I, I, I, P]),
     "bdetr_stem_pool_bwd_chunks": (I, [L]),
@@ -187,6 +190,9 @@ SIGNATURES = {
     "bdetr_cost_matrix": (I, [C.POINTER(LossDesc), P, P, P, P, P, P, P, P, P, P, P, P]),
     "bdetr_lsa": (I, [P, P, I, I, I, P, P]),
     "bdetr_set_loss": (I, [C.POINTER(LossDesc), P, P, P, P, P, P, P, P, P, P, P, P, F, P]),
+    "bdetr_cost_matrix_tiled": (I, [C.POINTER(LossDesc), I, P, P, P, P, P, P, P, P, P]),
+    "bdetr_lsa_tiled": (I, [P, P, I, I, I, I, P, P]),
+    "bdetr_set_loss_tiled": (I, [C.POINTER(LossDesc), I, P, P, P, P, P, P, P, P, P, P, P, P, F, P]),
     "bdetr_match_to_mask": (I, [P, P, I, I, I, P]),
     "bdetr_sgd_slab_elems": (I, []),
     "bdetr_sgd_nesterov_clipnorm": (I, [P, P, I, P, P, I, P, P, P, F, F, F, P, P]),

@@ -18,6 +18,8 @@ class BoostedDETR(Model):
                  classification_only=False, attribute_weight=1.0, name="DETR", use_intermediate_predictions=True, **kwargs):
         seed = int(kwargs.pop("seed", 0))
         backbone_name = kwargs.pop("backbone_name", "ResNet")
+        if kwargs.pop("use_intermediate_losses", False):
+            raise ValueError("BoostedDETR has one matcher and one loss per weak learner already; use_intermediate_losses is DETR's option")
         super().__init__(name=name, seed=seed)
         category_weight = box_weight = exist_weight = None
         if classification_only:

@@ -157,20 +157,22 @@ __device__ float att_cost_elem(const float* hot_m, const float* pred_n, int A) {
 __global__ __launch_bounds__(64) void cost_matrix_kernel(bdetr_loss_desc d, const float* __restrict__ cat_pred, const float* __restrict__ att_pred,
                                                          const float* __restrict__ box_pred, const int32_t* __restrict__ cat_ids,
                                                          const float* __restrict__ att_hot, const float* __restrict__ bbox,
-                                                         const int32_t* __restrict__ num_objects,
+                                                         const int32_t* __restrict__ num_objects, int period,
                                                          float* __restrict__ cost, float* __restrict__ ccat, float* __restrict__ catt, float* __restrict__ cbox) {
-    const int m = blockIdx.x, b = blockIdx.y;
-    const bool live = num_objects == nullptr || m < num_objects[b];
+    // period: the targets are [period] images and prediction image b is matched against target image b % period (the decoder layers'
+    // predictions stacked as [L * period] images: bdetr_cost_matrix_tiled); period == d.B for the plain entry point
+    const int m = blockIdx.x, b = blockIdx.y, bt = b % period;
+    const bool live = num_objects == nullptr || m < num_objects[bt];
     const int64_t row = ((int64_t)b * d.M + m) * d.N;
-    const int cid = cat_ids[(int64_t)b * d.M + m];
-    const float* tb = bbox + ((int64_t)b * d.M + m) * 4;
+    const int cid = cat_ids[(int64_t)bt * d.M + m];
+    const float* tb = bbox + ((int64_t)bt * d.M + m) * 4;
     const bool use_att = d.attribute_weight != 0.f && att_hot != nullptr && d.A > 0;
     for (int n = threadIdx.x; n < d.N; n += 64) {
         float c = 0.f, a = 0.f, bx = 0.f;
         if (live) {
             c = d.category_weight * cat_cost_elem(cat_pred[((int64_t)b * d.N + n) * d.C + cid], d.C);
             bx = d.box_weight * box_loss_fwd(tb, box_pred + ((int64_t)b * d.N + n) * 4);
-            if (use_att) a = d.attribute_weight * att_cost_elem(att_hot + ((int64_t)b * d.M + m) * d.A, att_pred + ((int64_t)b * d.N + n) * d.A, d.A);
+            if (use_att) a = d.attribute_weight * att_cost_elem(att_hot + ((int64_t)bt * d.M + m) * d.A, att_pred + ((int64_t)b * d.N + n) * d.A, d.A);
         }
         cost[row + n] = (c + bx) + a;      // category_cost + box_cost + attribute_cost (line 130)
         if (ccat) ccat[row + n] = c;
@@ -202,10 +204,10 @@ __device__ __forceinline__ int wave_max_i32(int v) {
 // remaining[nc]; uchar SR[nr], SC[nc]; then (optionally) the fp32 cost block.
 template <bool COST_IN_LDS>
 __global__ __launch_bounds__(64) void lsa_kernel(const float* __restrict__ cost, const int32_t* __restrict__ num_objects,
-                                                 int M, int N, int32_t* __restrict__ match, int maxdim) {
+                                                 int M, int N, int32_t* __restrict__ match, int maxdim, int period) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = blockIdx.x, lane = threadIdx.x;
-    int n_obj = num_objects[b];
+    int n_obj = num_objects[b % period];          // (period: see cost_matrix_kernel)
     n_obj = max(0, min(n_obj, M));
     int32_t* mrow = match + (int64_t)b * M;
     for (int m = lane; m < M; m += 64) mrow[m] = -1;
@@ -339,18 +341,18 @@ __global__ __launch_bounds__(256) void set_loss_kernel(bdetr_loss_desc d, const 
                                                        const float* __restrict__ att_hot, const float* __restrict__ bbox,
                                                        const int32_t* __restrict__ num_objects, const int32_t* __restrict__ match,
                                                        float* __restrict__ losses, float* __restrict__ d_cat, float* __restrict__ d_att,
-                                                       float* __restrict__ d_box, float loss_scale) {
+                                                       float* __restrict__ d_box, float loss_scale, int period) {
     __shared__ float sh[4];
     extern __shared__ __attribute__((aligned(16))) unsigned char smem2[];
     int* assigned = reinterpret_cast<int*>(smem2);            // [N] -> matched object or -1
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = blockIdx.x, tid = threadIdx.x, bt = b % period;      // (period: see cost_matrix_kernel; one loss call = `period` images)
     const bool use_att = d.attribute_weight != 0.f && att_hot != nullptr && d.A > 0 && att_pred != nullptr;
     // tot = 1 + sum over the (replica's) batch of num_objects (lines 144-145)
     float cnt = 0.f;
-    for (int k = tid; k < d.B; k += 256) cnt += (float)num_objects[k];
+    for (int k = tid; k < period; k += 256) cnt += (float)num_objects[k];
     const float tot = 1.0f + block_sum(cnt, sh);
     const float np1 = 1.0f + (float)d.N;
-    const int n_obj = max(0, min(num_objects[b], d.M));
+    const int n_obj = max(0, min(num_objects[bt], d.M));
 
     for (int n = tid; n < d.N; n += 256) assigned[n] = -1;
     // zero this image's gradient slices
@@ -378,8 +380,8 @@ __global__ __launch_bounds__(256) void set_loss_kernel(bdetr_loss_desc d, const 
             }
         }
         if (m < 0) continue;
-        const int cid = cat_ids[(int64_t)b * d.M + m];
-        const float* tb = bbox + ((int64_t)b * d.M + m) * 4;
+        const int cid = cat_ids[(int64_t)bt * d.M + m];
+        const float* tb = bbox + ((int64_t)bt * d.M + m) * 4;
         const float* pb = box_pred + ((int64_t)b * d.N + n) * 4;
         const float pcid = pc[cid];
         s_cat += d.category_weight * cat_cost_elem(pcid, d.C);
@@ -398,7 +400,7 @@ __global__ __launch_bounds__(256) void set_loss_kernel(bdetr_loss_desc d, const 
             s_iou += giou_fwd(t, p, 0);
         }
         if (use_att) {
-            const float* hot = att_hot + ((int64_t)b * d.M + m) * d.A;
+            const float* hot = att_hot + ((int64_t)bt * d.M + m) * d.A;
             const float* pa = att_pred + ((int64_t)b * d.N + n) * d.A;
             s_att += d.attribute_weight * att_cost_elem(hot, pa, d.A);
             if (d_att) {
@@ -433,35 +435,75 @@ int check_loss_desc(const bdetr_loss_desc* d, const char* who) {
 
 }  // namespace
 
-extern "C" int bdetr_cost_matrix(const bdetr_loss_desc* d, const float* cat_pred, const float* att_pred,
-                                 const float* box_pred, const int32_t* cat_ids, const float* att_hot,
-                                 const float* bbox, const int32_t* num_objects, float* cost, float* cost_cat, float* cost_att,
-                                 float* cost_box, void* stream) {
-    if (int e = check_loss_desc(d, "bdetr_cost_matrix")) return e;
-    BDETR_CHECK_ARG(cat_pred && box_pred && cat_ids && bbox && cost, "bdetr_cost_matrix: null pointer");
-    BDETR_CHECK_ARG(d->attribute_weight == 0.f || d->A == 0 || (att_pred && att_hot), "bdetr_cost_matrix: attribute tensors required when attribute_weight != 0");
+namespace {
+
+bool period_ok(int B, int period) { return period > 0 && B % period == 0; }
+
+int cost_matrix_impl(const char* who, const bdetr_loss_desc* d, int period, const float* cat_pred, const float* att_pred, const float* box_pred,
+                     const int32_t* cat_ids, const float* att_hot, const float* bbox, const int32_t* num_objects, float* cost, float* cost_cat,
+                     float* cost_att, float* cost_box, void* stream) {
+    if (int e = check_loss_desc(d, who)) return e;
+    BDETR_CHECK_ARG(cat_pred && box_pred && cat_ids && bbox && cost, "%s: null pointer", who);
+    BDETR_CHECK_ARG(d->attribute_weight == 0.f || d->A == 0 || (att_pred && att_hot), "%s: attribute tensors required when attribute_weight != 0", who);
+    BDETR_CHECK_ARG(period_ok(d->B, period), "%s: B=%d is not a multiple of period=%d", who, d->B, period);
     hipLaunchKernelGGL(cost_matrix_kernel, dim3(d->M, d->B), dim3(64), 0, (hipStream_t)stream, *d, cat_pred, att_pred, box_pred, cat_ids, att_hot, bbox,
-                       num_objects, cost, cost_cat, cost_att, cost_box);
+                       num_objects, period, cost, cost_cat, cost_att, cost_box);
     return bdetr_launch_status("cost_matrix");
 }
 
-extern "C" int bdetr_lsa(const float* cost, const int32_t* num_objects, int B, int M, int N, int32_t* match, void* stream) {
-    BDETR_CHECK_ARG(cost && num_objects && match && B > 0 && M > 0 && N > 0, "bdetr_lsa: bad arguments");
+int lsa_impl(const char* who, const float* cost, const int32_t* num_objects, int B, int period, int M, int N, int32_t* match, void* stream) {
+    BDETR_CHECK_ARG(cost && num_objects && match && B > 0 && M > 0 && N > 0 && period_ok(B, period), "%s: bad arguments", who);
     const int maxdim = M > N ? M : N;
     size_t state = (size_t)maxdim * (3 * sizeof(double) + 4 * sizeof(int) + 2) + 16;
     size_t with_cost = state + (size_t)M * N * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
     if (with_cost <= 150 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lsa_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)with_cost);
-        if (e != hipSuccess) { bdetr_set_error("bdetr_lsa: cannot reserve %zu bytes of LDS: %s", with_cost, hipGetErrorString(e)); return (int)e; }
-        hipLaunchKernelGGL((lsa_kernel<true>), dim3(B), dim3(64), with_cost, st, cost, num_objects, M, N, match, maxdim);
+        if (e != hipSuccess) { bdetr_set_error("%s: cannot reserve %zu bytes of LDS: %s", who, with_cost, hipGetErrorString(e)); return (int)e; }
+        hipLaunchKernelGGL((lsa_kernel<true>), dim3(B), dim3(64), with_cost, st, cost, num_objects, M, N, match, maxdim, period);
     } else {
-        BDETR_CHECK_ARG(state <= 150 * 1024, "bdetr_lsa: problem too large (max(M,N)=%d)", maxdim);
+        BDETR_CHECK_ARG(state <= 150 * 1024, "%s: problem too large (max(M,N)=%d)", who, maxdim);
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lsa_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)state);
-        if (e != hipSuccess) { bdetr_set_error("bdetr_lsa: cannot reserve %zu bytes of LDS: %s", state, hipGetErrorString(e)); return (int)e; }
-        hipLaunchKernelGGL((lsa_kernel<false>), dim3(B), dim3(64), state, st, cost, num_objects, M, N, match, maxdim);
+        if (e != hipSuccess) { bdetr_set_error("%s: cannot reserve %zu bytes of LDS: %s", who, state, hipGetErrorString(e)); return (int)e; }
+        hipLaunchKernelGGL((lsa_kernel<false>), dim3(B), dim3(64), state, st, cost, num_objects, M, N, match, maxdim, period);
     }
     return bdetr_launch_status("lsa");
+}
+
+int set_loss_impl(const char* who, const bdetr_loss_desc* d, int period, const float* cat_pred, const float* att_pred, const float* box_pred,
+                  const int32_t* cat_ids, const float* att_hot, const float* bbox, const int32_t* num_objects, const int32_t* match, float* losses,
+                  float* d_cat, float* d_att, float* d_box, float loss_scale, void* stream) {
+    if (int e = check_loss_desc(d, who)) return e;
+    BDETR_CHECK_ARG(cat_pred && box_pred && cat_ids && bbox && num_objects && match && losses, "%s: null pointer", who);
+    BDETR_CHECK_ARG(period_ok(d->B, period), "%s: B=%d is not a multiple of period=%d", who, d->B, period);
+    hipLaunchKernelGGL(set_loss_kernel, dim3(d->B), dim3(256), (size_t)d->N * sizeof(int), (hipStream_t)stream, *d, cat_pred, att_pred, box_pred,
+                       cat_ids, att_hot, bbox, num_objects, match, losses, d_cat, d_att, d_box, loss_scale, period);
+    return bdetr_launch_status("set_loss");
+}
+
+}  // namespace
+
+extern "C" int bdetr_cost_matrix(const bdetr_loss_desc* d, const float* cat_pred, const float* att_pred,
+                                 const float* box_pred, const int32_t* cat_ids, const float* att_hot,
+                                 const float* bbox, const int32_t* num_objects, float* cost, float* cost_cat, float* cost_att,
+                                 float* cost_box, void* stream) {
+    return cost_matrix_impl("bdetr_cost_matrix", d, d ? d->B : 1, cat_pred, att_pred, box_pred, cat_ids, att_hot, bbox, num_objects, cost, cost_cat, cost_att,
+                            cost_box, stream);
+}
+
+extern "C" int bdetr_cost_matrix_tiled(const bdetr_loss_desc* d, int period, const float* cat_pred, const float* att_pred,
+                                       const float* box_pred, const int32_t* cat_ids, const float* att_hot,
+                                       const float* bbox, const int32_t* num_objects, float* cost, void* stream) {
+    return cost_matrix_impl("bdetr_cost_matrix_tiled", d, period, cat_pred, att_pred, box_pred, cat_ids, att_hot, bbox, num_objects, cost, nullptr, nullptr,
+                            nullptr, stream);
+}
+
+extern "C" int bdetr_lsa(const float* cost, const int32_t* num_objects, int B, int M, int N, int32_t* match, void* stream) {
+    return lsa_impl("bdetr_lsa", cost, num_objects, B, B, M, N, match, stream);
+}
+
+extern "C" int bdetr_lsa_tiled(const float* cost, const int32_t* num_objects, int B, int period, int M, int N, int32_t* match, void* stream) {
+    return lsa_impl("bdetr_lsa_tiled", cost, num_objects, B, period, M, N, match, stream);
 }
 
 extern "C" int bdetr_match_to_mask(const int32_t* match, float* mask, int B, int M, int N, void* stream) {
@@ -475,9 +517,15 @@ extern "C" int bdetr_set_loss(const bdetr_loss_desc* d, const float* cat_pred, c
                               const float* bbox, const int32_t* num_objects, const int32_t* match,
                               float* losses, float* d_cat, float* d_att, float* d_box, float loss_scale,
                               void* stream) {
-    if (int e = check_loss_desc(d, "bdetr_set_loss")) return e;
-    BDETR_CHECK_ARG(cat_pred && box_pred && cat_ids && bbox && num_objects && match && losses, "bdetr_set_loss: null pointer");
-    hipLaunchKernelGGL(set_loss_kernel, dim3(d->B), dim3(256), (size_t)d->N * sizeof(int), (hipStream_t)stream, *d, cat_pred, att_pred, box_pred,
-                       cat_ids, att_hot, bbox, num_objects, match, losses, d_cat, d_att, d_box, loss_scale);
-    return bdetr_launch_status("set_loss");
+    return set_loss_impl("bdetr_set_loss", d, d ? d->B : 1, cat_pred, att_pred, box_pred, cat_ids, att_hot, bbox, num_objects, match, losses, d_cat, d_att,
+                         d_box, loss_scale, stream);
+}
+
+extern "C" int bdetr_set_loss_tiled(const bdetr_loss_desc* d, int period, const float* cat_pred, const float* att_pred,
+                                    const float* box_pred, const int32_t* cat_ids, const float* att_hot,
+                                    const float* bbox, const int32_t* num_objects, const int32_t* match,
+                                    float* losses, float* d_cat, float* d_att, float* d_box, float loss_scale,
+                                    void* stream) {
+    return set_loss_impl("bdetr_set_loss_tiled", d, period, cat_pred, att_pred, box_pred, cat_ids, att_hot, bbox, num_objects, match, losses, d_cat, d_att,
+                         d_box, loss_scale, stream);
 }

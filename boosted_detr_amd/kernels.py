@@ -706,6 +706,47 @@ def bn_bwd(dout, out, x2d, mean, rstd, gamma, relu, frozen, want_residual_grad=F
     return dx, dgamma, dbeta, dres
 
 
+# ---- BatchNorm over row groups (csrc/groupnorm_rows.hip): x2d is [G * R, C], group g = rows [g R, (g + 1) R) ----
+def bn_rows_stats(x2d, groups: int, eps):
+    """Per-group batch statistics: (mean, rstd, var), each [G, C] (biased variance).  Raises the range guard for non-finite statistics."""
+    _chk(x2d)
+    rows, Cc = x2d.shape
+    assert rows % groups == 0, (rows, groups)
+    mean, rstd, var = empty(groups, Cc, like=x2d), empty(groups, Cc, like=x2d), empty(groups, Cc, like=x2d)
+    check(_lib.lib().bdetr_bn_rows_stats(_p(x2d), groups, rows // groups, Cc, eps, _p(mean), _p(rstd), _p(var),
+                                         _p(overflow_flag()) if _GUARD_ACTIVE[0] else None, _stream()), "bn_rows_stats")
+    return mean, rstd, var
+
+
+def bn_rows_apply(x2d, groups: int, mean, rstd, gamma, beta, var=None, momentum=0.0, moving_mean=None, moving_var=None):
+    """out = gamma * (x - mean_g) * rstd_g + beta.  mean / rstd: [G, C] from bn_rows_stats, or [C] (moving statistics, shared by every
+    group).  With moving_mean / moving_var (and var): the launch also folds the G groups' statistics into them in group order, as G
+    sequential keras calls would - skipped while the range guard is up."""
+    _chk(x2d, mean, rstd, gamma, beta, var, moving_mean, moving_var)
+    rows, Cc = x2d.shape
+    assert rows % groups == 0, (rows, groups)
+    grouped = mean.dim() == 2
+    out = torch.empty_like(x2d)
+    check(_lib.lib().bdetr_bn_rows_apply(_p(x2d), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(out), groups, rows // groups, Cc, int(grouped), _p(var),
+                                         momentum, _p(moving_mean), _p(moving_var),
+                                         _p(overflow_flag()) if (_GUARD_ACTIVE[0] and moving_mean is not None) else None, _stream()), "bn_rows_apply")
+    return out
+
+
+def bn_rows_bwd(dout, x2d, groups: int, mean, rstd, gamma, frozen, dgamma=None, dbeta=None):
+    """(dx, dgamma, dbeta): dgamma / dbeta summed over all groups, dx from each row's own group (frozen: dx = g * rstd * gamma)."""
+    _chk(dout, x2d, mean, rstd, gamma, dgamma, dbeta)
+    rows, Cc = x2d.shape
+    assert rows % groups == 0 and dout.shape == x2d.shape, (rows, groups)
+    dx = torch.empty_like(x2d)
+    dgamma = empty(Cc, like=x2d) if dgamma is None else dgamma
+    dbeta = empty(Cc, like=x2d) if dbeta is None else dbeta
+    ws = empty(2 * groups * Cc, like=x2d)
+    check(_lib.lib().bdetr_bn_rows_bwd(_p(dout), _p(x2d), _p(mean), _p(rstd), _p(gamma), int(mean.dim() == 2), int(frozen), _p(dx), _p(dgamma), _p(dbeta),
+                                       _p(ws), groups, rows // groups, Cc, _stream()), "bn_rows_bwd")
+    return dx, dgamma, dbeta
+
+
 # --------------------------------------------------------------------------------------
 # pooling / softmax / layernorm / activations
 # --------------------------------------------------------------------------------------
@@ -969,9 +1010,16 @@ def loss_desc(B, M, N, Cc, A, category_weight, attribute_weight, box_weight, exi
     return LossDesc(B, M, N, Cc, A, category_weight, attribute_weight, box_weight, exist_weight)
 
 
-def cost_matrix(d: LossDesc, cat_pred, att_pred, box_pred, cat_ids, att_hot, bbox, num_objects, components=False):
+def cost_matrix(d: LossDesc, cat_pred, att_pred, box_pred, cat_ids, att_hot, bbox, num_objects, components=False, period=None):
+    """period: the predictions are d.B = L * period images (several calls stacked), the targets `period` images (bdetr_cost_matrix_tiled)."""
     _chk(cat_pred, att_pred, box_pred, att_hot, bbox)
     _chk(cat_ids, num_objects, dtype=torch.int32)
+    if period is not None:
+        assert not components and d.B % period == 0 and cat_ids.shape[0] == period and num_objects.numel() == period
+        cost = empty(d.B, d.M, d.N, like=cat_pred)
+        check(_lib.lib().bdetr_cost_matrix_tiled(C.byref(d), period, _p(cat_pred), _p(att_pred), _p(box_pred), _p(cat_ids), _p(att_hot), _p(bbox),
+                                                 _p(num_objects), _p(cost), _stream()), "cost_matrix_tiled")
+        return cost
     cost = empty(d.B, d.M, d.N, like=cat_pred)
     comps = [empty(d.B, d.M, d.N, like=cat_pred) for _ in range(3)] if components else [None] * 3
     check(_lib.lib().bdetr_cost_matrix(C.byref(d), _p(cat_pred), _p(att_pred), _p(box_pred), _p(cat_ids), _p(att_hot), _p(bbox),
@@ -979,11 +1027,15 @@ def cost_matrix(d: LossDesc, cat_pred, att_pred, box_pred, cat_ids, att_hot, bbo
     return (cost, comps) if components else cost
 
 
-def lsa(cost, num_objects):
+def lsa(cost, num_objects, period=None):
     _chk(cost)
     _chk(num_objects, dtype=torch.int32)
     B, M, N = cost.shape
     match = empty(B, M, like=cost, dtype=torch.int32)
+    if period is not None:
+        assert B % period == 0 and num_objects.numel() == period
+        check(_lib.lib().bdetr_lsa_tiled(_p(cost), _p(num_objects), B, period, M, N, _p(match), _stream()), "lsa_tiled")
+        return match
     check(_lib.lib().bdetr_lsa(_p(cost), _p(num_objects), B, M, N, _p(match), _stream()), "lsa")
     return match
 
@@ -996,13 +1048,19 @@ def match_to_mask(match, N):
     return mask
 
 
-def set_loss(d: LossDesc, cat_pred, att_pred, box_pred, cat_ids, att_hot, bbox, num_objects, match, loss_scale=1.0, want_grads=True):
+def set_loss(d: LossDesc, cat_pred, att_pred, box_pred, cat_ids, att_hot, bbox, num_objects, match, loss_scale=1.0, want_grads=True, period=None):
     _chk(cat_pred, att_pred, box_pred, att_hot, bbox)
     _chk(cat_ids, num_objects, match, dtype=torch.int32)
     losses = empty(6, d.B, like=cat_pred)
     d_cat = torch.empty_like(cat_pred) if want_grads else None
     d_att = torch.empty_like(att_pred) if (want_grads and att_pred is not None) else None
     d_box = torch.empty_like(box_pred) if want_grads else None
+    if period is not None:
+        assert d.B % period == 0 and cat_ids.shape[0] == period and num_objects.numel() == period
+        check(_lib.lib().bdetr_set_loss_tiled(C.byref(d), period, _p(cat_pred), _p(att_pred), _p(box_pred), _p(cat_ids), _p(att_hot), _p(bbox),
+                                              _p(num_objects), _p(match), _p(losses), _p(d_cat), _p(d_att), _p(d_box), float(loss_scale), _stream()),
+              "set_loss_tiled")
+        return losses, d_cat, d_att, d_box
     check(_lib.lib().bdetr_set_loss(C.byref(d), _p(cat_pred), _p(att_pred), _p(box_pred), _p(cat_ids), _p(att_hot), _p(bbox), _p(num_objects),
                                     _p(match), _p(losses), _p(d_cat), _p(d_att), _p(d_box), float(loss_scale), _stream()), "set_loss")
     return losses, d_cat, d_att, d_box

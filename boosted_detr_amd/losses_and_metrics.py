@@ -89,18 +89,22 @@ class MatchingLoss(Layer):
         self.built = True
 
     def call(self, inputs, training=False):
+        """The predictions may hold several calls stacked along the batch axis ([L * B, N, ...] against targets of B images: the decoder
+        layers' heads under DETR(use_intermediate_losses=True)): cost matrix, assignment and loss then run once over all L * B images,
+        every block of B images being one loss call of its own, and `losses` is [6][L * B]."""
         y_true, y_pred = inputs
         category, attribute, bbox, num_objects = y_true
         cat_preds, attribute_preds, box_preds = y_pred
         B, N, Cc = cat_preds.shape
         M = category.shape[1]
         A = attribute_preds.shape[-1]
+        period = category.shape[0] if category.shape[0] != B else None
         d = K.loss_desc(B, M, N, Cc, A, self.category_weight, self.attribute_weight, self.box_weight, self.exist_weight)
-        cost = K.cost_matrix(d, cat_preds, attribute_preds, box_preds, category, attribute, bbox, num_objects)
-        match = K.lsa(cost, num_objects)
+        cost = K.cost_matrix(d, cat_preds, attribute_preds, box_preds, category, attribute, bbox, num_objects, period=period)
+        match = K.lsa(cost, num_objects, period=period)
         tape = current_tape()
         losses, d_cat, d_att, d_box = K.set_loss(d, cat_preds, attribute_preds, box_preds, category, attribute, bbox,
-                                                 num_objects, match, loss_scale=self.loss_scale, want_grads=tape is not None)
+                                                 num_objects, match, loss_scale=self.loss_scale, want_grads=tape is not None, period=period)
         self.last_match, self.last_cost, self.last_num_objects = match, cost, num_objects
         if tape is not None:
             tape.record([losses], [cat_preds, attribute_preds, box_preds], lambda g: (d_cat, d_att, d_box))

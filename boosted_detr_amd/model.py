@@ -7,10 +7,12 @@ model (``add_loss`` of a per-image [B] vector, 5 ``add_metric`` calls), ``test_s
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
-from . import backbone, losses_and_metrics, prediction_heads, tokenizers, transformers
+from . import backbone, losses_and_metrics, ops, prediction_heads, tokenizers, transformers
 from .engine import to_device
 from .training import Model
 
@@ -57,6 +59,7 @@ class DETR(Model):
         train_panoptic_head = bool(kwargs.pop("train_panoptic_head", False))
         with_panoptic_head = bool(kwargs.pop("with_panoptic_head", False)) or train_panoptic_head
         mask_weight = float(kwargs.pop("mask_weight", 1.0))
+        use_intermediate_losses = bool(kwargs.pop("use_intermediate_losses", False))
         super().__init__(name=name, seed=seed)                      # pad_value / oov_value etc. are swallowed like the reference's **kwargs
         category_weight = box_weight = exist_weight = None
         if classification_only:
@@ -110,6 +113,21 @@ class DETR(Model):
                 self.PanopticAttention.trainable = False
                 self.PanopticNeck.trainable = False
         self._panoptic_inputs = None
+        # Deep supervision (model.py:179,186: a switch the reference hard-codes to False): the shared heads, the matcher and the set loss
+        # behind EVERY decoder block, the loss and the four loss metrics summed over the blocks; IOU, the returned predictions and
+        # loss_fn.last_match stay the last block's.  May be changed between steps.  BDETR_AUX_STACKED=0 (read here) runs it as the
+        # reference's per-block loop over the existing kernels instead of ONE pass of heads / matcher / loss over the stacked outputs.
+        self.use_intermediate_losses = use_intermediate_losses
+        self.aux_stacked = os.environ.get("BDETR_AUX_STACKED", "1") != "0"
+        self.aux_predictions = None       # per decoder block [cat, att, box] of the last training call with the option on
+        self.aux_logits = None            # ... and the three heads' pre-activation outputs
+        self._aux_matches = None
+
+    @property
+    def aux_matches(self):
+        """int32 [L, B, M]: every decoder block's assignment of the last training call with use_intermediate_losses, or None."""
+        m = self._aux_matches
+        return torch.stack(m) if isinstance(m, list) else m
 
     def _require_panoptic_head(self) -> None:
         if self.PanopticAttention is None:
@@ -129,6 +147,8 @@ class DETR(Model):
         c.update({k: getattr(self, k) for k in ("num_object_preds", "image_size", "num_encoder_blocks", "num_encoder_heads", "encoder_dim",
                                                  "num_decoder_blocks", "num_decoder_heads", "decoder_dim", "num_panoptic_heads",
                                                  "panoptic_dim", "vocab_dict")})
+        if getattr(self, "use_intermediate_losses", False):
+            c["use_intermediate_losses"] = True
         return c
 
     def call(self, inputs, training=False, raw=False):
@@ -145,11 +165,15 @@ class DETR(Model):
         encoder_features, decoder_features, encoder_key, decoder_positional = \
             self.DecoderPrep([encoder_features, positional_encoding], training=training)
 
-        use_intermediate_losses = False       # hard-coded in the reference (model.py:179)
+        use_intermediate_losses = bool(self.use_intermediate_losses)       # (hard-coded False in the reference, model.py:179)
+        stacked = training and use_intermediate_losses and self.aux_stacked and self.num_decoder_blocks > 1
         loss_terms, metrics_i, y_pred_i = [], None, None
+        layer_outputs, aux_preds, aux_logits, aux_matches = [], [], [], []
         for i in range(self.num_decoder_blocks):
             decoder_features = self.DecoderBlocks[i]([encoder_features, decoder_features, encoder_key, decoder_positional], training=training)
-            if training and (use_intermediate_losses or i >= self.num_decoder_blocks - 1):
+            if stacked:
+                layer_outputs.append(decoder_features)
+            elif training and (use_intermediate_losses or i >= self.num_decoder_blocks - 1):
                 cat_preds_i = self.CategoryPredictionHead([decoder_features], training=training)
                 attribute_preds_i = self.AttributePredictionHead([decoder_features], training=training)
                 box_coord_preds_i = self.BoxPredictionHead([decoder_features], training=training)
@@ -157,6 +181,14 @@ class DETR(Model):
                 losses_i, metrics_i = self.loss_fn([y_true, y_pred_i])
                 loss_terms.append(losses_i)
                 self._loss_roots.append(self.loss_fn._losses_tensor)
+                aux_preds.append(y_pred_i)
+                aux_logits.append([h.last_logits for h in (self.CategoryPredictionHead, self.AttributePredictionHead, self.BoxPredictionHead)])
+                aux_matches.append(self.loss_fn.last_match)
+        if stacked:
+            loss_terms, metrics_i, y_pred_i, aux_preds, aux_logits, aux_matches = self._stacked_heads_and_losses(layer_outputs, y_true)
+        if training:
+            self.aux_predictions, self.aux_logits, self._aux_matches = \
+                (aux_preds, aux_logits, aux_matches) if use_intermediate_losses else (None, None, None)
 
         if self.PanopticAttention is not None:
             self._panoptic_inputs = (image_encoding, decoder_features, positional_encoding.value)
@@ -175,6 +207,29 @@ class DETR(Model):
         attribute_preds = self.AttributePredictionHead([decoder_features], training=training)
         box_coord_preds = self.BoxPredictionHead([decoder_features], training=training)
         return _inference_outputs(self, cat_preds, attribute_preds, box_coord_preds, raw)
+
+    def _stacked_heads_and_losses(self, layer_outputs, y_true):
+        """The shared heads, the matcher and the set loss behind every decoder block as ONE pass over the blocks' outputs stacked along
+        the batch axis ([L * B, N, D]): every head GEMM, the cost matrix, the assignment (one workgroup per (block, image)) and the loss
+        run once, BatchNormalization keeps each block's own batch statistics (ops.batchnorm_rows) and every head parameter receives one
+        gradient contribution.  Returns what the per-block loop leaves: per-block loss terms, the last block's metrics / predictions,
+        per-block predictions, logits and assignments (views of the stacked tensors)."""
+        L, B = len(layer_outputs), layer_outputs[0].shape[0]
+        features = ops.stack_rows(layer_outputs)
+        heads = (self.CategoryPredictionHead, self.AttributePredictionHead, self.BoxPredictionHead)
+        y_pred = [h([features], training=True, groups=L) for h in heads]
+        losses, metrics = self.loss_fn([y_true, y_pred])
+        self._loss_roots.append(self.loss_fn._losses_tensor)
+        block = lambda t, l: t[l * B:(l + 1) * B]
+        loss_terms = [[block(t, l) for t in losses] for l in range(L)]
+        aux_preds = [[block(t, l) for t in y_pred] for l in range(L)]
+        aux_logits = [[block(h.last_logits, l) for h in heads] for l in range(L)]
+        for h in heads:
+            h.last_logits = block(h.last_logits, L - 1)
+        lf = self.loss_fn
+        aux_matches = lf.last_match.view(L, B, -1)
+        lf.last_match, lf.last_cost = block(lf.last_match, L - 1), block(lf.last_cost, L - 1)
+        return loss_terms, [block(metrics[0], L - 1)], aux_preds[-1], aux_preds, aux_logits, aux_matches
 
     def _register(self, loss_terms, metrics_i, mask_loss=None):
         """model.py:206-221.  Per-learner loss vectors are kept as a list (summed on the host when

@@ -19,7 +19,7 @@ import torch
 
 from . import kernels as K
 from . import _lib
-from .engine import WEIGHTS_VERSION, Variable, current_tape, dense_contribution, info, materialise, own, side_task, tag
+from .engine import WEIGHTS_VERSION, Variable, capture, current_tape, dense_contribution, info, materialise, own, side_task, tag
 
 # Dropout masks are keyed by (per-step seed, dropout site, element index).  The per-step seed lives in HBM
 # (one int64 the host rewrites before every step), the site salt is a launch argument: a captured step graph then
@@ -246,6 +246,9 @@ class _PackCache:
     def __init__(self, alloc, table_row, pack):
         self.alloc, self.table_row, self.pack = alloc, table_row, pack
         self.rows, self.table, self.version = [], None, -1       # rows: (weakref(var), value, fwd copy, bwd copy)
+        # tables a captured step launched its refresh with: the graph holds their ADDRESS, so they outlive the rebuild that a later
+        # model's variables trigger (a second model built after a capture freed the table under the first one's replays)
+        self.captured_tables = []
 
     def get(self, w: Variable):
         c = getattr(w, "_packs", None)
@@ -259,6 +262,8 @@ class _PackCache:
                 rows = np.array([self.table_row(*r[1:]) for r in self.rows], np.int64)
                 self.table = torch.from_numpy(rows).to(w.value.device)
             self.pack(self.table)
+            if capture() is not None and not any(t is self.table for t in self.captured_tables):
+                self.captured_tables.append(self.table)
             self.version = WEIGHTS_VERSION[0]
         return c[1], c[2]
 
@@ -573,6 +578,49 @@ def batchnorm(x: torch.Tensor, bn: BNState, training: bool, bessel: bool) -> tor
         return (own(dx.view(x.shape)),)
 
     _rec([out], [x], backward)
+    return out
+
+
+def batchnorm_rows(x: torch.Tensor, bn: BNState, training: bool, groups: int) -> torch.Tensor:
+    """BatchNormalization of `groups` stacked calls: x is [groups * B, ..., C] and every [B, ..., C] block is normalised with its own batch
+    statistics (biased variance: the heads' 3-D keras path), the moving statistics updated once per block in block order
+    (csrc/groupnorm_rows.hip).  One statistics + one apply launch forward, two launches backward, one contribution to gamma / beta."""
+    x2d = _2d(x)
+    g, b = bn.gamma.value, bn.beta.value
+    if training:
+        mean, rstd, var = K.bn_rows_stats(x2d, groups, bn.eps)
+        out2d = K.bn_rows_apply(x2d, groups, mean, rstd, g, b, var, bn.momentum, bn.moving_mean.value, bn.moving_var.value)
+    else:
+        K.demote_split_forward()
+        mean, rstd = K.bn_stats_frozen(bn.moving_mean.value, bn.moving_var.value, bn.eps)
+        out2d = K.bn_rows_apply(x2d, groups, mean, rstd, g, b)
+    out = out2d.view(x.shape)
+
+    def backward(g_out):
+        sg, sb = GradSink(bn.gamma), GradSink(bn.beta)
+        dx, _, _ = K.bn_rows_bwd(_2d(g_out.contiguous()), x2d, groups, mean, rstd, bn.gamma.value, not training, dgamma=sg.buf, dbeta=sb.buf)
+        sg.commit()
+        sb.commit()
+        return (own(dx.view(x.shape)),)
+
+    _rec([out], [x], backward)
+    return out
+
+
+def stack_rows(xs) -> torch.Tensor:
+    """[B, N, D] x L -> [L * B, N, D] (the decoder layers' outputs in front of the shared heads).  The backward hands every input its own
+    [B, N, D] block of the incoming gradient; the Tape adds it to what the next decoder block sends."""
+    L, B = len(xs), xs[0].shape[0]
+    out = torch.empty((L * B,) + tuple(xs[0].shape[1:]), dtype=xs[0].dtype, device=xs[0].device)
+    for l, x in enumerate(xs):
+        K.copy_cols(x.contiguous(), x.shape[-1], out[l * B:(l + 1) * B], 0)
+
+    def backward(g):
+        # the blocks are disjoint and nothing else reads an owned g behind this node: each block is then the Tape's own
+        g, mine = g.contiguous(), info(g).owned
+        return tuple(own(g[l * B:(l + 1) * B]) if mine else g[l * B:(l + 1) * B] for l in range(L))
+
+    _rec([out], list(xs), backward)
     return out
 
 

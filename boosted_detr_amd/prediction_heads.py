@@ -36,12 +36,17 @@ class _Head(Layer):
         self.name = keep
         self.DenseOut = _Dense(self, self.out_name, self.hidden_dim, self.out_dim, "glorot_normal")
 
-    def trunk(self, inputs, training):
+    def trunk(self, inputs, training, groups=1):
+        """groups > 1: `features` is [groups * B, N, D], the outputs of that many decoder layers stacked; every [B, N, D] block sees the
+        BatchNormalization of a call of its own (ops.batchnorm_rows), the Dense layers run once over all of them."""
         features = inputs[0]                                  # [B, N, D]
         if features.shape[1] != self.num_preds:
             raise NotImplementedError("Conv1D re-count branch (prediction_heads.py:120-123) is off the hot path")
         x = self.DenseHidden(features, K.ACT_RELU)
-        x = ops.batchnorm(x, self.BatchNorm, training and self.trainable, bessel=False)
+        if groups > 1:
+            x = ops.batchnorm_rows(x, self.BatchNorm, training and self.trainable, groups)
+        else:
+            x = ops.batchnorm(x, self.BatchNorm, training and self.trainable, bessel=False)
         # the pre-activation output (softmax / sigmoid / box-sigmoid input: prediction_heads.py:111,180,44) stays reachable
         # as `last_logits`: the parity tests compare it with the oracle's, the north star's "logits within 1e-3"
         self.last_logits = self.DenseOut(x)
@@ -59,8 +64,8 @@ class BoxPredictionHead(_Head):
     def __init__(self, hidden_dim, num_preds, name="BoxPredictionHead", **kwargs):
         super().__init__(hidden_dim, num_preds, 4, name, **kwargs)
 
-    def call(self, inputs, training=False):
-        return ops.box_sigmoid(self.trunk(inputs, training))     # 3*sigmoid(x/100)-1 in (-1,2), COCO [xmin,ymin,w,h]
+    def call(self, inputs, training=False, groups=1):
+        return ops.box_sigmoid(self.trunk(inputs, training, groups))     # 3*sigmoid(x/100)-1 in (-1,2), COCO [xmin,ymin,w,h]
 
 
 class SingleClassPredictionHead(_Head):
@@ -75,8 +80,8 @@ class SingleClassPredictionHead(_Head):
         c.update({"num_classes": self.num_classes})
         return c
 
-    def call(self, inputs, training=False):
-        return ops.softmax_lastdim(self.trunk(inputs, training))
+    def call(self, inputs, training=False, groups=1):
+        return ops.softmax_lastdim(self.trunk(inputs, training, groups))
 
 
 class MultiClassPredictionHead(_Head):
@@ -91,5 +96,5 @@ class MultiClassPredictionHead(_Head):
         c.update({"num_classes": self.num_classes})
         return c
 
-    def call(self, inputs, training=False):
-        return ops.sigmoid(self.trunk(inputs, training))
+    def call(self, inputs, training=False, groups=1):
+        return ops.sigmoid(self.trunk(inputs, training, groups))

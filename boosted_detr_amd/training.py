@@ -1104,7 +1104,8 @@ class Model(Layer):
         dp = self._dp
         return (id(opt), (id(dp), dp.world, dp.active, dp.overlap) if dp is not None else None,
                 tuple(getattr(opt, "_built_for", None) or ()), tuple(id(v) for v in self.trainable_variables),
-                bool(self.guard_check_every), transformers.AttentionBlock.dropout_rate, transformers.FeedForwardBlock.dropout_rate, loss, hyper)
+                bool(self.guard_check_every), transformers.AttentionBlock.dropout_rate, transformers.FeedForwardBlock.dropout_rate, loss, hyper,
+                bool(getattr(self, "use_intermediate_losses", False)), bool(getattr(self, "aux_stacked", True)))
 
     def _finish_step(self, stage_scalars: bool) -> Dict[str, list]:
         """A step behind its backward pass, eager or captured: stage the gradients, raise the guard for a non-finite loss, finish the

@@ -376,7 +376,29 @@ int bdetr_bn_bwd(const float* dout, const float* out, const float* x, const floa
                  float* ws, int64_t rows, int C, void* stream);
 
 /* ------------------------------------------------------------------------
- * K4  3x3/2 max-pool with 1-pixel zero pad (ResNet-50 pool1_pad + pool1_pool)
+ * K3b BatchNormalization over row groups (csrc/groupnorm_rows.hip): x is [G*R][C] and group g = rows [g*R, (g+1)*R) is
+ *     normalised with its OWN batch statistics - what G separate keras BatchNormalization calls on [R][C] compute
+ *     (the shared prediction heads behind every decoder layer, model.py:179-186 with use_intermediate_losses).
+ *     One launch for the statistics, one for the apply, two for the backward, independent of G; no atomics, fixed
+ *     summation order.  C % 4 == 0, G <= 65535, G*R < 2^31, tensors 16-byte aligned.  G = 1 is plain BatchNorm.
+ * ---------------------------------------------------------------------- */
+/* mean, rstd, var: [G][C] (biased variance, fp64 finalise).  guard_flag (may be null): set when a statistic is not finite. */
+int bdetr_bn_rows_stats(const float* x, int G, int64_t R, int C, float eps, float* mean, float* rstd, float* var,
+                        int* guard_flag, void* stream);
+/* out = gamma*(x-mean_g)*rstd_g + beta.  grouped_stats != 0: mean/rstd are [G][C], else [C] shared by every group (moving
+ * statistics).  moving_mean != NULL (needs grouped_stats and var): the moving statistics are updated G times in group order,
+ * mm <- momentum*mm + (1-momentum)*mean_g (variance alike: biased) - unless guard_flag (may be null) is set. */
+int bdetr_bn_rows_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* out,
+                        int G, int64_t R, int C, int grouped_stats, const float* var, float momentum, float* moving_mean,
+                        float* moving_var, const int* guard_flag, void* stream);
+/* backward: dgamma[C] / dbeta[C] = sums over ALL rows of g*xhat / g (xhat from the row's own group), dx from the row's own
+ * group's sums; frozen != 0: the statistics were constants (dx = g*rstd*gamma).  ws: 2*G*C floats. */
+int bdetr_bn_rows_bwd(const float* dout, const float* x, const float* mean, const float* rstd, const float* gamma,
+                      int grouped_stats, int frozen, float* dx, float* dgamma, float* dbeta, float* ws, int G, int64_t R, int C,
+                      void* stream);
+
+/* ------------------------------------------------------------------------
+ * K4 3x3/2 max-pool with 1-pixel zero pad (ResNet-50 pool1_pad + pool1_pool)
  * ---------------------------------------------------------------------- */
 int bdetr_maxpool3x3s2_fwd(const float* x, float* y, int N, int H, int W, int C, int OH, int OW, void* stream);
 int bdetr_maxpool3x3s2_bwd(const float* x, const float* y, const float* dy, float* dx,
@@ -594,6 +616,20 @@ int bdetr_set_loss(const bdetr_loss_desc* d, const float* cat_pred, const float*
                    const float* bbox, const int32_t* num_objects, const int32_t* match,
                    float* losses, float* d_cat, float* d_att, float* d_box, float loss_scale,
                    void* stream);
+/* The same three over predictions of SEVERAL calls stacked along the batch axis (the decoder layers' heads, model.py:179-186 with
+ * use_intermediate_losses): d->B = L * period prediction images, the targets (cat_ids, att_hot, bbox, num_objects) hold `period` images and
+ * prediction image b is matched against target image b % period; each block of `period` images is one loss call of its own (its
+ * 1 + sum(num_objects) normaliser runs over the `period` target images).  cost [B,M,N], match [B,M], losses [6][B]. */
+int bdetr_cost_matrix_tiled(const bdetr_loss_desc* d, int period, const float* cat_pred, const float* att_pred,
+                            const float* box_pred, const int32_t* cat_ids, const float* att_hot,
+                            const float* bbox, const int32_t* num_objects, float* cost, void* stream);
+int bdetr_lsa_tiled(const float* cost, const int32_t* num_objects, int B, int period, int M, int N,
+                    int32_t* match, void* stream);
+int bdetr_set_loss_tiled(const bdetr_loss_desc* d, int period, const float* cat_pred, const float* att_pred,
+                         const float* box_pred, const int32_t* cat_ids, const float* att_hot,
+                         const float* bbox, const int32_t* num_objects, const int32_t* match,
+                         float* losses, float* d_cat, float* d_att, float* d_box, float loss_scale,
+                         void* stream);
 /* mask[B,M,N] = 1 where match[b][m]==n (MatchingAssignment output, for inspection/tests) */
 int bdetr_match_to_mask(const int32_t* match, float* mask, int B, int M, int N, void* stream);
 
