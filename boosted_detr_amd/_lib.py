@@ -203,6 +203,7 @@ SIGNATURES = {
     "bdetr_mask_match": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P]),
     "bdetr_det_match_coco": (I, [P] * 11 + [I] * 7 + [P] * 7),
     "bdetr_mask_match_coco": (I, [P] * 13 + [I] * 8 + [P] * 7),
+    "bdetr_mask_targets": (I, [P, L, P, P, P, P, I, I, I, P, P, P]),
 }
 
 

@@ -1239,6 +1239,104 @@ def mask_match_coco(score, label, det_bits, det_pop, gt_label, gt_bits, gt_pop, 
 
 
 # --------------------------------------------------------------------------------------
+# mask targets from COCO segmentations - csrc/maskraster.hip (K18)
+# --------------------------------------------------------------------------------------
+MASK_KIND_NONE, MASK_KIND_POLY, MASK_KIND_RLE = 0, 1, 2
+MASK_MAX_DIM, MASK_MAX_COORD, MASK_MAX_GRID = 4096, 1 << 23, 32
+
+
+def _flat_ranges(starts, lengths):
+    """Indices of the concatenated ranges [starts[k], starts[k] + lengths[k]) and, per index, the range it belongs to."""
+    owner = np.repeat(np.arange(starts.size), lengths)
+    first = np.cumsum(lengths) - lengths
+    return np.arange(int(lengths.sum())) - np.repeat(first - starts, lengths), owner
+
+
+def check_mask_pack(items, item_off, kind, hw, placement, grid: int):
+    """The host arrays of bdetr_mask_targets against every rule include/bdetr.h states for them (the kernel cannot report): dtypes
+    and shapes raise BdetrError, broken offsets and limits ValueError.  Vectorised over the objects.  Returns (B, M)."""
+    for name, a in (("items", items), ("item_off", item_off), ("kind", kind), ("hw", hw), ("placement", placement)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.int32:
+            raise _lib.BdetrError(f"mask_targets: {name} must be an int32 NumPy array, got {getattr(a, 'dtype', type(a).__name__)}")
+    if kind.ndim != 2 or kind.size == 0:
+        raise _lib.BdetrError(f"mask_targets: kind must be [B,M] with at least one element, got {kind.shape}")
+    B, M = kind.shape
+    if items.ndim != 1 or item_off.shape != (B * M + 1,) or hw.shape != (B, M, 2) or placement.shape != (B, 6):
+        raise _lib.BdetrError("mask_targets: operand shapes disagree (items [T], item_off [B M + 1], kind [B,M], hw [B,M,2], placement [B,6])")
+    if not 1 <= int(grid) <= MASK_MAX_GRID:
+        raise ValueError(f"mask_targets: grid must be in [1, {MASK_MAX_GRID}], got {grid}")
+    off = item_off.astype(np.int64)
+    if off[0] < 0 or (np.diff(off) < 0).any() or off[-1] > items.size:
+        raise ValueError("mask_targets: item_off must be non-decreasing and stay inside the item buffer")
+    if ((kind < 0) | (kind > MASK_KIND_RLE)).any():
+        raise ValueError("mask_targets: kind must be 0 (none), 1 (polygon) or 2 (RLE)")
+    used = kind != MASK_KIND_NONE
+    if used.any() and ((hw[used] < 1) | (hw[used] > MASK_MAX_DIM)).any():
+        raise ValueError(f"mask_targets: source height and width must be in [1, {MASK_MAX_DIM}], got up to {int(hw[used].max())}")
+    p = placement.astype(np.int64)
+    if ((p[:, :2] < 1) | (p[:, :2] > MASK_MAX_DIM)).any() or (p[:, 2:4] < 1).any() or (p[:, 4:] < 0).any() \
+            or (p[:, 4] + p[:, 2] > p[:, 0]).any() or (p[:, 5] + p[:, 3] > p[:, 1]).any():
+        raise ValueError(f"mask_targets: placement (H, W, new_h, new_w, off_h, off_w) needs 1 <= H, W <= {MASK_MAX_DIM}, new >= 1, off >= 0 "
+                         "and off + new <= canvas")
+    flat_kind, size, it = kind.reshape(-1), np.diff(off), items.astype(np.int64)
+
+    def fail(objects, what):
+        raise ValueError(f"mask_targets: object {int(objects[0])}: {what}")
+
+    poly = np.flatnonzero(flat_kind == MASK_KIND_POLY)
+    if poly.size:
+        start, n = off[poly], size[poly]
+        if (n < 2).any():
+            fail(poly[n < 2], "a polygon's items are R, R + 1 ring offsets and the vertices")
+        R = it[start]
+        short = (R < 0) | (2 + R > n)
+        if short.any():
+            fail(poly[short], "a polygon's items are R, R + 1 ring offsets and the vertices")
+        idx, owner = _flat_ranges(start + 1, R + 1)
+        ring = it[idx]
+        down = np.flatnonzero((np.diff(ring) < 0) & (owner[1:] == owner[:-1]))
+        wrong = (ring[np.cumsum(R + 1) - (R + 1)] != 0) | (n != 2 + R + 2 * it[start + 1 + R])
+        if down.size or wrong.any():
+            fail(poly[owner[down]] if down.size else poly[wrong], "ring offsets must start at 0, be non-decreasing and end at the vertex count")
+        idx, owner = _flat_ranges(start + 2 + R, n - 2 - R)
+        far = np.abs(it[idx]) > MASK_MAX_COORD
+        if far.any():
+            fail(poly[owner[far]], "snapped coordinates must stay within +-2^23 (1/256 pixel)")
+    rle = np.flatnonzero(flat_kind == MASK_KIND_RLE)
+    if rle.size:
+        start, n = off[rle], size[rle]
+        what = "one-runs must be (start, length) pairs, ascending, disjoint and inside h * w"
+        if (n % 2).any():
+            fail(rle[n % 2 > 0], what)
+        idx, owner = _flat_ranges(start, n)
+        runs, owner = it[idx].reshape(-1, 2), owner[::2]
+        pixels = hw.reshape(-1, 2).astype(np.int64).prod(axis=1)[rle]
+        end = runs.sum(axis=1)
+        broken = (runs < 0).any(axis=1) | (end > pixels[owner])
+        broken[1:] |= (runs[1:, 0] < end[:-1]) & (owner[1:] == owner[:-1])
+        if broken.any():
+            fail(rle[owner[broken]], what)
+    return B, M
+
+
+def mask_targets(items, item_off, kind, hw, placement, grid: int = 23, device=None):
+    """COCO segmentations -> (masks f32 [B,M,grid,grid], area int32 [B,M]) in HBM (include/bdetr.h, K18).  The operands are the HOST
+    int32 arrays pipeline.pad_annotations(with_masks=True) packs: they are checked here (check_mask_pack) before anything is
+    launched, go to the device in one copy, and nothing is read back."""
+    B, M = check_mask_pack(items, item_off, kind, hw, placement, grid)
+    G = int(grid)
+    parts = [item_off.reshape(-1), kind.reshape(-1), hw.reshape(-1), placement.reshape(-1), items]
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    buf = torch.from_numpy(np.concatenate(parts)).to(dev)
+    d_off, d_kind, d_hw, d_place, d_items = torch.split(buf, [int(a.size) for a in parts])
+    masks = empty(B, M, G, G, like=buf)
+    area = empty(B, M, like=buf, dtype=torch.int32)
+    check(_lib.lib().bdetr_mask_targets(_p(d_items) if items.size else None, int(items.size), _p(d_off), _p(d_kind), _p(d_hw), _p(d_place),
+                                        B, M, G, _p(masks), _p(area), _stream()), "mask_targets")
+    return masks, area
+
+
+# --------------------------------------------------------------------------------------
 # panoptic head pieces (forward) - csrc/panoptic.hip
 # --------------------------------------------------------------------------------------
 def pad4(c: int) -> int:

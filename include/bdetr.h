@@ -775,6 +775,37 @@ int bdetr_mask_match_coco(const float* score, const int32_t* label, const uint64
                           int32_t* order, int32_t* class_rank, uint16_t* tp_bits, uint16_t* ig_bits, int32_t* matched_gt,
                           int32_t* gt_count, void* stream);
 
+/* ------------------------------------------------------------------------
+ * K18  mask targets: COCO segmentations (polygons, RLE) -> the mask head's float grid targets (csrc/maskraster.hip; the host
+ *   side is pipeline.pad_annotations(with_masks=True) / pipeline.mask_targets).  One workgroup per object, o = b M + m.
+ *   Inputs, all int32 in HBM:
+ *       kind      [B,M]     0 = none (padding, or an annotation without a segmentation), 1 = polygon, 2 = RLE
+ *       hw        [B,M,2]   the source image's (h, w) of the object
+ *       item_off  [B M + 1] object o owns items[item_off[o] : item_off[o+1]]
+ *       items     [n_items] polygon: R, then the ring offsets e[0..R] counted in vertices (e[0] = 0, e[R] = V), then V vertices
+ *                           (x, y) snapped to 1/256 pixel (q = rint(256 v), round half to even), 2 + R + 2 V items in all;
+ *                           RLE: (start, length) of every one-run in COCO's column-major pixel order (idx = x h + y), ascending
+ *                           and disjoint (the host's prefix sum of the counts)
+ *       placement [B,6]     (H, W, new_h, new_w, off_h, off_w): the source stretched to new_h x new_w at (off_h, off_w) of an
+ *                           H x W canvas; (1, 1, 1, 1, 0, 0) is "the whole canvas"
+ *   Source mask.  Pixel (x, y) has the centre (256 x + 128, 256 y + 128).  A ring's edge with endpoints lo, hi (lo.y < hi.y) crosses
+ *   the pixel's row when lo.y <= cy < hi.y (horizontal edges never do) and the crossing counts for the pixel when
+ *   (cy - lo.y) (hi.x - lo.x) <= (cx - lo.x) (hi.y - lo.y) in int64; the pixel is inside the ring when the count is odd (even-odd;
+ *   left and top boundaries inclusive, right and bottom exclusive); the mask is the OR over the rings; rings of fewer than 3
+ *   vertices contribute nothing; vertices outside the image are legal.  RLE: the one-runs.
+ *   Outputs: masks float [B,M,G,G], masks[i,j] = (float)((double)N[i,j] / (double)(H h W w)) with the int64 numerator
+ *       N[i,j] = sum over set pixels of OY(y,i) OX(x,j),
+ *       OY(y,i) = max(0, min(PY0 + G new_h, (i+1) H h) - max(PY0, i H h)),  PY0 = G (h off_h + y new_h),  OX likewise
+ *   - the exact share of grid cell (i,j) the placed mask covers; area int32 [B,M] = the source mask's set pixels.  N is summed in
+ *   LDS with 64-bit integer adds (no float atomics): two calls give the same bits.  Objects of kind 0 get zeros and area 0.
+ *   Limits: 1 <= G <= 32, B M <= 2^24, n_items < 2^31: anything else returns -1 (bdetr_last_error) without a launch.  Per object
+ *   1 <= h, w, H, W <= 4096, new >= 1, off >= 0, off + new <= canvas, offsets monotone and inside the buffer, coordinates within
+ *   +-2^23: the kernel cannot report, so an object that breaks one of these gets zeros (coordinates are clamped, runs are clipped
+ *   to the image) and never an out-of-range access; kernels.mask_targets checks all of them on the host before the launch.
+ * ---------------------------------------------------------------------- */
+int bdetr_mask_targets(const int32_t* items, int64_t n_items, const int32_t* item_off, const int32_t* kind, const int32_t* hw,
+                       const int32_t* placement, int B, int M, int G, float* masks, int32_t* area, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
