@@ -204,6 +204,13 @@ SIGNATURES = {
     "bdetr_det_match_coco": (I, [P] * 11 + [I] * 7 + [P] * 7),
     "bdetr_mask_match_coco": (I, [P] * 13 + [I] * 8 + [P] * 7),
     "bdetr_mask_targets": (I, [P, L, P, P, P, P, I, I, I, P, P, P]),
+    # K19-K22 (csrc/maskimage.hip): masks at image resolution, uint64 [Hm, Wm] each.  K19: bilinear upsample of the logits in fp64,
+    # cut at 0, one ballot per word; K20: K18's source mask, stored; K21: popcount intersection [B,N,M], integer adds only;
+    # K22: K17's matching fed from that intersection and per-image pixel counts
+    "bdetr_mask_upsample_bits": (I, [P, P, I, I, I, I, I, P, P, P]),
+    "bdetr_mask_source_bits": (I, [P, L, P, P, P, I, I, I, I, P, P, P]),
+    "bdetr_mask_inter": (I, [P, P, P, I, I, I, I, I, P, P]),
+    "bdetr_mask_match_coco_inter": (I, [P] * 13 + [I] * 7 + [P] * 7),
 }
 
 

@@ -9,10 +9,13 @@ runs COCOeval's ``accumulate`` there in NumPy fp64; ``results`` does so for seve
 ``DetectionEvaluator`` / ``MaskEvaluator`` are the short form: no crowd regions (``iscrowd``), no area ranges (everything is "all"),
 one ``max_dets``.  ``CocoEvaluator`` / ``CocoMaskEvaluator`` are the full protocol (K16 / K17): crowd regions are *ignore*, every
 area range is matched on its own (a ground truth outside the range is *ignore*), and the accumulate runs per (range, max_det) -
-the 12 numbers of pycocotools' ``summarize``.  What remains different from pycocotools: masks (``iouType="segm"``) are compared on
-the panoptic head's own 23 x 23 output grid, prediction logits cut at 0 and [0,1] targets at 0.5 - not upsampled to image
-resolution, not RLE (a mask's area is its share of the grid times the image's H x W); a query's mask shares its box's class and
-score (DETR's convention).
+the 12 numbers of pycocotools' ``summarize``.  ``CocoMaskEvaluator`` compares masks (``iouType="segm"``) on the panoptic head's own
+23 x 23 output grid, prediction logits cut at 0 and [0,1] targets at 0.5 (a mask's area is its share of the grid times the image's
+H x W).  ``CocoImageMaskEvaluator`` (K19-K22) compares them at image resolution instead: logits upsampled to the image and cut at 0,
+ground truths as their exact source bitmasks, areas in pixels.  What remains different from pycocotools there: the polygon
+boundary rule of K18 (boundary pixels can differ from pycocotools' scan conversion; RLE is exact) and an upsample rule that is this
+project's own (bilinear in fp64, reproducible bit for bit; it agrees with torch's interpolate except within rounding of zero).  A
+query's mask shares its box's class and score (DETR's convention).
 """
 from __future__ import annotations
 
@@ -428,6 +431,120 @@ class CocoMaskEvaluator(CocoEvaluator):
         order, class_rank, tp_bits, ig_bits, matched = K.mask_match_coco(
             score, label, det_bits, det_pop, cat_ids.contiguous(), gt_bits, gt_pop, crowd, area, num_objects.reshape(-1).contiguous(), hw,
             self._ranges_dev, self.iou_thresholds, int(mask_logits.shape[2]), self.num_classes, self.max_dets[-1], self._gt_count)
+        self._kept.append((score, label, class_rank, tp_bits, ig_bits, order))
+        self.last_matched_gt = matched
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# masks at image resolution (K19-K22)
+# ---------------------------------------------------------------------------------------------------------------------
+def host_image_hw(height, width) -> np.ndarray:
+    """height / width [B] as HOST arrays or sequences (what pad_annotations(with_eval_fields=True) gives) -> int32 [B,2].  Device
+    tensors are refused: the buffer sizes of the image-resolution path come from these values, and reading them back would be a
+    host synchronisation per batch."""
+    if height is None or width is None:
+        raise ValueError("image-resolution masks need the batch's 'height' and 'width' (pad_annotations(with_eval_fields=True))")
+    parts = []
+    for name, v in (("height", height), ("width", width)):
+        if hasattr(v, "is_cuda"):                                # a torch tensor
+            if v.is_cuda:
+                raise ValueError(f"image-resolution masks need '{name}' as a host array or sequence, not a device tensor: the buffer "
+                                 "sizes come from it and nothing is read back per batch")
+            v = v.numpy()
+        a = np.asarray(v)
+        if a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"image-resolution masks need '{name}' as integers [B], got {a.dtype} {a.shape}")
+        parts.append(a.reshape(-1).astype(np.int64))
+    if parts[0].size != parts[1].size:
+        raise ValueError("'height' and 'width' must have one entry per image each")
+    return np.stack(parts, axis=1).astype(np.int32)
+
+
+class CocoImageMaskEvaluator(CocoEvaluator):
+    """Running mask AP (iouType="segm") by the full COCO protocol AT IMAGE RESOLUTION, as a COCO user compares it: every query's
+    logits are upsampled to its image's height x width and cut at 0 (bdetr_mask_upsample_bits, K19 - DETR's own segmentation
+    post-processing), every ground truth is its exact source bitmask (bdetr_mask_source_bits, K20: polygons by K18's rule, RLE
+    exactly), the two are intersected by popcount (bdetr_mask_inter, K21) and matched by COCOeval's rule
+    (bdetr_mask_match_coco_inter, K22).  A mask's area is its pixel count.  What it keeps, and ``result``, are CocoEvaluator's; it
+    reads nothing back per batch.
+
+    max_mask_bytes: the budget for the two bitmask buffers of ONE batch, 8 Hm Wm B (N + M) bytes with Hm = max height and
+    Wm = ceil(max width / 64); a batch over it is refused with a ValueError before anything is launched, and the evaluator stays
+    usable.  The default is 1 GiB: sixteen 480 x 640 images with 100 queries and 100 ground-truth rows need 117 MiB, two
+    1333 x 800 images 53 MiB."""
+
+    DEFAULT_MAX_MASK_BYTES = 1 << 30
+
+    def __init__(self, num_classes: int, iou_thresholds=None, max_dets=(1, 10, 100), area_ranges=None, max_mask_bytes: Optional[int] = None):
+        super().__init__(num_classes, iou_thresholds, max_dets, area_ranges)
+        self.max_mask_bytes = self.DEFAULT_MAX_MASK_BYTES if max_mask_bytes is None else int(max_mask_bytes)
+        if self.max_mask_bytes < 1:
+            raise ValueError("max_mask_bytes must be positive")
+
+    def check_batch(self, segments, image_hw_host, N: int):
+        """Every refusal of update() that needs no device: the segments pack, the images' sizes, that every segmented object was
+        annotated on its image's own (height, width), and the byte budget.  Returns (image_hw int32 [B,2], Hm, Wm)."""
+        from . import kernels as K
+        if not isinstance(segments, dict) or any(k not in segments for k in ("items", "item_off", "kind", "hw")):
+            raise ValueError("image-resolution masks need the batch's 'segments': the host pack of pipeline.pad_annotations(..., "
+                             "with_masks=True) (items, item_off, kind, hw); dense 'masks' are grid data")
+        if hasattr(image_hw_host, "is_cuda"):
+            if image_hw_host.is_cuda:
+                raise ValueError("image_hw_host must be a host array [B,2], not a device tensor: the buffer sizes come from it")
+            image_hw_host = image_hw_host.numpy()
+        hw = np.asarray(image_hw_host)
+        kind, seg_hw = segments["kind"], segments["hw"]
+        if not isinstance(kind, np.ndarray) or kind.ndim != 2 or not isinstance(seg_hw, np.ndarray) or seg_hw.shape != kind.shape + (2,):
+            raise ValueError("segments: kind must be a NumPy array [B,M] and hw [B,M,2]")
+        B, M = kind.shape
+        if hw.shape != (B, 2) or not np.issubdtype(hw.dtype, np.integer):
+            raise ValueError(f"image_hw_host must be integers [B={B},2] (height, width), got {hw.dtype} {hw.shape}")
+        hw = hw.astype(np.int32)
+        Hm, Wm = K.mask_layout(hw)
+        used = kind != K.MASK_KIND_NONE
+        wrong = used & (seg_hw != hw[:, None, :]).any(axis=2)
+        if wrong.any():
+            b, m = (int(v[0]) for v in np.nonzero(wrong))
+            raise ValueError(f"segments: object {m} of image {b} was annotated on a {tuple(int(v) for v in seg_hw[b, m])} image, the batch "
+                             f"says (height, width) = {tuple(int(v) for v in hw[b])}")
+        need = 8 * Hm * Wm * B * (int(N) + M)
+        if need > self.max_mask_bytes:
+            raise ValueError(f"the bitmask buffers of this batch need {need} bytes (8 Hm Wm B (N + M) with Hm={Hm}, Wm={Wm}, B={B}, N={N}, "
+                             f"M={M}); max_mask_bytes is {self.max_mask_bytes}")
+        return hw, Hm, Wm
+
+    def update(self, cat_pred, mask_logits, cat_ids, segments, num_objects, image_hw_host, iscrowd=None, area=None) -> None:
+        """cat_pred [B,N,C] and mask_logits f32 [B,N,G,G] (or [B,N,G*G]) in HBM as for CocoMaskEvaluator.update; cat_ids int32 [B,M];
+        segments: the HOST pack of pad_annotations(with_masks=True), row m belonging to cat_ids row m; num_objects int32 [B];
+        image_hw_host: HOST integers [B,2], every image's (height, width) - the size its segmentations were annotated on; iscrowd /
+        area as CocoEvaluator.update takes them (area None: the mask's pixel count).  Every refusal comes before the first launch."""
+        import torch
+        from . import kernels as K
+        if cat_pred.shape[-1] != self.num_classes:
+            raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {self.num_classes}")
+        if cat_pred.dim() != 3 or mask_logits.dim() not in (3, 4) or cat_ids.dim() != 2:
+            raise ValueError("expected cat_pred [B,N,C], mask_logits [B,N,G,G], cat_ids [B,M]")
+        B, N = cat_pred.shape[:2]
+        M = cat_ids.shape[1]
+        G = int(round(float(mask_logits.shape[2]) ** 0.5)) if mask_logits.dim() == 3 else int(mask_logits.shape[2])
+        if tuple(mask_logits.shape[:2]) != (B, N) or mask_logits[0, 0].numel() != G * G:
+            raise ValueError(f"mask_logits {tuple(mask_logits.shape)} do not fit cat_pred [B={B},N={N},C] with a square grid")
+        hw, Hm, Wm = self.check_batch(segments, image_hw_host, N)
+        if segments["kind"].shape != (B, M):
+            raise ValueError(f"segments: kind is {segments['kind'].shape}, cat_ids [B={B},M={M}]")
+        device = cat_pred.device
+        # the ground truths first: mask_source_bits checks the whole pack on the host before it launches
+        gt_bits, gt_pop = K.mask_source_bits(segments["items"], segments["item_off"], segments["kind"], segments["hw"], Hm, Wm, device=device)
+        flat = torch.from_numpy(np.concatenate([hw.reshape(-1), hw[:, 0] * hw[:, 1]]).astype(np.int32)).to(device)      # one copy
+        hw_dev, pix = flat[:2 * B].view(B, 2), flat[2 * B:]
+        crowd, area, hw_dev = self._coco_operands(device, B, M, iscrowd, area, hw_dev)
+        num_objects = num_objects.reshape(-1).contiguous()
+        score, label = K.det_postprocess(cat_pred.contiguous())
+        det_bits, det_pop = K.mask_upsample_bits(mask_logits.reshape(B, N, G, G).contiguous(), hw_dev, Hm, Wm)
+        inter = K.mask_inter(det_bits, gt_bits, num_objects)
+        order, class_rank, tp_bits, ig_bits, matched = K.mask_match_coco_inter(
+            score, label, inter, det_pop, cat_ids.contiguous(), gt_pop, crowd, area, num_objects, hw_dev, pix, self._ranges_dev,
+            self.iou_thresholds, self.num_classes, self.max_dets[-1], self._gt_count)
         self._kept.append((score, label, class_rank, tp_bits, ig_bits, order))
         self.last_matched_gt = matched
 

@@ -1337,6 +1337,143 @@ def mask_targets(items, item_off, kind, hw, placement, grid: int = 23, device=No
 
 
 # --------------------------------------------------------------------------------------
+# masks at image resolution - csrc/maskimage.hip (K19-K22)
+# --------------------------------------------------------------------------------------
+MASK_MAX_WORDS_PER_ROW = MASK_MAX_DIM // 64
+
+
+def mask_layout(image_hw):
+    """(Hm, Wm) of the batch layout K19-K22 share, from the HOST int array image_hw [B,2]: Hm = max height, Wm = ceil(max width / 64).
+    Heights and widths outside [1, 4096] are a ValueError."""
+    hw = np.asarray(image_hw)
+    if hw.ndim != 2 or hw.shape[1] != 2 or hw.shape[0] < 1 or not np.issubdtype(hw.dtype, np.integer):
+        raise _lib.BdetrError(f"mask_layout: image_hw must be a host integer array [B,2], got {getattr(hw, 'dtype', None)} {hw.shape}")
+    if int(hw.min()) < 1 or int(hw.max()) > MASK_MAX_DIM:
+        raise ValueError(f"mask_layout: image heights and widths must be in [1, {MASK_MAX_DIM}], got {int(hw.min())} .. {int(hw.max())}")
+    return int(hw[:, 0].max()), (int(hw[:, 1].max()) + 63) // 64
+
+
+def _check_layout(what: str, Hm: int, Wm: int):
+    if not (1 <= int(Hm) <= MASK_MAX_DIM and 1 <= int(Wm) <= MASK_MAX_WORDS_PER_ROW):
+        raise ValueError(f"{what}: the mask layout needs 1 <= Hm <= {MASK_MAX_DIM} and 1 <= Wm <= {MASK_MAX_WORDS_PER_ROW}, got Hm={Hm} Wm={Wm}")
+    return int(Hm), int(Wm)
+
+
+def mask_upsample_bits(logits, image_hw, Hm: int, Wm: int, out=None):
+    """logits f32 [B,N,G,G], image_hw int32 [B,2] in HBM -> (bits int64 [B,N,Hm,Wm], pop int32 [B,N]) (include/bdetr.h, K19): every
+    query's logits brought to its image's h_b x w_b by the fp64 bilinear rule stated there and cut at 0, packed 64 pixels of a row
+    to a word.  Bits at x >= w_b and rows y >= h_b are written as zero.  out: a bits buffer to write into."""
+    _dtypes("mask_upsample_bits", logits=(logits, torch.float32), image_hw=(image_hw, torch.int32))
+    if logits.dim() != 4 or logits.shape[2] != logits.shape[3] or logits.numel() == 0:
+        raise _lib.BdetrError(f"mask_upsample_bits: logits must be [B,N,G,G] with at least one element, got {tuple(logits.shape)}")
+    B, N, G, _ = logits.shape
+    if tuple(image_hw.shape) != (B, 2):
+        raise _lib.BdetrError("mask_upsample_bits: operand shapes disagree (logits [B,N,G,G], image_hw [B,2])")
+    if not 1 <= G <= MASK_MAX_GRID:
+        raise ValueError(f"mask_upsample_bits: G must be in [1, {MASK_MAX_GRID}], got {G}")
+    Hm, Wm = _check_layout("mask_upsample_bits", Hm, Wm)
+    _chk(logits)
+    _chk(image_hw, dtype=torch.int32)
+    if out is None:
+        out = empty(B, N, Hm, Wm, like=logits, dtype=torch.int64)
+    else:
+        _dtypes("mask_upsample_bits", out=(out, torch.int64))
+        if tuple(out.shape) != (B, N, Hm, Wm):
+            raise _lib.BdetrError("mask_upsample_bits: out must be [B,N,Hm,Wm]")
+        _chk(out, dtype=torch.int64)
+    pop = empty(B, N, like=logits, dtype=torch.int32)
+    check(_lib.lib().bdetr_mask_upsample_bits(_p(logits), _p(image_hw), B, N, G, Hm, Wm, _p(out), _p(pop), _stream()), "mask_upsample_bits")
+    return out, pop
+
+
+def check_source_pack(items, item_off, kind, hw, Hm: int, Wm: int):
+    """check_mask_pack for K20: the same rules for the host arrays (no placement), and every segmented object must fit the layout
+    (h <= Hm, ceil(w / 64) <= Wm).  Returns (B, M)."""
+    if not isinstance(kind, np.ndarray) or kind.ndim != 2:
+        raise _lib.BdetrError(f"mask_source_bits: kind must be an int32 NumPy array [B,M], got {getattr(kind, 'shape', type(kind).__name__)}")
+    B, M = check_mask_pack(items, item_off, kind, hw, np.tile(np.asarray([[1, 1, 1, 1, 0, 0]], np.int32), (kind.shape[0], 1)), 1)
+    Hm, Wm = _check_layout("mask_source_bits", Hm, Wm)
+    used = kind != MASK_KIND_NONE
+    if used.any() and ((hw[..., 0][used] > Hm).any() or (hw[..., 1][used] > 64 * Wm).any()):
+        raise ValueError(f"mask_source_bits: a segmented object's (h, w) does not fit the layout Hm={Hm}, Wm={Wm}")
+    return B, M
+
+
+def mask_source_bits(items, item_off, kind, hw, Hm: int, Wm: int, device=None, out=None):
+    """The segments pack of pipeline.pad_annotations(with_masks=True) -> (bits int64 [B,M,Hm,Wm], pop int32 [B,M]) in HBM
+    (include/bdetr.h, K20): every object's exact source mask by K18's rule, in the layout of mask_upsample_bits; pop is
+    mask_targets' area.  The operands are HOST int32 arrays, checked here before anything is launched; one copy to the device,
+    nothing read back.  out: a bits buffer to write into."""
+    B, M = check_source_pack(items, item_off, kind, hw, Hm, Wm)
+    Hm, Wm = int(Hm), int(Wm)
+    parts = [item_off.reshape(-1), kind.reshape(-1), hw.reshape(-1), items]
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    buf = torch.from_numpy(np.concatenate(parts)).to(dev)
+    d_off, d_kind, d_hw, d_items = torch.split(buf, [int(a.size) for a in parts])
+    if out is None:
+        out = empty(B, M, Hm, Wm, like=buf, dtype=torch.int64)
+    else:
+        _dtypes("mask_source_bits", out=(out, torch.int64))
+        if tuple(out.shape) != (B, M, Hm, Wm):
+            raise _lib.BdetrError("mask_source_bits: out must be [B,M,Hm,Wm]")
+        _chk(out, dtype=torch.int64)
+    pop = empty(B, M, like=buf, dtype=torch.int32)
+    check(_lib.lib().bdetr_mask_source_bits(_p(d_items) if items.size else None, int(items.size), _p(d_off), _p(d_kind), _p(d_hw), B, M, Hm, Wm,
+                                            _p(out), _p(pop), _stream()), "mask_source_bits")
+    return out, pop
+
+
+def mask_inter(det_bits, gt_bits, num_objects):
+    """det_bits int64 [B,N,Hm,Wm], gt_bits int64 [B,M,Hm,Wm], num_objects int32 [B] -> inter int32 [B,N,M] (include/bdetr.h, K21):
+    the set bits two masks share, for the ground-truth rows m < num_objects[b]; 0 for the others.  Integer adds only."""
+    _dtypes("mask_inter", det_bits=(det_bits, torch.int64), gt_bits=(gt_bits, torch.int64), num_objects=(num_objects, torch.int32))
+    if det_bits.dim() != 4 or gt_bits.dim() != 4 or det_bits.numel() == 0 or gt_bits.numel() == 0:
+        raise _lib.BdetrError("mask_inter: operand shapes disagree (det_bits [B,N,Hm,Wm], gt_bits [B,M,Hm,Wm])")
+    B, N, Hm, Wm = det_bits.shape
+    M = gt_bits.shape[1]
+    if tuple(gt_bits.shape) != (B, M, Hm, Wm) or num_objects.numel() != B:
+        raise _lib.BdetrError("mask_inter: operand shapes disagree (det_bits [B,N,Hm,Wm], gt_bits [B,M,Hm,Wm], num_objects [B])")
+    _check_layout("mask_inter", Hm, Wm)
+    _chk(det_bits, gt_bits, dtype=torch.int64)
+    _chk(num_objects, dtype=torch.int32)
+    inter = empty(B, N, M, like=det_bits, dtype=torch.int32)
+    check(_lib.lib().bdetr_mask_inter(_p(det_bits), _p(gt_bits), _p(num_objects), B, N, M, Hm, Wm, _p(inter), _stream()), "mask_inter")
+    return inter
+
+
+def mask_match_coco_inter(score, label, inter, det_pop, gt_label, gt_pop, gt_crowd, gt_area, num_objects, image_hw, pix, area_ranges,
+                          thresholds, num_classes: int, max_dets: int, gt_count):
+    """mask_match_coco fed from an intersection instead of the bits (include/bdetr.h, K22): inter int32 [B,N,M] as mask_inter
+    returns it, det_pop int32 [B,N] / gt_pop int32 [B,M] the masks' set bits, pix int32 [B] the pixels a mask of image b has.
+    Everything else, and what is returned, as mask_match_coco."""
+    _dtypes("mask_match_coco_inter", score=(score, torch.float32), label=(label, torch.int32), inter=(inter, torch.int32),
+            det_pop=(det_pop, torch.int32), gt_label=(gt_label, torch.int32), gt_pop=(gt_pop, torch.int32), num_objects=(num_objects, torch.int32),
+            pix=(pix, torch.int32))
+    if score.dim() != 2 or gt_label.dim() != 2:
+        raise _lib.BdetrError("mask_match_coco_inter: operand shapes disagree (score [B,N], gt_label [B,M], inter [B,N,M])")
+    B, N = score.shape
+    M = gt_label.shape[1]
+    if tuple(label.shape) != (B, N) or tuple(inter.shape) != (B, N, M) or tuple(det_pop.shape) != (B, N) or tuple(gt_pop.shape) != (B, M) \
+            or num_objects.numel() != B or pix.numel() != B:
+        raise _lib.BdetrError("mask_match_coco_inter: operand shapes disagree (score [B,N], gt_label [B,M], inter [B,N,M], pix [B])")
+    A = _coco_operands("mask_match_coco_inter", B, M, gt_crowd, gt_area, image_hw, area_ranges, gt_count, int(num_classes))
+    _chk(score)
+    _chk(label, inter, det_pop, gt_label, gt_pop, num_objects, pix, dtype=torch.int32)
+    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
+    T = int(thr.size)
+    order = empty(B, N, like=score, dtype=torch.int32)
+    class_rank = empty(B, N, like=score, dtype=torch.int32)
+    tp_bits = empty(max(A, 1), B, N, like=score, dtype=torch.int16)
+    ig_bits = empty(max(A, 1), B, N, like=score, dtype=torch.int16)
+    matched = empty(max(A, 1), B, max(T, 1), N, like=score, dtype=torch.int32)
+    check(_lib.lib().bdetr_mask_match_coco_inter(_p(score), _p(label), _p(inter), _p(det_pop), _p(gt_label), _p(gt_pop), _p(gt_crowd), _p(gt_area),
+                                                 _p(num_objects), _p(image_hw), _p(pix), _p(area_ranges), thr.ctypes.data, B, N, M,
+                                                 int(num_classes), T, A, int(max_dets), _p(order), _p(class_rank), _p(tp_bits), _p(ig_bits),
+                                                 _p(matched), _p(gt_count), _stream()), "mask_match_coco_inter")
+    return order, class_rank, tp_bits, ig_bits, matched
+
+
+# --------------------------------------------------------------------------------------
 # panoptic head pieces (forward) - csrc/panoptic.hip
 # --------------------------------------------------------------------------------------
 def pad4(c: int) -> int:

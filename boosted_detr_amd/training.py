@@ -647,20 +647,22 @@ class DetectionAP(Callback):
     test_step trains (the reference's quirk), this leaves the model as it found it.  Put it before the callbacks that write the logs.
     iou_types / mask_evaluator: as Model.evaluate's; with "segm" the logs gain val_mask_AP, val_mask_AP50, val_mask_AP75, val_mask_AR.
     coco=True: Model.evaluate(coco=True); the logs gain val_AP_small ... val_AR_large (every number of the COCO summary) and, with
-    "segm", the val_mask_ counterparts."""
+    "segm", the val_mask_ counterparts.  mask_resolution: Model.evaluate's ("image" needs coco=True)."""
 
     def __init__(self, validation_data, every: int = 1, steps: Optional[int] = None, evaluator=None, iou_types=("bbox",), mask_evaluator=None,
-                 coco: bool = False):
+                 coco: bool = False, mask_resolution: str = "grid"):
         self.validation_data, self.every, self.steps, self.evaluator = validation_data, max(1, int(every)), steps, evaluator
         self.iou_types, self.mask_evaluator, self.coco = Model._check_iou_types(iou_types), mask_evaluator, bool(coco)
+        self.mask_resolution = Model._check_mask_resolution(mask_resolution, self.coco)
         self.history: List[dict] = []
 
     def on_epoch_end(self, epoch, logs=None):
         if (epoch + 1) % self.every:
             return
         if self.coco:
+            extra = {} if self.mask_resolution == "grid" else {"mask_resolution": self.mask_resolution}
             res = self.model.evaluate(self.validation_data, steps=self.steps, evaluator=self.evaluator, iou_types=self.iou_types,
-                                      mask_evaluator=self.mask_evaluator, coco=True)
+                                      mask_evaluator=self.mask_evaluator, coco=True, **extra)
             prefixes = [p for p, t in (("", "bbox"), ("mask_", "segm")) if t in self.iou_types]
             vals = {f"val_{k}": float(res[k]) for p in prefixes for k in res
                     if k.startswith(p) and (k[len(p):] in ("AP", "AP50", "AP75", "AR") or k[len(p):].startswith(("AP_", "AR_")))}
@@ -1251,26 +1253,63 @@ class Model(Layer):
             raise ValueError(f"iou_types must name one or both of {cls.IOU_TYPES}, got {iou_types!r}")
         return tuple(t for t in cls.IOU_TYPES if t in types)
 
+    MASK_RESOLUTIONS = ("grid", "image")
+
+    @classmethod
+    def _check_mask_resolution(cls, mask_resolution, coco: bool) -> str:
+        if mask_resolution not in cls.MASK_RESOLUTIONS:
+            raise ValueError(f"mask_resolution must be one of {cls.MASK_RESOLUTIONS}, got {mask_resolution!r}")
+        if mask_resolution == "image" and not coco:
+            raise ValueError('mask_resolution="image" needs coco=True: the short protocol scores masks on the grid only')
+        return mask_resolution
+
+    @staticmethod
+    def _image_mask_fields(batch: dict):
+        """(segments, image_hw int32 [B,2] on the HOST) of a batch for the image-resolution path; a ValueError says what is missing."""
+        from . import evaluation
+        segments = batch.get("segments")
+        if segments is None:
+            raise ValueError('mask_resolution="image" needs every batch\'s \'segments\', the host pack of pipeline.pad_annotations(..., '
+                             "with_masks=True); dense 'masks' are grid data and are not enough")
+        return segments, evaluation.host_image_hw(batch.get("height"), batch.get("width"))
+
     def _require_panoptic_head(self) -> None:
         """Raises unless the model can produce masks (DETR with a panoptic head overrides this)."""
         raise RuntimeError(f"{type(self).__name__} has no mask head: iou_types with 'segm' and segmentations() need a DETR built with "
                            "with_panoptic_head=True or train_panoptic_head=True")
 
-    def segmentations(self, inputs: dict) -> Dict[str, torch.Tensor]:
+    def segmentations(self, inputs: dict, resolution: str = "grid") -> Dict[str, torch.Tensor]:
         """detections(inputs) plus every query's mask, in HBM: mask_logits f32 [B,N,23,23] from the panoptic head and masks int64
         [B,N,W], the logits cut at 0 (sigmoid > 0.5) and packed 64 pixels to a word, row-major (bit p mod 64 of word p div 64;
-        W = ceil(529/64) = 9).  Afterwards panoptic_masks() answers for this call."""
+        W = ceil(529/64) = 9).  Afterwards panoptic_masks() answers for this call.
+        resolution="image": also image_masks int64 [B,N,Hm,Wm], the logits upsampled to each image's own height x width and cut at 0
+        (include/bdetr.h, K19: Hm = max height, Wm = ceil(max width / 64), pixel (x, y) is bit x mod 64 of word [y, x div 64], zero
+        outside the image), image_mask_area int32 [B,N], their pixel counts, and image_hw int32 [B,2].  It needs inputs["height"] and
+        inputs["width"] as host arrays or sequences."""
         from .panoptic_neck import MASK_GRID
+        if resolution not in self.MASK_RESOLUTIONS:
+            raise ValueError(f"resolution must be one of {self.MASK_RESOLUTIONS}, got {resolution!r}")
         self._require_panoptic_head()
+        if resolution == "image":
+            from . import evaluation
+            hw = evaluation.host_image_hw(inputs.get("height"), inputs.get("width"))
+            Hm, Wm = K.mask_layout(hw)
         out = self.detections(inputs)
         logits = self.panoptic_masks()
         B, N = logits.shape[:2]
         bits, _ = K.mask_binarize(logits.contiguous(), 0.0)
         out.update(mask_logits=logits.reshape(B, N, MASK_GRID, MASK_GRID), masks=bits)
+        if resolution == "image":
+            if hw.shape[0] != B:
+                raise ValueError(f"'height' / 'width' have {hw.shape[0]} entries, the batch has {B} images")
+            from .engine import to_device
+            hw_dev = to_device(hw, torch.int32)
+            image_bits, image_area = K.mask_upsample_bits(out["mask_logits"].contiguous(), hw_dev, Hm, Wm)
+            out.update(image_masks=image_bits, image_mask_area=image_area, image_hw=hw_dev)
         return out
 
     def evaluate(self, x: Iterable[dict], steps: Optional[int] = None, evaluator=None, return_dict: bool = True, verbose: int = 0,
-                 iou_types=("bbox",), mask_evaluator=None, coco: bool = False):
+                 iou_types=("bbox",), mask_evaluator=None, coco: bool = False, mask_resolution: str = "grid"):
         """COCO-style AP over the batches of `x` (dicts as for training: strings or pre-tokenised ids).  Per batch: an inference-mode
         forward pass and the two kernels of csrc/detmetric.hip, nothing read back; one device-to-host copy at the end (evaluation.py).
         Changes nothing: weights, moving statistics, optimizer slots and counters, the step seed, captured steps and what
@@ -1287,13 +1326,22 @@ class Model(Layer):
         ignored rather than matched), area [B,M] in pixels of the original image, height / width [B] the original size; missing keys
         mean no crowd, the area of the box (or mask) and the model's image_size.  The dict gains AP_small, AP_medium, AP_large, AR_1,
         AR_10, AR_100, AR_small, AR_medium, AR_large and stats, the 12 numbers in pycocotools' summarize order (with "segm" the
-        mask_ counterparts and mask_stats); return_dict=False returns stats, followed by mask_stats."""
+        mask_ counterparts and mask_stats); return_dict=False returns stats, followed by mask_stats.
+        mask_resolution: "grid" (the default: everything above) or "image", with coco=True only: "segm" is scored at image resolution,
+        as a COCO user compares it - every query's logits upsampled to its image's height x width and cut at 0, every ground truth
+        its exact source bitmask, areas in pixels (evaluation.CocoImageMaskEvaluator; csrc/maskimage.hip, K19-K22).  Every batch
+        then needs 'segments' (pipeline.pad_annotations(with_masks=True); 'masks' are not read) and 'height' / 'width' as HOST arrays
+        (with_eval_fields=True), each segmentation annotated on that size; a batch that lacks them, or whose bitmasks would exceed
+        the evaluator's max_mask_bytes, is a ValueError before anything is launched for it.  Same keys in the result, still one
+        device-to-host copy.  mask_evaluator: then a CocoImageMaskEvaluator."""
         from . import evaluation
         from .model import _prepare_masks, _prepare_targets
         types = self._check_iou_types(iou_types)
         coco = bool(coco) or isinstance(evaluator, evaluation.CocoEvaluator) or isinstance(mask_evaluator, evaluation.CocoEvaluator)
+        self._check_mask_resolution(mask_resolution, coco)
         if coco:
-            return self._evaluate_coco(x, steps, evaluator, return_dict, verbose, types, mask_evaluator)
+            image_masks = mask_resolution == "image" or isinstance(mask_evaluator, evaluation.CocoImageMaskEvaluator)      # its class selects the path
+            return self._evaluate_coco(x, steps, evaluator, return_dict, verbose, types, mask_evaluator, image_masks)
         box_ev = mask_ev = None
         if "bbox" in types:
             box_ev = evaluator if evaluator is not None else evaluation.DetectionEvaluator(self.num_categories)
@@ -1347,8 +1395,8 @@ class Model(Layer):
             hw = tuple(int(v) for v in self.image_size[:2])
         return iscrowd, area, hw
 
-    def _evaluate_coco(self, x, steps, evaluator, return_dict, verbose, types, mask_evaluator):
-        """evaluate(coco=True): the same loop over CocoEvaluator / CocoMaskEvaluator."""
+    def _evaluate_coco(self, x, steps, evaluator, return_dict, verbose, types, mask_evaluator, image_masks: bool = False):
+        """evaluate(coco=True): the same loop over CocoEvaluator / CocoMaskEvaluator (image_masks: CocoImageMaskEvaluator)."""
         from . import evaluation
         from .model import _prepare_masks, _prepare_targets
         box_ev = mask_ev = None
@@ -1359,23 +1407,30 @@ class Model(Layer):
             box_ev.reset()
         if "segm" in types:
             self._require_panoptic_head()
-            mask_ev = mask_evaluator if mask_evaluator is not None else evaluation.CocoMaskEvaluator(self.num_categories)
-            if not isinstance(mask_ev, evaluation.CocoMaskEvaluator):
-                raise ValueError("coco=True needs a CocoMaskEvaluator as mask_evaluator")
+            mask_class = evaluation.CocoImageMaskEvaluator if image_masks else evaluation.CocoMaskEvaluator
+            mask_ev = mask_evaluator if mask_evaluator is not None else mask_class(self.num_categories)
+            if not isinstance(mask_ev, mask_class):
+                raise ValueError(f"coco=True needs a {mask_class.__name__} as mask_evaluator" + (' with mask_resolution="image"' if image_masks else ""))
             mask_ev.reset()
+        image_masks = image_masks and mask_ev is not None
         keep_panoptic = self._panoptic_inputs
         t0, n = time.time(), 0
         try:
             for step, batch in enumerate(x):
                 if steps is not None and step >= steps:
                     break
+                if image_masks:                               # every refusal of this batch before anything is launched for it
+                    segments, hw_host = self._image_mask_fields(batch)
+                    mask_ev.check_batch(segments, hw_host, self.num_object_preds)
                 cat_ids, _, bbox, num_objects = _prepare_targets(self, batch)
-                masks = _prepare_masks(batch, bbox.shape[0], bbox.shape[1]) if mask_ev is not None else None
+                masks = _prepare_masks(batch, bbox.shape[0], bbox.shape[1]) if mask_ev is not None and not image_masks else None
                 iscrowd, area, hw = self._coco_fields(batch, bbox.shape[0], bbox.shape[1])
                 cat_preds, _, box_preds = self.predict_raw(batch)
                 if box_ev is not None:
                     box_ev.update(cat_preds, box_preds, cat_ids, bbox, num_objects, iscrowd, area, hw)
-                if mask_ev is not None:
+                if image_masks:
+                    mask_ev.update(cat_preds, self.panoptic_masks(), cat_ids, segments, num_objects, hw_host, iscrowd, area)
+                elif mask_ev is not None:
                     mask_ev.update(cat_preds, self.panoptic_masks(), cat_ids, masks, num_objects, iscrowd, area, hw)
                 n += 1
         finally:

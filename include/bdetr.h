@@ -806,6 +806,64 @@ int bdetr_mask_match_coco(const float* score, const int32_t* label, const uint64
 int bdetr_mask_targets(const int32_t* items, int64_t n_items, const int32_t* item_off, const int32_t* kind, const int32_t* hw,
                        const int32_t* placement, int B, int M, int G, float* masks, int32_t* area, void* stream);
 
+/* ------------------------------------------------------------------------
+ * K19-K22  mask AP at image resolution (csrc/maskimage.hip; evaluation.CocoImageMaskEvaluator chains them, once per batch, and
+ *   reads nothing back).  Additions to ABI 8: nothing that existed changed.
+ *   Layout shared by all four.  For a batch Hm = max height, Wm = ceil(max width / 64).  A mask is uint64 [Hm, Wm], row-major at
+ *   image resolution: pixel (x, y) of image b is bit (x mod 64) of word [y, x div 64]; the bits at x >= w_b and all words of the
+ *   rows y >= h_b are zero.  K19 and K20 WRITE those zeros; no caller's memset is relied on.  1 <= Hm <= 4096, 1 <= Wm <= 64.
+ *
+ * K19  bdetr_mask_upsample_bits: logits float [B,N,G,G], image_hw int32 [B,2] (h_b, w_b; clamped to [0, Hm] x [0, 64 Wm])
+ *   -> bits [B,N,Hm,Wm], pop int32 [B,N] (the set bits: an integer sum).  Bilinear with half-pixel centres, as
+ *   torch.nn.functional.interpolate(mode="bilinear", align_corners=False) away from zero, but stated so that it can be reproduced
+ *   bit for bit.  Along an axis with n target pixels, for the target pixel p:
+ *       num = (2 p + 1) G - n;  D = 2 n;  i0 = floor(num / D) (floor division: -1 for a negative num);  r = num - i0 D;
+ *       ia = max(i0, 0);  ib = min(i0 + 1, G - 1);  t = (double)r / (double)D
+ *   and the value, in fp64 with every operation rounded on its own (no FMA: the file is compiled with -ffp-contract=off):
+ *       top = (1 - tx) L[ia_y, ia_x] + tx L[ia_y, ib_x];  bot = the same on row ib_y;  v = (1 - ty) top + ty bot
+ *   The bit is set when v > 0 (NaN: not set; an infinite logit next to a zero weight gives NaN, by IEEE).  One wave ballot of the
+ *   predicate over 64 consecutive x is the output word.  At h = w = G the rule returns finite logits exactly.
+ *   Limits: B N <= 2^24, 1 <= G <= 32; anything else returns -1 (bdetr_last_error) without a launch.
+ *
+ * K20  bdetr_mask_source_bits: K18's segments pack (items, item_off, kind, hw - see K18) -> bits [B,M,Hm,Wm], pop int32 [B,M].
+ *   The mask is K18's SOURCE MASK by the rule stated there (vertices snapped to 1/256 pixel, even-odd fill sampled at pixel
+ *   centres, rings ORed, RLE one-runs exact); nothing is placed and no coverage is computed.  pop = the set bits = K18's area.
+ *   Objects of kind 0 get zeros and pop 0.  Limits: K18's (B M <= 2^24, n_items < 2^31), else -1 without a launch; per object
+ *   K18's rules plus h <= Hm and ceil(w / 64) <= Wm: the kernel cannot report, so an object that breaks one of them gets zeros
+ *   (coordinates are clamped, runs are clipped to the image) and never an out-of-range access.
+ *
+ * K21  bdetr_mask_inter: det_bits [B,N,Hm,Wm], gt_bits [B,M,Hm,Wm], num_objects int32 [B] -> inter int32 [B,N,M]:
+ *       inter[b,n,m] = sum over the Hm Wm words of popcount(d[w] & g[w]) for m < min(max(num_objects[b], 0), M), else 0.
+ *   The entry zeroes inter itself and the waves add into it with integer atomics only: two calls give the same bits.  A
+ *   workgroup keeps 8 detections x 8 ground truths of counters in registers while its share of the words streams past (16-byte
+ *   loads when Hm Wm is even and both bases are 16-byte aligned, else 8-byte loads); tiles at or past num_objects leave at once.
+ *   Limits: B <= 65535, N, M <= 1024.
+ *
+ * K22  bdetr_mask_match_coco_inter: K17's rule, operation for operation, with the IoU source replaced.  In place of det_bits /
+ *   gt_bits and the scalar P it takes inter int32 [B,N,M] (K21), det_pop / gt_pop (K19 / K20) and pix int32 [B], the number of
+ *   pixels a mask of image b has (image mode: h_b w_b; >= 1):
+ *       IoU        : union = det_pop + gt_pop - inter, in integers; iou = union > 0 ? (double)inter / (double)union : 0
+ *       crowd IoU  : (double)inter / (double)det_pop, 0 when that is 0
+ *       areas      : (double)pop * scale_b / (double)pix[b], scale_b = (double)H_b (double)W_b from image_hw; ground truth:
+ *                    gt_area when given
+ *   Everything else - ranking, truncation, ignore, matching, ties, every output - as K17 / K16.  With inter from the grid's bits
+ *   and pix = P it gives bdetr_mask_match_coco's outputs bit for bit.  The image's inter is staged in LDS when
+ *   24 Np + 8 Mp + roundup8(Np + Mp) + 4 N M bytes fit the default 64 KiB (N = M = 100 does: 42.4 KiB), otherwise it is read from
+ *   memory.  Limits: those of K17 without P and W; anything else returns -1 (bdetr_last_error) without a launch.
+ * ---------------------------------------------------------------------- */
+int bdetr_mask_upsample_bits(const float* logits, const int32_t* image_hw, int B, int N, int G, int Hm, int Wm, uint64_t* bits,
+                             int32_t* pop, void* stream);
+int bdetr_mask_source_bits(const int32_t* items, int64_t n_items, const int32_t* item_off, const int32_t* kind, const int32_t* hw,
+                           int B, int M, int Hm, int Wm, uint64_t* bits, int32_t* pop, void* stream);
+int bdetr_mask_inter(const uint64_t* det_bits, const uint64_t* gt_bits, const int32_t* num_objects, int B, int N, int M, int Hm, int Wm,
+                     int32_t* inter, void* stream);
+int bdetr_mask_match_coco_inter(const float* score, const int32_t* label, const int32_t* inter, const int32_t* det_pop,
+                                const int32_t* gt_label, const int32_t* gt_pop, const uint8_t* gt_crowd, const float* gt_area,
+                                const int32_t* num_objects, const int32_t* image_hw, const int32_t* pix, const double* area_ranges,
+                                const double* thresholds, int B, int N, int M, int C, int T, int A, int max_dets, int32_t* order,
+                                int32_t* class_rank, uint16_t* tp_bits, uint16_t* ig_bits, int32_t* matched_gt, int32_t* gt_count,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif
