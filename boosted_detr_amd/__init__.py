@@ -78,10 +78,11 @@ def __getattr__(name):
     if name == "BoostedDETR":
         from .boosted_model import BoostedDETR
         return BoostedDETR
-    if name in ("SGD", "AdamW", "Adam", "CosineDecayRestarts", "ModelCheckpoint", "TerminateOnNaN", "TensorBoard", "latest_checkpoint", "DetectionAP"):
+    if name in ("SGD", "AdamW", "Adam", "CosineDecayRestarts", "ModelCheckpoint", "TerminateOnNaN", "TensorBoard", "latest_checkpoint", "DetectionAP",
+                "PanopticQuality"):
         from . import training
         return getattr(training, name)
-    if name in ("DetectionEvaluator", "MaskEvaluator"):
+    if name in ("DetectionEvaluator", "MaskEvaluator", "PanopticEvaluator"):
         from . import evaluation
         return getattr(evaluation, name)
     raise AttributeError(name)

@@ -211,6 +211,13 @@ SIGNATURES = {
     "bdetr_mask_source_bits": (I, [P, L, P, P, P, I, I, I, I, P, P, P]),
     "bdetr_mask_inter": (I, [P, P, P, I, I, I, I, I, P, P]),
     "bdetr_mask_match_coco_inter": (I, [P] * 13 + [I] * 7 + [P] * 7),
+    # K23-K26 (csrc/panopticmerge.hip): panoptic quality at image resolution.  K23: which queries become segments; K24: the
+    # per-pixel merge of the kept queries (K19's value, largest positive wins) into ids and disjoint bitmasks; K25: the ground
+    # truth made exclusive in place; K26: panopticapi's matching in integers
+    "bdetr_panoptic_select": (I, [P, P, P, I, I, I, F, P, P]),
+    "bdetr_panoptic_merge": (I, [P, P, P, I, I, I, I, I, P, P, P, P]),
+    "bdetr_panoptic_gt_exclusive": (I, [P, P, P, I, I, I, I, I, P, P]),
+    "bdetr_panoptic_match": (I, [P] * 8 + [I] * 5 + [P] * 5),
 }
 
 

@@ -16,6 +16,9 @@ ground truths as their exact source bitmasks, areas in pixels.  What remains dif
 boundary rule of K18 (boundary pixels can differ from pycocotools' scan conversion; RLE is exact) and an upsample rule that is this
 project's own (bilinear in fp64, reproducible bit for bit; it agrees with torch's interpolate except within rounding of zero).  A
 query's mask shares its box's class and score (DETR's convention).
+
+``PanopticEvaluator`` (K23-K26) is the COCO panoptic task's PQ / SQ / RQ at image resolution: the kept queries' upsampled logits merged
+into one id per pixel, the ground truths made disjoint, panopticapi's matching in integers; ``accumulate_pq`` is its host half.
 """
 from __future__ import annotations
 
@@ -460,6 +463,40 @@ def host_image_hw(height, width) -> np.ndarray:
     return np.stack(parts, axis=1).astype(np.int32)
 
 
+def check_image_mask_batch(segments, image_hw_host, N: int, max_mask_bytes: int):
+    """Every refusal of an image-resolution update() that needs no device (CocoImageMaskEvaluator, PanopticEvaluator): the segments
+    pack, the images' sizes, that every segmented object was annotated on its image's own (height, width), and the byte budget
+    of the two bitmask buffers.  Returns (image_hw int32 [B,2], Hm, Wm)."""
+    from . import kernels as K
+    if not isinstance(segments, dict) or any(k not in segments for k in ("items", "item_off", "kind", "hw")):
+        raise ValueError("image-resolution masks need the batch's 'segments': the host pack of pipeline.pad_annotations(..., "
+                         "with_masks=True) (items, item_off, kind, hw); dense 'masks' are grid data")
+    if hasattr(image_hw_host, "is_cuda"):
+        if image_hw_host.is_cuda:
+            raise ValueError("image_hw_host must be a host array [B,2], not a device tensor: the buffer sizes come from it")
+        image_hw_host = image_hw_host.numpy()
+    hw = np.asarray(image_hw_host)
+    kind, seg_hw = segments["kind"], segments["hw"]
+    if not isinstance(kind, np.ndarray) or kind.ndim != 2 or not isinstance(seg_hw, np.ndarray) or seg_hw.shape != kind.shape + (2,):
+        raise ValueError("segments: kind must be a NumPy array [B,M] and hw [B,M,2]")
+    B, M = kind.shape
+    if hw.shape != (B, 2) or not np.issubdtype(hw.dtype, np.integer):
+        raise ValueError(f"image_hw_host must be integers [B={B},2] (height, width), got {hw.dtype} {hw.shape}")
+    hw = hw.astype(np.int32)
+    Hm, Wm = K.mask_layout(hw)
+    used = kind != K.MASK_KIND_NONE
+    wrong = used & (seg_hw != hw[:, None, :]).any(axis=2)
+    if wrong.any():
+        b, m = (int(v[0]) for v in np.nonzero(wrong))
+        raise ValueError(f"segments: object {m} of image {b} was annotated on a {tuple(int(v) for v in seg_hw[b, m])} image, the batch "
+                         f"says (height, width) = {tuple(int(v) for v in hw[b])}")
+    need = 8 * Hm * Wm * B * (int(N) + M)
+    if need > max_mask_bytes:
+        raise ValueError(f"the bitmask buffers of this batch need {need} bytes (8 Hm Wm B (N + M) with Hm={Hm}, Wm={Wm}, B={B}, N={N}, "
+                         f"M={M}); max_mask_bytes is {max_mask_bytes}")
+    return hw, Hm, Wm
+
+
 class CocoImageMaskEvaluator(CocoEvaluator):
     """Running mask AP (iouType="segm") by the full COCO protocol AT IMAGE RESOLUTION, as a COCO user compares it: every query's
     logits are upsampled to its image's height x width and cut at 0 (bdetr_mask_upsample_bits, K19 - DETR's own segmentation
@@ -484,34 +521,7 @@ class CocoImageMaskEvaluator(CocoEvaluator):
     def check_batch(self, segments, image_hw_host, N: int):
         """Every refusal of update() that needs no device: the segments pack, the images' sizes, that every segmented object was
         annotated on its image's own (height, width), and the byte budget.  Returns (image_hw int32 [B,2], Hm, Wm)."""
-        from . import kernels as K
-        if not isinstance(segments, dict) or any(k not in segments for k in ("items", "item_off", "kind", "hw")):
-            raise ValueError("image-resolution masks need the batch's 'segments': the host pack of pipeline.pad_annotations(..., "
-                             "with_masks=True) (items, item_off, kind, hw); dense 'masks' are grid data")
-        if hasattr(image_hw_host, "is_cuda"):
-            if image_hw_host.is_cuda:
-                raise ValueError("image_hw_host must be a host array [B,2], not a device tensor: the buffer sizes come from it")
-            image_hw_host = image_hw_host.numpy()
-        hw = np.asarray(image_hw_host)
-        kind, seg_hw = segments["kind"], segments["hw"]
-        if not isinstance(kind, np.ndarray) or kind.ndim != 2 or not isinstance(seg_hw, np.ndarray) or seg_hw.shape != kind.shape + (2,):
-            raise ValueError("segments: kind must be a NumPy array [B,M] and hw [B,M,2]")
-        B, M = kind.shape
-        if hw.shape != (B, 2) or not np.issubdtype(hw.dtype, np.integer):
-            raise ValueError(f"image_hw_host must be integers [B={B},2] (height, width), got {hw.dtype} {hw.shape}")
-        hw = hw.astype(np.int32)
-        Hm, Wm = K.mask_layout(hw)
-        used = kind != K.MASK_KIND_NONE
-        wrong = used & (seg_hw != hw[:, None, :]).any(axis=2)
-        if wrong.any():
-            b, m = (int(v[0]) for v in np.nonzero(wrong))
-            raise ValueError(f"segments: object {m} of image {b} was annotated on a {tuple(int(v) for v in seg_hw[b, m])} image, the batch "
-                             f"says (height, width) = {tuple(int(v) for v in hw[b])}")
-        need = 8 * Hm * Wm * B * (int(N) + M)
-        if need > self.max_mask_bytes:
-            raise ValueError(f"the bitmask buffers of this batch need {need} bytes (8 Hm Wm B (N + M) with Hm={Hm}, Wm={Wm}, B={B}, N={N}, "
-                             f"M={M}); max_mask_bytes is {self.max_mask_bytes}")
-        return hw, Hm, Wm
+        return check_image_mask_batch(segments, image_hw_host, N, self.max_mask_bytes)
 
     def update(self, cat_pred, mask_logits, cat_ids, segments, num_objects, image_hw_host, iscrowd=None, area=None) -> None:
         """cat_pred [B,N,C] and mask_logits f32 [B,N,G,G] (or [B,N,G*G]) in HBM as for CocoMaskEvaluator.update; cat_ids int32 [B,M];
@@ -547,6 +557,182 @@ class CocoImageMaskEvaluator(CocoEvaluator):
             self.iou_thresholds, self.num_classes, self.max_dets[-1], self._gt_count)
         self._kept.append((score, label, class_rank, tp_bits, ig_bits, order))
         self.last_matched_gt = matched
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# panoptic quality (K23-K26)
+# ---------------------------------------------------------------------------------------------------------------------
+def accumulate_pq(records: Sequence[tuple], num_classes: int, stuff_classes=()) -> Dict[str, object]:
+    """panopticapi's PQStat over what bdetr_panoptic_match left.
+
+    records: per batch, in arrival order, ``(gt_state [B,M], pred_state [B,N], match_inter [B,M], match_union [B,M], gt_label [B,M],
+    pred_label [B,N])`` int32 host arrays.  Walked in (batch, image, row) order: a ground-truth row with state >= 0 is a TP of its
+    class and adds (double)match_inter / (double)match_union to that class's running fp64 iou_sum, state -1 is a FN; a predicted
+    row with state -1 is a FP of its class.  Per class PQ = iou_sum / (tp + fp / 2 + fn / 2), SQ = iou_sum / tp (0 without a TP),
+    RQ = tp / (tp + fp / 2 + fn / 2); the averages are the means over the classes with tp + fp + fn > 0 - over all of them, over
+    the things (every class not in stuff_classes) and over the stuff - and 0.0 with 0 classes when there is none."""
+    C = int(num_classes)
+    tp, fp, fn = np.zeros(C, np.int64), np.zeros(C, np.int64), np.zeros(C, np.int64)
+    iou_sum = [0.0] * C
+    images = 0
+    for gt_state, pred_state, match_inter, match_union, gt_label, pred_label in records:
+        gs, gl = np.asarray(gt_state, np.int64).reshape(-1), np.asarray(gt_label, np.int64).reshape(-1)
+        ps, pl = np.asarray(pred_state, np.int64).reshape(-1), np.asarray(pred_label, np.int64).reshape(-1)
+        mi, mu = np.asarray(match_inter, np.int64).reshape(-1), np.asarray(match_union, np.int64).reshape(-1)
+        images += int(np.asarray(gt_state).shape[0])
+        g_ok, p_ok = (gl >= 0) & (gl < C), (pl >= 0) & (pl < C)
+        tp += np.bincount(gl[(gs >= 0) & g_ok], minlength=C)
+        fn += np.bincount(gl[(gs == -1) & g_ok], minlength=C)
+        fp += np.bincount(pl[(ps == -1) & p_ok], minlength=C)
+        for k in np.flatnonzero((gs >= 0) & g_ok):                # row-major: image by image, row by row
+            iou_sum[int(gl[k])] += float(mi[k]) / float(mu[k])
+    pq, sq, rq = np.full(C, np.nan), np.full(C, np.nan), np.full(C, np.nan)
+    scored = (tp + fp + fn) > 0
+    for c in np.flatnonzero(scored):
+        denom = float(tp[c]) + 0.5 * float(fp[c]) + 0.5 * float(fn[c])
+        pq[c] = iou_sum[c] / denom
+        sq[c] = iou_sum[c] / float(tp[c]) if tp[c] else 0.0
+        rq[c] = float(tp[c]) / denom
+    stuff = np.zeros(C, bool)
+    stuff[[int(c) for c in stuff_classes]] = True
+
+    def average(sel):
+        pick = np.flatnonzero(scored & sel)
+        if pick.size == 0:
+            return 0.0, 0.0, 0.0, 0
+        n = float(pick.size)
+        return (sum(float(pq[c]) for c in pick) / n, sum(float(sq[c]) for c in pick) / n, sum(float(rq[c]) for c in pick) / n, int(pick.size))
+
+    out: Dict[str, object] = {}
+    for suffix, sel in (("", np.ones(C, bool)), ("_th", ~stuff), ("_st", stuff)):
+        p, s, r, n = average(sel)
+        out.update({"PQ" + suffix: p, "SQ" + suffix: s, "RQ" + suffix: r, "num_classes_scored" + suffix: n})
+    out.update(per_class_PQ=pq, per_class_SQ=sq, per_class_RQ=rq, tp=tp, fp=fp, fn=fn, iou_sum=np.asarray(iou_sum, np.float64),
+               num_images=images)
+    return out
+
+
+class PanopticEvaluator:
+    """Running panoptic quality (PQ / SQ / RQ of the COCO panoptic task) at image resolution.  ``update`` chains, on the current
+    stream: the ground truths' exact source bitmasks (bdetr_mask_source_bits, K20) made exclusive in place
+    (bdetr_panoptic_gt_exclusive, K25), bdetr_det_postprocess, the selection of the queries that become segments
+    (bdetr_panoptic_select, K23: score > score_threshold, the kept queries of a stuff class merged), the per-pixel merge of their
+    upsampled logits into pairwise disjoint masks (bdetr_panoptic_merge, K24), the popcount intersection of the two disjoint sets
+    (bdetr_mask_inter, K21) and panopticapi's matching in integers (bdetr_panoptic_match, K26).  Per batch it keeps gt_state /
+    match_inter / match_union / gt_label [B,M] and pred_state / pred_label [B,N] in HBM and reads nothing back; ``result`` makes one
+    device-to-host copy and accumulates on the host (``accumulate_pq``).
+
+    What differs from DETR's PostProcessPanoptic and panopticapi (include/bdetr.h, K24 / K26): a pixel that no kept query claims
+    with a positive logit stays void; a predicted segment below min_area pixels is no segment (neither FP nor matchable) instead
+    of being removed before a second argmax; the crowd rule sums over all crowd segments of the class.
+    stuff_classes: class ids in [2, num_classes); max_mask_bytes: as CocoImageMaskEvaluator's."""
+
+    DEFAULT_MAX_MASK_BYTES = CocoImageMaskEvaluator.DEFAULT_MAX_MASK_BYTES
+
+    def __init__(self, num_classes: int, score_threshold: float = 0.85, min_area: int = 5, stuff_classes=(), max_mask_bytes: Optional[int] = None):
+        if num_classes < 3:
+            raise ValueError("num_classes counts <PAD> and <OOV>: at least 3")
+        if not 0.0 <= float(score_threshold) < 1.0:
+            raise ValueError(f"score_threshold must be in [0, 1), got {score_threshold}")
+        if int(min_area) != min_area or int(min_area) < 0:
+            raise ValueError(f"min_area must be a non-negative integer, got {min_area}")
+        self.num_classes, self.score_threshold, self.min_area = int(num_classes), float(score_threshold), int(min_area)
+        self.stuff_classes = self.check_stuff_classes(stuff_classes, self.num_classes)
+        self.max_mask_bytes = self.DEFAULT_MAX_MASK_BYTES if max_mask_bytes is None else int(max_mask_bytes)
+        if self.max_mask_bytes < 1:
+            raise ValueError("max_mask_bytes must be positive")
+        self.reset()
+
+    @staticmethod
+    def check_stuff_classes(stuff_classes, num_classes: int) -> tuple:
+        """Sorted distinct class ids; anything that is not an integer in [2, num_classes) is a ValueError."""
+        out = set()
+        for c in ([] if stuff_classes is None else stuff_classes):
+            if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)) or not 2 <= int(c) < num_classes:
+                raise ValueError(f"stuff_classes must be class ids (integers) in [2, {num_classes}), got {c!r}")
+            out.add(int(c))
+        return tuple(sorted(out))
+
+    def reset(self) -> None:
+        self._kept: List[tuple] = []          # per batch: (gt_state, pred_state, match_inter, match_union, gt_label, pred_label)
+        self._is_stuff = None                 # uint8 [C] in HBM, allocated by the first update that needs it
+        self.last = None                      # the last batch's small intermediates, in HBM (inspection / tests)
+
+    def check_batch(self, segments, image_hw_host, N: int):
+        """CocoImageMaskEvaluator.check_batch's refusals and byte budget.  Returns (image_hw int32 [B,2], Hm, Wm)."""
+        return check_image_mask_batch(segments, image_hw_host, N, self.max_mask_bytes)
+
+    def update(self, cat_pred, mask_logits, cat_ids, segments, num_objects, image_hw_host, iscrowd=None) -> None:
+        """cat_pred [B,N,C], mask_logits f32 [B,N,G,G] (or [B,N,G*G]), cat_ids int32 [B,M], num_objects int32 [B] in HBM; segments:
+        the HOST pack of pad_annotations(with_masks=True); image_hw_host: HOST integers [B,2]; iscrowd [B,M] or None - exactly what
+        CocoImageMaskEvaluator.update takes.  Every refusal comes before the first launch."""
+        import torch
+        from . import kernels as K
+        if cat_pred.shape[-1] != self.num_classes:
+            raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {self.num_classes}")
+        if cat_pred.dim() != 3 or mask_logits.dim() not in (3, 4) or cat_ids.dim() != 2:
+            raise ValueError("expected cat_pred [B,N,C], mask_logits [B,N,G,G], cat_ids [B,M]")
+        B, N = cat_pred.shape[:2]
+        M = cat_ids.shape[1]
+        G = int(round(float(mask_logits.shape[2]) ** 0.5)) if mask_logits.dim() == 3 else int(mask_logits.shape[2])
+        if tuple(mask_logits.shape[:2]) != (B, N) or mask_logits[0, 0].numel() != G * G:
+            raise ValueError(f"mask_logits {tuple(mask_logits.shape)} do not fit cat_pred [B={B},N={N},C] with a square grid")
+        hw, Hm, Wm = self.check_batch(segments, image_hw_host, N)
+        if segments["kind"].shape != (B, M):
+            raise ValueError(f"segments: kind is {segments['kind'].shape}, cat_ids [B={B},M={M}]")
+        device = cat_pred.device
+        gt_bits, _ = K.mask_source_bits(segments["items"], segments["item_off"], segments["kind"], segments["hw"], Hm, Wm, device=device)
+        hw_dev = torch.from_numpy(hw).to(device)
+        crowd = None if iscrowd is None else (torch.as_tensor(iscrowd).to(device) != 0).to(torch.uint8).reshape(B, M).contiguous()
+        if self.stuff_classes and self._is_stuff is None:
+            flags = np.zeros(self.num_classes, np.uint8)
+            flags[list(self.stuff_classes)] = 1
+            self._is_stuff = torch.from_numpy(flags).to(device)
+        num_objects = num_objects.reshape(-1).contiguous()
+        gt_label = cat_ids.contiguous()
+        gt_pop = K.panoptic_gt_exclusive(gt_bits, gt_label, num_objects, self.num_classes)
+        score, label = K.det_postprocess(cat_pred.contiguous())
+        seg_of = K.panoptic_select(score, label, self.score_threshold, self.num_classes, self._is_stuff)
+        _, bits, pop = K.panoptic_merge(mask_logits.reshape(B, N, G, G).contiguous(), seg_of, hw_dev, Hm, Wm)
+        inter = K.mask_inter(bits, gt_bits, num_objects)
+        gt_state, pred_state, match_inter, match_union = K.panoptic_match(inter, pop, label, seg_of, gt_pop, gt_label, crowd, num_objects,
+                                                                          self.num_classes, self.min_area)
+        self._kept.append((gt_state, pred_state, match_inter, match_union, gt_label, label))
+        self.last = {"seg_of": seg_of, "pred_pop": pop, "gt_pop": gt_pop, "inter": inter, "score": score}
+
+    # the protocol of evaluation.results(): one copy for several evaluators
+    def _device_parts(self) -> list:
+        return [t.reshape(-1) for rec in self._kept for t in rec]
+
+    def _flat_size(self) -> int:
+        return sum(t.numel() for rec in self._kept for t in rec)
+
+    def _nothing(self):
+        return ([],)
+
+    def _from_flat(self, flat: np.ndarray):
+        records, o = [], 0
+        for rec in self._kept:
+            host = []
+            for t in rec:
+                host.append(flat[o:o + t.numel()].reshape(tuple(t.shape)))
+                o += t.numel()
+            records.append(tuple(host))
+        return (records,)
+
+    def _to_host(self):
+        """One device-to-host copy: every kept tensor, packed as int32 words."""
+        import torch
+        if not self._kept:
+            return []
+        return self._from_flat(torch.cat(self._device_parts()).cpu().numpy())[0]
+
+    def result_from(self, records: Sequence[tuple]) -> Dict[str, object]:
+        """The host half alone: accumulate_pq over records as the kernels leave them (host int32 arrays; no device is needed)."""
+        return accumulate_pq(records, self.num_classes, self.stuff_classes)
+
+    def result(self) -> Dict[str, object]:
+        return self.result_from(self._to_host())
 
 
 def results(evaluators: Sequence[DetectionEvaluator]) -> List[Dict[str, object]]:

@@ -1474,6 +1474,115 @@ def mask_match_coco_inter(score, label, inter, det_pop, gt_label, gt_pop, gt_cro
 
 
 # --------------------------------------------------------------------------------------
+# panoptic merge and panoptic quality - csrc/panopticmerge.hip (K23-K26)
+# --------------------------------------------------------------------------------------
+PANOPTIC_MAX_ROWS = 1024          # queries / ground-truth rows per image
+
+
+def panoptic_select(score, label, threshold: float, num_classes: int, is_stuff=None):
+    """score f32 [B,N], label int32 [B,N] (det_postprocess), is_stuff uint8 [C] or None -> seg_of int32 [B,N] (include/bdetr.h,
+    K23): -1 when not score > threshold, the lowest kept query of the same label for a stuff class, otherwise n itself."""
+    _dtypes("panoptic_select", score=(score, torch.float32), label=(label, torch.int32))
+    if score.dim() != 2 or score.numel() == 0 or tuple(label.shape) != tuple(score.shape):
+        raise _lib.BdetrError("panoptic_select: operand shapes disagree (score [B,N], label [B,N])")
+    B, N = score.shape
+    if N > PANOPTIC_MAX_ROWS:
+        raise ValueError(f"panoptic_select: N must be in [1, {PANOPTIC_MAX_ROWS}], got {N}")
+    if not 0.0 <= float(threshold) < 1.0:
+        raise ValueError(f"panoptic_select: threshold must be in [0, 1), got {threshold}")
+    if is_stuff is not None:
+        _dtypes("panoptic_select", is_stuff=(is_stuff, torch.uint8))
+        if is_stuff.dim() != 1 or is_stuff.numel() != int(num_classes):
+            raise _lib.BdetrError(f"panoptic_select: is_stuff must be [C={int(num_classes)}]")
+        _chk(is_stuff, dtype=torch.uint8)
+    _chk(score)
+    _chk(label, dtype=torch.int32)
+    seg_of = empty(B, N, like=score, dtype=torch.int32)
+    check(_lib.lib().bdetr_panoptic_select(_p(score), _p(label), _p(is_stuff), B, N, int(num_classes), float(threshold), _p(seg_of), _stream()),
+          "panoptic_select")
+    return seg_of
+
+
+def panoptic_merge(logits, seg_of, image_hw, Hm: int, Wm: int, with_bits: bool = True):
+    """logits f32 [B,N,G,G], seg_of int32 [B,N], image_hw int32 [B,2] in HBM -> (ids int16 [B,Hm,64 Wm], bits int64 [B,N,Hm,Wm] or
+    None, pop int32 [B,N]) (include/bdetr.h, K24): per pixel the kept query (seg_of >= 0) with the largest positive value of
+    mask_upsample_bits' rule wins, ids holds its seg_of (-1: void or outside the image), bits[b,s] the pixels of id s - pairwise
+    disjoint - and pop their counts.  with_bits=False passes NULL: the bitmasks are not written."""
+    _dtypes("panoptic_merge", logits=(logits, torch.float32), seg_of=(seg_of, torch.int32), image_hw=(image_hw, torch.int32))
+    if logits.dim() != 4 or logits.shape[2] != logits.shape[3] or logits.numel() == 0:
+        raise _lib.BdetrError(f"panoptic_merge: logits must be [B,N,G,G] with at least one element, got {tuple(logits.shape)}")
+    B, N, G, _ = logits.shape
+    if tuple(seg_of.shape) != (B, N) or tuple(image_hw.shape) != (B, 2):
+        raise _lib.BdetrError("panoptic_merge: operand shapes disagree (logits [B,N,G,G], seg_of [B,N], image_hw [B,2])")
+    if not 1 <= G <= MASK_MAX_GRID:
+        raise ValueError(f"panoptic_merge: G must be in [1, {MASK_MAX_GRID}], got {G}")
+    if N > PANOPTIC_MAX_ROWS:
+        raise ValueError(f"panoptic_merge: N must be in [1, {PANOPTIC_MAX_ROWS}], got {N}")
+    Hm, Wm = _check_layout("panoptic_merge", Hm, Wm)
+    _chk(logits)
+    _chk(seg_of, image_hw, dtype=torch.int32)
+    ids = empty(B, Hm, 64 * Wm, like=logits, dtype=torch.int16)
+    bits = empty(B, N, Hm, Wm, like=logits, dtype=torch.int64) if with_bits else None
+    pop = empty(B, N, like=logits, dtype=torch.int32)
+    check(_lib.lib().bdetr_panoptic_merge(_p(logits), _p(seg_of), _p(image_hw), B, N, G, Hm, Wm, _p(ids), _p(bits), _p(pop), _stream()),
+          "panoptic_merge")
+    return ids, bits, pop
+
+
+def panoptic_gt_exclusive(gt_bits, gt_label, num_objects, num_classes: int):
+    """mask_source_bits' gt_bits int64 [B,M,Hm,Wm] IN PLACE -> the ground truth as a panoptic map (include/bdetr.h, K25): rows at
+    or past num_objects and rows with a label outside [2, C) are zeroed, every other row loses the pixels an earlier row covers.
+    Returns gt_pop int32 [B,M], the exclusive pixel counts."""
+    _dtypes("panoptic_gt_exclusive", gt_bits=(gt_bits, torch.int64), gt_label=(gt_label, torch.int32), num_objects=(num_objects, torch.int32))
+    if gt_bits.dim() != 4 or gt_bits.numel() == 0:
+        raise _lib.BdetrError(f"panoptic_gt_exclusive: gt_bits must be [B,M,Hm,Wm], got {tuple(gt_bits.shape)}")
+    B, M, Hm, Wm = gt_bits.shape
+    if tuple(gt_label.shape) != (B, M) or num_objects.numel() != B:
+        raise _lib.BdetrError("panoptic_gt_exclusive: operand shapes disagree (gt_bits [B,M,Hm,Wm], gt_label [B,M], num_objects [B])")
+    if M > PANOPTIC_MAX_ROWS:
+        raise ValueError(f"panoptic_gt_exclusive: M must be in [1, {PANOPTIC_MAX_ROWS}], got {M}")
+    _check_layout("panoptic_gt_exclusive", Hm, Wm)
+    _chk(gt_bits, dtype=torch.int64)
+    _chk(gt_label, num_objects, dtype=torch.int32)
+    gt_pop = empty(B, M, like=gt_bits, dtype=torch.int32)
+    check(_lib.lib().bdetr_panoptic_gt_exclusive(_p(gt_bits), _p(gt_label), _p(num_objects), B, M, int(num_classes), Hm, Wm, _p(gt_pop),
+                                                 _stream()), "panoptic_gt_exclusive")
+    return gt_pop
+
+
+def panoptic_match(inter, pred_pop, pred_label, seg_of, gt_pop, gt_label, gt_crowd, num_objects, num_classes: int, min_area: int):
+    """panopticapi's matching in integers (include/bdetr.h, K26): inter int32 [B,N,M] (mask_inter on the two disjoint sets),
+    pred_pop / pred_label / seg_of int32 [B,N], gt_pop / gt_label int32 [B,M], gt_crowd uint8 [B,M] or None, num_objects int32 [B]
+    -> (gt_state [B,M], pred_state [B,N], match_inter [B,M], match_union [B,M]), all int32."""
+    _dtypes("panoptic_match", inter=(inter, torch.int32), pred_pop=(pred_pop, torch.int32), pred_label=(pred_label, torch.int32),
+            seg_of=(seg_of, torch.int32), gt_pop=(gt_pop, torch.int32), gt_label=(gt_label, torch.int32), num_objects=(num_objects, torch.int32))
+    if inter.dim() != 3 or inter.numel() == 0:
+        raise _lib.BdetrError(f"panoptic_match: inter must be [B,N,M], got {tuple(inter.shape)}")
+    B, N, M = inter.shape
+    if any(tuple(t.shape) != (B, N) for t in (pred_pop, pred_label, seg_of)) or any(tuple(t.shape) != (B, M) for t in (gt_pop, gt_label)) \
+            or num_objects.numel() != B:
+        raise _lib.BdetrError("panoptic_match: operand shapes disagree (inter [B,N,M], pred_* / seg_of [B,N], gt_* [B,M], num_objects [B])")
+    if gt_crowd is not None:
+        _dtypes("panoptic_match", gt_crowd=(gt_crowd, torch.uint8))
+        if tuple(gt_crowd.shape) != (B, M):
+            raise _lib.BdetrError("panoptic_match: gt_crowd must be [B,M]")
+        _chk(gt_crowd, dtype=torch.uint8)
+    if N > PANOPTIC_MAX_ROWS or M > PANOPTIC_MAX_ROWS:
+        raise ValueError(f"panoptic_match: N and M must be in [1, {PANOPTIC_MAX_ROWS}], got N={N} M={M}")
+    if int(min_area) < 0:
+        raise ValueError(f"panoptic_match: min_area must not be negative, got {min_area}")
+    _chk(inter, pred_pop, pred_label, seg_of, gt_pop, gt_label, num_objects, dtype=torch.int32)
+    gt_state = empty(B, M, like=inter, dtype=torch.int32)
+    pred_state = empty(B, N, like=inter, dtype=torch.int32)
+    match_inter = empty(B, M, like=inter, dtype=torch.int32)
+    match_union = empty(B, M, like=inter, dtype=torch.int32)
+    check(_lib.lib().bdetr_panoptic_match(_p(inter), _p(pred_pop), _p(pred_label), _p(seg_of), _p(gt_pop), _p(gt_label), _p(gt_crowd),
+                                          _p(num_objects), B, N, M, int(num_classes), int(min_area), _p(gt_state), _p(pred_state),
+                                          _p(match_inter), _p(match_union), _stream()), "panoptic_match")
+    return gt_state, pred_state, match_inter, match_union
+
+
+# --------------------------------------------------------------------------------------
 # panoptic head pieces (forward) - csrc/panoptic.hip
 # --------------------------------------------------------------------------------------
 def pad4(c: int) -> int:

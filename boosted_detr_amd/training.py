@@ -682,6 +682,29 @@ class DetectionAP(Callback):
             logs.update(vals)
 
 
+class PanopticQuality(Callback):
+    """Panoptic quality on a held-out set at the end of an epoch: Model.evaluate_panoptic over `validation_data` (at most `steps`
+    batches), every `every` epochs; adds val_PQ, val_SQ and val_RQ to that epoch's logs.  Like DetectionAP it leaves the model as
+    it found it; put it before the callbacks that write the logs.  evaluator / score_threshold / min_area / stuff_classes: as
+    Model.evaluate_panoptic's."""
+
+    def __init__(self, validation_data, every: int = 1, steps: Optional[int] = None, evaluator=None, score_threshold: float = 0.85,
+                 min_area: int = 5, stuff_classes=()):
+        self.validation_data, self.every, self.steps, self.evaluator = validation_data, max(1, int(every)), steps, evaluator
+        self.score_threshold, self.min_area, self.stuff_classes = float(score_threshold), int(min_area), tuple(stuff_classes)
+        self.history: List[dict] = []
+
+    def on_epoch_end(self, epoch, logs=None):
+        if (epoch + 1) % self.every:
+            return
+        res = self.model.evaluate_panoptic(self.validation_data, steps=self.steps, evaluator=self.evaluator, score_threshold=self.score_threshold,
+                                           min_area=self.min_area, stuff_classes=self.stuff_classes)
+        vals = {f"val_{k}": float(res[k]) for k in ("PQ", "SQ", "RQ")}
+        self.history.append({"epoch": epoch, **vals})
+        if logs is not None:
+            logs.update(vals)
+
+
 def latest_checkpoint(checkpoint_dir: str) -> Optional[str]:
     files = sorted(glob.glob(os.path.join(checkpoint_dir, "*.safetensors")), key=os.path.getmtime)
     return files[-1] if files else None
@@ -1449,6 +1472,86 @@ class Model(Layer):
         if return_dict:
             return res
         return [v for p, ev in (("", box_ev), ("mask_", mask_ev)) if ev is not None for v in res[p + "stats"]]
+
+    def panoptic_segmentation(self, inputs: dict, score_threshold: float = 0.85, min_area: int = 5, stuff_classes=()) -> Dict[str, torch.Tensor]:
+        """One id per pixel, in HBM: the queries with score > score_threshold become segments (the kept queries of a class in
+        stuff_classes are one segment, the lowest of them), and per pixel the segment whose query has the largest positive
+        upsampled logit wins (include/bdetr.h, K23 / K24).  Returns panoptic_ids int16 [B,Hm,64 Wm] (the segment's query index; -1:
+        void, or outside the image; Hm = max height, Wm = ceil(max width / 64)), segment_label int32 [B,N] and segment_score f32
+        [B,N] (every query's; a segment's are those of its query), segment_area int32 [B,N] (pixels; 0 where n is no segment or has
+        fewer than min_area pixels - the pixels of such a segment are -1 in panoptic_ids) and image_hw int32 [B,2].  Needs the
+        panoptic head and inputs["height"] / inputs["width"] as host arrays or sequences.  Afterwards panoptic_masks() answers for
+        this call."""
+        from . import evaluation
+        from .engine import to_device
+        from .panoptic_neck import MASK_GRID
+        self._require_panoptic_head()
+        stuff = evaluation.PanopticEvaluator.check_stuff_classes(stuff_classes, self.num_categories)
+        if int(min_area) != min_area or int(min_area) < 0:
+            raise ValueError(f"min_area must be a non-negative integer, got {min_area}")
+        hw = evaluation.host_image_hw(inputs.get("height"), inputs.get("width"))
+        Hm, Wm = K.mask_layout(hw)
+        cat_preds, _, _ = self.predict_raw(inputs)
+        logits = self.panoptic_masks()
+        B, N = logits.shape[:2]
+        if hw.shape[0] != B:
+            raise ValueError(f"'height' / 'width' have {hw.shape[0]} entries, the batch has {B} images")
+        hw_dev = to_device(hw, torch.int32)
+        is_stuff = None
+        if stuff:
+            flags = np.zeros(self.num_categories, np.uint8)
+            flags[list(stuff)] = 1
+            is_stuff = to_device(flags, torch.uint8)
+        score, label = K.det_postprocess(cat_preds.contiguous())
+        seg_of = K.panoptic_select(score, label, float(score_threshold), self.num_categories, is_stuff)
+        ids, _, pop = K.panoptic_merge(logits.reshape(B, N, MASK_GRID, MASK_GRID).contiguous(), seg_of, hw_dev, Hm, Wm, with_bits=False)
+        own = seg_of == torch.arange(N, device=seg_of.device, dtype=torch.int32)[None, :]
+        is_segment = own & (pop >= max(int(min_area), 1))
+        area = torch.where(is_segment, pop, torch.zeros_like(pop))
+        # a small elementwise pass: the pixels of a segment below min_area become void
+        flat = ids.reshape(B, -1)
+        dropped = (flat >= 0) & ~torch.gather(is_segment, 1, flat.clamp(min=0).long())
+        ids = torch.where(dropped, torch.full_like(flat, -1), flat).reshape(ids.shape)
+        return {"panoptic_ids": ids, "segment_label": label, "segment_score": score, "segment_area": area, "image_hw": hw_dev}
+
+    def evaluate_panoptic(self, x: Iterable[dict], steps: Optional[int] = None, evaluator=None, score_threshold: float = 0.85,
+                          min_area: int = 5, stuff_classes=(), return_dict: bool = True, verbose: int = 0):
+        """Panoptic quality (PQ / SQ / RQ of the COCO panoptic task) over the batches of `x`, at image resolution
+        (evaluation.PanopticEvaluator; csrc/panopticmerge.hip, K23-K26).  Per batch: an inference-mode forward pass, the head on that
+        call's features and the evaluator's kernels, nothing read back; one device-to-host copy at the end.  Changes nothing, as
+        evaluate(): weights, moving statistics, optimizer slots and counters, the step seed and what panoptic_masks() answers for
+        stay as they were.  Every batch needs what evaluate(coco=True, mask_resolution="image") needs: 'segments'
+        (pipeline.pad_annotations(with_masks=True)), 'height' / 'width' as HOST arrays (with_eval_fields=True) and optionally
+        'iscrowd'; a batch that lacks them, or whose bitmasks would exceed the evaluator's max_mask_bytes, is a ValueError before
+        anything is launched for it.  evaluator: a PanopticEvaluator (it is reset first; its own threshold, min_area and stuff
+        classes hold); otherwise one is built from score_threshold / min_area / stuff_classes.  Returns its result() dict, or with
+        return_dict=False the list [PQ, SQ, RQ]."""
+        from . import evaluation
+        from .model import _prepare_targets
+        self._require_panoptic_head()
+        ev = evaluator if evaluator is not None else evaluation.PanopticEvaluator(self.num_categories, score_threshold, min_area, stuff_classes)
+        if not isinstance(ev, evaluation.PanopticEvaluator):
+            raise ValueError("evaluate_panoptic needs a PanopticEvaluator as evaluator")
+        ev.reset()
+        keep_panoptic = self._panoptic_inputs
+        t0, n = time.time(), 0
+        try:
+            for step, batch in enumerate(x):
+                if steps is not None and step >= steps:
+                    break
+                segments, hw_host = self._image_mask_fields(batch)      # every refusal of this batch before anything is launched for it
+                ev.check_batch(segments, hw_host, self.num_object_preds)
+                cat_ids, _, bbox, num_objects = _prepare_targets(self, batch)
+                iscrowd, _, _ = self._coco_fields(batch, bbox.shape[0], bbox.shape[1])
+                cat_preds, _, _ = self.predict_raw(batch)
+                ev.update(cat_preds, self.panoptic_masks(), cat_ids, segments, num_objects, hw_host, iscrowd)
+                n += 1
+        finally:
+            self._panoptic_inputs = keep_panoptic      # panoptic_masks() keeps answering for the last call the user made
+        res = ev.result()
+        if verbose:
+            print(f"evaluate_panoptic - {time.time() - t0:.1f}s - {n} steps - " + " - ".join(f"{k}: {res[k]:.4f}" for k in ("PQ", "SQ", "RQ")))
+        return res if return_dict else [res[k] for k in ("PQ", "SQ", "RQ")]
 
     def step_logs(self) -> Dict[str, list]:
         """name -> list of per-image [B] device tensors (one per weak learner).  Nothing is copied to

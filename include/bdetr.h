@@ -864,6 +864,77 @@ int bdetr_mask_match_coco_inter(const float* score, const int32_t* label, const 
                                 int32_t* class_rank, uint16_t* tp_bits, uint16_t* ig_bits, int32_t* matched_gt, int32_t* gt_count,
                                 void* stream);
 
+/* ------------------------------------------------------------------------
+ * K23-K26  panoptic merge and panoptic quality at image resolution (csrc/panopticmerge.hip; evaluation.PanopticEvaluator chains
+ *   K20, K25, K14's postprocess, K23, K24, K21 and K26 once per batch and reads nothing back).  Additions to ABI 8: nothing that
+ *   existed changed.  Every mask uses the layout of K19-K22: uint64 [Hm, Wm], pixel (x, y) is bit (x mod 64) of word [y, x div 64],
+ *   bits outside the image are zero and are WRITTEN as zero by K24 and K25.  1 <= Hm <= 4096, 1 <= Wm <= 64, B <= 65535,
+ *   N <= 1024, M <= 1024, 3 <= C <= 65536, 1 <= G <= 32; anything else returns -1 (bdetr_last_error) without a launch.  No kernel
+ *   reads or writes out of range, whatever its inputs hold (sizes are clamped, ids outside [0, N) count as "not kept").
+ *
+ * K23  bdetr_panoptic_select: score float [B,N], label int32 [B,N] (bdetr_det_postprocess), is_stuff uint8 [C] or NULL,
+ *   0 <= threshold < 1 -> seg_of int32 [B,N]: which queries become segments.
+ *       seg_of[n] = -1 when !(score[n] > threshold): a score equal to the threshold and a NaN score are dropped;
+ *       otherwise, for a label in [0, C) with is_stuff[label] != 0, the LOWEST kept query index of that image with the same
+ *       label (DETR's merging of same-class stuff: the kept queries of a stuff class are one segment); otherwise n itself.
+ *   Above threshold 0.5 a kept query's class is also its argmax over ALL classes, "no object" included (the probabilities sum to
+ *   1, so nothing else can reach 0.5); below 0.5 that is not guaranteed and a kept query can be one that DETR's own
+ *   post-processing, which takes the argmax with "no object" first, would have dropped.
+ *
+ * K24  bdetr_panoptic_merge: logits float [B,N,G,G], seg_of int32 [B,N], image_hw int32 [B,2] (clamped as in K19)
+ *   -> ids int16 [B,Hm,64 Wm] (16-byte aligned), bits uint64 [B,N,Hm,Wm] (may be NULL: not written), pop int32 [B,N].
+ *   A query is KEPT when seg_of[n] is in [0, N).  For every pixel inside the image every kept query's value v is K19's v, by the
+ *   same axis rule and the same three fp64 lines, operation for operation (no FMA), bit for bit.
+ *       winner : the kept query with the largest v among those with v > 0; on an exact tie the LOWEST query index; NaN never wins
+ *       ids    : seg_of[winner]; -1 when no kept query has v > 0, and -1 outside the image (x >= w_b or y >= h_b)
+ *       bits   : bits[b,s] = the pixels with id s - the masks of one image are pairwise disjoint; rows of queries that are no
+ *                segment id are written as zeros
+ *       pop    : the set bits of bits[b,s] (an integer sum; the entry zeroes it, the waves add): two calls give the same bits
+ *   One wave ballot per 64 consecutive x gives one word, as in K19.  The kept queries are compacted once per workgroup, so a
+ *   query that is not kept costs nothing per pixel; their logits are read through the caches and are not staged in LDS (100
+ *   kept queries at G = 23 are 211 KB).
+ *   Stated difference from DETR's PostProcessPanoptic: a pixel that no kept query claims with a positive logit stays void (the
+ *   project's cut at 0, as in K19; DETR takes a softmax argmax over the kept queries and has no void), and small segments are
+ *   dropped at matching time (min_area, K26) instead of re-running the argmax without them.
+ *
+ * K25  bdetr_panoptic_gt_exclusive: K20's gt_bits [B,M,Hm,Wm] IN PLACE -> the ground truth as a panoptic map; gt_label int32
+ *   [B,M], num_objects int32 [B], C.  Rows with m >= num_objects[b] or a label outside [2, C) are zeroed: they are no segments
+ *   and their pixels are void.  Among the remaining rows a pixel belongs to the lowest row that covers it:
+ *       out[m] = in[m] & ~(in[0] | ... | in[m-1])   over segment rows only
+ *   gt_pop int32 [B,M] is rewritten with the exclusive counts (integer adds).  Purely elementwise per word.
+ *
+ * bdetr_mask_inter (K21) is reused unchanged on the two disjoint sets: inter int32 [B,N,M].
+ *
+ * K26  bdetr_panoptic_match: panopticapi's pq_compute_single_core in integers, one workgroup per image.  inter int32 [B,N,M],
+ *   pred_pop int32 [B,N], pred_label int32 [B,N], seg_of int32 [B,N], gt_pop int32 [B,M], gt_label int32 [B,M], gt_crowd uint8
+ *   [B,M] or NULL, num_objects int32 [B], min_area >= 0.
+ *       predicted segment : seg_of[n] == n and pred_pop[n] >= max(min_area, 1)
+ *       gt segment        : m < num_objects[b], label in [2, C) (what K25 kept) and gt_pop[m] >= 1
+ *       void_n            : pred_pop[n] - sum over m of inter[n,m]
+ *       match (n, m)      : both are segments, m is not crowd, the labels are equal, and with
+ *                           union = pred_pop[n] + gt_pop[m] - inter[n,m] - void_n:   2 inter[n,m] > union
+ *                           - the integer form of IoU > 0.5.  On disjoint maps at most one m per n and one n per m can satisfy
+ *                           it, so no ordering is involved (on other inputs the lowest index is taken)
+ *       FN                : an unmatched non-crowd ground-truth segment
+ *       FP                : an unmatched predicted segment, unless 2 (void_n + sum over the crowd segments m of n's label of
+ *                           inter[n,m]) > pred_pop[n]: then it is excused
+ *   Outputs, all int32: gt_state [B,M] (matched n >= 0; -1 FN; -2 crowd; -3 not a segment), pred_state [B,N] (matched m >= 0;
+ *   -1 FP; -2 excused; -3 not a segment), match_inter [B,M] and match_union [B,M] (0 unless matched).
+ *   The two differences from panopticapi: the crowd sum runs over ALL crowd segments of the class (identical whenever an image
+ *   has at most one per class, as COCO panoptic files do), and a predicted segment below min_area is no segment at all - neither
+ *   FP nor matchable - where DETR removes it before the maps are compared.
+ * ---------------------------------------------------------------------- */
+int bdetr_panoptic_select(const float* score, const int32_t* label, const uint8_t* is_stuff, int B, int N, int C, float threshold,
+                          int32_t* seg_of, void* stream);
+int bdetr_panoptic_merge(const float* logits, const int32_t* seg_of, const int32_t* image_hw, int B, int N, int G, int Hm, int Wm,
+                         int16_t* ids, uint64_t* bits, int32_t* pop, void* stream);
+int bdetr_panoptic_gt_exclusive(uint64_t* gt_bits, const int32_t* gt_label, const int32_t* num_objects, int B, int M, int C, int Hm, int Wm,
+                                int32_t* gt_pop, void* stream);
+int bdetr_panoptic_match(const int32_t* inter, const int32_t* pred_pop, const int32_t* pred_label, const int32_t* seg_of,
+                         const int32_t* gt_pop, const int32_t* gt_label, const uint8_t* gt_crowd, const int32_t* num_objects, int B, int N,
+                         int M, int C, int min_area, int32_t* gt_state, int32_t* pred_state, int32_t* match_inter, int32_t* match_union,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
