@@ -19,9 +19,10 @@ OBJ_DIR = CSRC / "_obj"
 SOURCES = ["common.cpp", "igemm.hip", "sgemm.hip", "hconv.hip", "hwgrad.hip", "p16.hip", "attention.hip", "rowchain.hip", "augment.hip", "norm.hip", "groupnorm_rows.hip", "elementwise.hip", "panoptic.hip", "matcher.hip", "optim.hip", "detmetric.hip", "maskmetric.hip", "maskraster.hip", "maskimage.hip", "panopticmerge.hip"]
 ARCH = "gfx950"
 COMMON_FLAGS = ["-O3", "-fPIC", f"--offload-arch={ARCH}", "-std=c++20", "-Wall", "-Wno-unused-function"] + os.environ.get("BDETR_CXXFLAGS", "").split()
-# the matcher must not contract a*b+c into fma (scipy / numpy evaluate unfused); see matcher.hip.  detmetric.hip and
-# maskmetric.hip: the same, for their fp64 IoU; maskraster.hip: for its one fp64 division; maskimage.hip: for its fp64 bilinear
-# rule (every product and sum rounded on its own) and its IoU; panopticmerge.hip: for the same rule, repeated bit for bit
+# the matcher must not contract a*b+c into fma (scipy / numpy evaluate unfused); see matcher.hip.  detmetric.hip, maskmetric.hip
+# and maskimage.hip: the same, for the fp64 IoU of coco_match.h; maskraster.hip: for its one fp64 division; maskimage.hip and
+# panopticmerge.hip: for the fp64 bilinear rule of mask_upsample.h (every product and sum rounded on its own).  The two headers
+# switch contraction off themselves; the flags stay so that the files' own arithmetic does not depend on it either
 PER_FILE_FLAGS = {"matcher.hip": ["-ffp-contract=off"], "detmetric.hip": ["-ffp-contract=off"], "maskmetric.hip": ["-ffp-contract=off"],
                   "maskraster.hip": ["-ffp-contract=off"], "maskimage.hip": ["-ffp-contract=off"], "panopticmerge.hip": ["-ffp-contract=off"]}
 
@@ -41,8 +42,13 @@ def _digest(paths) -> str:
     return h.hexdigest()
 
 
+def headers() -> list:
+    """Every header a translation unit can include: all of csrc/*.h and the public one.  A change to any of them rebuilds everything."""
+    return sorted(CSRC.glob("*.h")) + [CSRC.parent.parent / "include" / "bdetr.h"]
+
+
 def build(force: bool = False, verbose: bool = True) -> Path:
-    deps = [CSRC / s for s in SOURCES] + [CSRC / "common.h", CSRC / "gemm_common.h", CSRC / "p16.h", CSRC.parent.parent / "include" / "bdetr.h"]
+    deps = [CSRC / s for s in SOURCES] + headers()
     stamp = CSRC / "_obj" / "stamp"
     dig = _digest(deps) + "|" + " ".join(COMMON_FLAGS)          # a build with other flags (BDETR_CXXFLAGS) is a different library
     if not force and LIB.exists() and stamp.exists() and stamp.read_text() == dig:
@@ -50,14 +56,14 @@ def build(force: bool = False, verbose: bool = True) -> Path:
     OBJ_DIR.mkdir(exist_ok=True)
     hipcc = _hipcc()
 
-    headers = [d for d in deps if d.suffix == ".h"]
+    hdrs = headers()
 
     def compile_one(src: str) -> Path:
         # one stamp per object: a change to one translation unit recompiles that unit only (a header change recompiles all)
         obj = OBJ_DIR / (src.rsplit(".", 1)[0] + ".o")
         flags = COMMON_FLAGS + PER_FILE_FLAGS.get(src, [])
         ostamp = OBJ_DIR / (src + ".stamp")
-        odig = _digest([CSRC / src] + headers) + "|" + " ".join(flags)
+        odig = _digest([CSRC / src] + hdrs) + "|" + " ".join(flags)
         if not force and obj.exists() and ostamp.exists() and ostamp.read_text() == odig:
             return obj
         cmd = [hipcc, *flags, "-x", "hip", "-c", str(CSRC / src), "-o", str(obj)]

@@ -5,17 +5,18 @@
 // Masks use maskimage.hip's layout: uint64 [Hm, Wm], pixel (x, y) is bit x mod 64 of word [y, x div 64]; bits outside the image
 // are zero and are WRITTEN as zero here.
 //
-// Compiled with -ffp-contract=off like maskimage.hip: K24's value of a pixel is K19's, operation for operation (no FMA), so the
-// merged masks of a single kept query are K19's bit for bit and NumPy reproduces the winner of every pixel.
-#include "common.h"
+// Compiled with -ffp-contract=off like maskimage.hip: K24's value of a pixel is K19's - both call mask_upsample.h (no FMA) -, so
+// the merged masks of a single kept query are K19's bit for bit and NumPy reproduces the winner of every pixel.
+#include "mask_upsample.h"
 #include <limits.h>
+
+using namespace maskup;
 
 namespace {
 
 typedef unsigned long long u64;
 
 constexpr int PM_THREADS = 256;
-constexpr int PM_MAX_G = 32;              // logit grid cells per side (K19's limit)
 constexpr int PM_MAX_DIM = 4096;          // image extents (K19's limit)
 constexpr int PM_MAX_N = 1024;            // queries per image (K21's limit)
 constexpr int PM_MAX_M = 1024;            // ground-truth rows per image (K21's limit)
@@ -63,23 +64,6 @@ __global__ __launch_bounds__(PM_THREADS) void panoptic_select_kernel(const float
 // ---------------------------------------------------------------------------------------------------------------------
 // K24: logits [B,N,G,G], seg_of [B,N] -> ids [B,Hm,64 Wm], bits [B,N,Hm,Wm] (optional), pop [B,N]
 // ---------------------------------------------------------------------------------------------------------------------
-struct pm_axis {
-    int ia, ib;
-    double t;
-};
-
-// maskimage.hip's axis_rule, operation for operation
-__device__ __forceinline__ pm_axis axis_rule(int p, int n, int G) {
-    const int num = (2 * p + 1) * G - n, D = 2 * n;
-    const int i0 = num >= 0 ? num / D : -((D - 1 - num) / D);      // floor division: -1 for every negative num (|num| < D)
-    const int r = num - i0 * D;
-    pm_axis a;
-    a.ia = min(max(i0, 0), G - 1);
-    a.ib = min(max(i0 + 1, 0), G - 1);
-    a.t = (double)r / (double)D;
-    return a;
-}
-
 // Grid (groups of runs, B).  A wave owns one run of 64 consecutive words of its image's Hm x Wm, as in K19: per word, lane l
 // evaluates pixel x = 64 wd + l.  The workgroup first compacts its image's kept queries (seg_of in [0, N)) in ascending order
 // into LDS - a query that is not kept costs nothing per pixel - and each lane then walks the kept list with a running
@@ -112,7 +96,7 @@ __global__ __launch_bounds__(PM_THREADS) void panoptic_merge_kernel(const float*
 
     for (int k = tid; k < PM_MAX_N / 64; k += nthr) s_segmask[k] = 0ull;
     for (int x = tid; x < w; x += nthr) {
-        const pm_axis a = axis_rule(x, w, G);
+        const axis a = axis_rule(x, w, G);
         s_tx[x] = a.t;
         s_ix[x] = (uint16_t)(a.ia | (a.ib << 8));
     }
@@ -153,7 +137,7 @@ __global__ __launch_bounds__(PM_THREADS) void panoptic_merge_kernel(const float*
             int id = -1;
             if (y < h && wd * 64 < w) {
                 if (y != cur_y) {
-                    const pm_axis a = axis_rule(y, h, G);
+                    const axis a = axis_rule(y, h, G);
                     oa = a.ia * G;
                     ob = a.ib * G;
                     ty = a.t;
@@ -169,9 +153,7 @@ __global__ __launch_bounds__(PM_THREADS) void panoptic_merge_kernel(const float*
                     int bq = -1;
                     for (int q = 0; q < K; ++q) {
                         const float* L = Lb + (int)s_kept[q] * GG;
-                        const double top = ux * (double)L[a0] + tx * (double)L[a1];
-                        const double bot = ux * (double)L[b0] + tx * (double)L[b1];
-                        const double v = uy * top + ty * bot;
+                        const double v = bilinear(ux, tx, uy, ty, L[a0], L[a1], L[b0], L[b1]);
                         if (v > best) {                          // NaN > best is false; a tie keeps the lower query
                             best = v;
                             bq = q;
@@ -347,9 +329,9 @@ extern "C" int bdetr_panoptic_select(const float* score, const int32_t* label, c
 extern "C" int bdetr_panoptic_merge(const float* logits, const int32_t* seg_of, const int32_t* image_hw, int B, int N, int G, int Hm, int Wm,
                                     int16_t* ids, uint64_t* bits, int32_t* pop, void* stream) {
     BDETR_CHECK_ARG(logits && seg_of && image_hw && ids && pop, "bdetr_panoptic_merge: null pointer (only bits may be null)");
-    BDETR_CHECK_ARG(B > 0 && B <= 65535 && N > 0 && N <= PM_MAX_N && G >= 1 && G <= PM_MAX_G && pm_layout_ok(Hm, Wm),
+    BDETR_CHECK_ARG(B > 0 && B <= 65535 && N > 0 && N <= PM_MAX_N && G >= 1 && G <= MAX_G && pm_layout_ok(Hm, Wm),
                     "bdetr_panoptic_merge: bad sizes B=%d N=%d G=%d Hm=%d Wm=%d (limits: B in [1, 65535], N in [1, %d], G in [1, %d], "
-                    "Hm in [1, %d], Wm in [1, %d])", B, N, G, Hm, Wm, PM_MAX_N, PM_MAX_G, PM_MAX_DIM, PM_MAX_DIM / 64);
+                    "Hm in [1, %d], Wm in [1, %d])", B, N, G, Hm, Wm, PM_MAX_N, MAX_G, PM_MAX_DIM, PM_MAX_DIM / 64);
     BDETR_CHECK_ARG((uintptr_t)ids % 16 == 0, "bdetr_panoptic_merge: ids must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     if (int e = bdetr_zero_bytes(pop, (size_t)B * N * sizeof(int32_t), st)) return e;      // the waves ADD into it

@@ -176,6 +176,22 @@ class DetectionEvaluator:
         return self.result_from(records, gt_count)
 
 
+def grid_mask_operands(num_classes: int, cat_pred, mask_logits, cat_ids, masks):
+    """The shape checks of a grid-mask update() (MaskEvaluator, CocoMaskEvaluator).  Returns (B, N, M, mask_logits [B,N,P],
+    masks [B,M,P])."""
+    if cat_pred.shape[-1] != num_classes:
+        raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {num_classes}")
+    if cat_pred.dim() != 3 or mask_logits.dim() not in (3, 4) or masks.dim() not in (3, 4) or cat_ids.dim() != 2:
+        raise ValueError("expected cat_pred [B,N,C], mask_logits [B,N,P], cat_ids [B,M], masks [B,M,P]")
+    B, N = cat_pred.shape[:2]
+    M = cat_ids.shape[1]
+    mask_logits, masks = mask_logits.reshape(B, mask_logits.shape[1], -1), masks.reshape(masks.shape[0], masks.shape[1], -1)
+    if tuple(mask_logits.shape[:2]) != (B, N) or tuple(masks.shape[:2]) != (B, M) or mask_logits.shape[2] != masks.shape[2]:
+        raise ValueError(f"mask_logits {tuple(mask_logits.shape)} and masks {tuple(masks.shape)} do not fit cat_pred [B={B},N={N},C] and "
+                         f"cat_ids [B,M={M}] with one pixel count")
+    return B, N, M, mask_logits, masks
+
+
 class MaskEvaluator(DetectionEvaluator):
     """Running COCO-style mask AP (iouType="segm") on the panoptic head's grid.  ``update`` launches bdetr_det_postprocess, two
     bdetr_mask_binarize (logits at 0, targets at 0.5) and bdetr_mask_match on the current stream; what it keeps, and ``result``, are
@@ -189,16 +205,7 @@ class MaskEvaluator(DetectionEvaluator):
         int32 [B].  All in HBM."""
         import torch
         from . import kernels as K
-        if cat_pred.shape[-1] != self.num_classes:
-            raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {self.num_classes}")
-        if cat_pred.dim() != 3 or mask_logits.dim() not in (3, 4) or masks.dim() not in (3, 4) or cat_ids.dim() != 2:
-            raise ValueError("expected cat_pred [B,N,C], mask_logits [B,N,P], cat_ids [B,M], masks [B,M,P]")
-        B, N = cat_pred.shape[:2]
-        M = cat_ids.shape[1]
-        mask_logits, masks = mask_logits.reshape(B, mask_logits.shape[1], -1), masks.reshape(masks.shape[0], masks.shape[1], -1)
-        if tuple(mask_logits.shape[:2]) != (B, N) or tuple(masks.shape[:2]) != (B, M) or mask_logits.shape[2] != masks.shape[2]:
-            raise ValueError(f"mask_logits {tuple(mask_logits.shape)} and masks {tuple(masks.shape)} do not fit cat_pred [B={B},N={N},C] and "
-                             f"cat_ids [B,M={M}] with one pixel count")
+        B, N, M, mask_logits, masks = grid_mask_operands(self.num_classes, cat_pred, mask_logits, cat_ids, masks)
         if self._gt_count is None:
             self._gt_count = torch.zeros(self.num_classes, dtype=torch.int32, device=cat_pred.device)
         score, label = K.det_postprocess(cat_pred.contiguous())
@@ -417,16 +424,7 @@ class CocoMaskEvaluator(CocoEvaluator):
     def update(self, cat_pred, mask_logits, cat_ids, masks, num_objects, iscrowd=None, area=None, image_hw=None) -> None:
         """As MaskEvaluator.update, plus iscrowd / area / image_hw as CocoEvaluator.update takes them (area None: from the mask)."""
         from . import kernels as K
-        if cat_pred.shape[-1] != self.num_classes:
-            raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {self.num_classes}")
-        if cat_pred.dim() != 3 or mask_logits.dim() not in (3, 4) or masks.dim() not in (3, 4) or cat_ids.dim() != 2:
-            raise ValueError("expected cat_pred [B,N,C], mask_logits [B,N,P], cat_ids [B,M], masks [B,M,P]")
-        B, N = cat_pred.shape[:2]
-        M = cat_ids.shape[1]
-        mask_logits, masks = mask_logits.reshape(B, mask_logits.shape[1], -1), masks.reshape(masks.shape[0], masks.shape[1], -1)
-        if tuple(mask_logits.shape[:2]) != (B, N) or tuple(masks.shape[:2]) != (B, M) or mask_logits.shape[2] != masks.shape[2]:
-            raise ValueError(f"mask_logits {tuple(mask_logits.shape)} and masks {tuple(masks.shape)} do not fit cat_pred [B={B},N={N},C] and "
-                             f"cat_ids [B,M={M}] with one pixel count")
+        B, N, M, mask_logits, masks = grid_mask_operands(self.num_classes, cat_pred, mask_logits, cat_ids, masks)
         crowd, area, hw = self._coco_operands(cat_pred.device, B, M, iscrowd, area, image_hw)
         score, label = K.det_postprocess(cat_pred.contiguous())
         det_bits, det_pop = K.mask_binarize(mask_logits.contiguous(), self.LOGIT_THRESHOLD)
@@ -497,6 +495,24 @@ def check_image_mask_batch(segments, image_hw_host, N: int, max_mask_bytes: int)
     return hw, Hm, Wm
 
 
+def image_mask_operands(evaluator, cat_pred, mask_logits, cat_ids, segments, image_hw_host):
+    """The checks of an image-resolution update() (CocoImageMaskEvaluator, PanopticEvaluator): the operands' shapes with the square
+    grid G, then the evaluator's check_batch, then that the pack has cat_ids' rows.  Returns (B, N, M, G, image_hw int32 [B,2], Hm, Wm)."""
+    if cat_pred.shape[-1] != evaluator.num_classes:
+        raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {evaluator.num_classes}")
+    if cat_pred.dim() != 3 or mask_logits.dim() not in (3, 4) or cat_ids.dim() != 2:
+        raise ValueError("expected cat_pred [B,N,C], mask_logits [B,N,G,G], cat_ids [B,M]")
+    B, N = cat_pred.shape[:2]
+    M = cat_ids.shape[1]
+    G = int(round(float(mask_logits.shape[2]) ** 0.5)) if mask_logits.dim() == 3 else int(mask_logits.shape[2])
+    if tuple(mask_logits.shape[:2]) != (B, N) or mask_logits[0, 0].numel() != G * G:
+        raise ValueError(f"mask_logits {tuple(mask_logits.shape)} do not fit cat_pred [B={B},N={N},C] with a square grid")
+    hw, Hm, Wm = evaluator.check_batch(segments, image_hw_host, N)
+    if segments["kind"].shape != (B, M):
+        raise ValueError(f"segments: kind is {segments['kind'].shape}, cat_ids [B={B},M={M}]")
+    return B, N, M, G, hw, Hm, Wm
+
+
 class CocoImageMaskEvaluator(CocoEvaluator):
     """Running mask AP (iouType="segm") by the full COCO protocol AT IMAGE RESOLUTION, as a COCO user compares it: every query's
     logits are upsampled to its image's height x width and cut at 0 (bdetr_mask_upsample_bits, K19 - DETR's own segmentation
@@ -530,18 +546,7 @@ class CocoImageMaskEvaluator(CocoEvaluator):
         area as CocoEvaluator.update takes them (area None: the mask's pixel count).  Every refusal comes before the first launch."""
         import torch
         from . import kernels as K
-        if cat_pred.shape[-1] != self.num_classes:
-            raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {self.num_classes}")
-        if cat_pred.dim() != 3 or mask_logits.dim() not in (3, 4) or cat_ids.dim() != 2:
-            raise ValueError("expected cat_pred [B,N,C], mask_logits [B,N,G,G], cat_ids [B,M]")
-        B, N = cat_pred.shape[:2]
-        M = cat_ids.shape[1]
-        G = int(round(float(mask_logits.shape[2]) ** 0.5)) if mask_logits.dim() == 3 else int(mask_logits.shape[2])
-        if tuple(mask_logits.shape[:2]) != (B, N) or mask_logits[0, 0].numel() != G * G:
-            raise ValueError(f"mask_logits {tuple(mask_logits.shape)} do not fit cat_pred [B={B},N={N},C] with a square grid")
-        hw, Hm, Wm = self.check_batch(segments, image_hw_host, N)
-        if segments["kind"].shape != (B, M):
-            raise ValueError(f"segments: kind is {segments['kind'].shape}, cat_ids [B={B},M={M}]")
+        B, N, M, G, hw, Hm, Wm = image_mask_operands(self, cat_pred, mask_logits, cat_ids, segments, image_hw_host)
         device = cat_pred.device
         # the ground truths first: mask_source_bits checks the whole pack on the host before it launches
         gt_bits, gt_pop = K.mask_source_bits(segments["items"], segments["item_off"], segments["kind"], segments["hw"], Hm, Wm, device=device)
@@ -668,18 +673,7 @@ class PanopticEvaluator:
         CocoImageMaskEvaluator.update takes.  Every refusal comes before the first launch."""
         import torch
         from . import kernels as K
-        if cat_pred.shape[-1] != self.num_classes:
-            raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {self.num_classes}")
-        if cat_pred.dim() != 3 or mask_logits.dim() not in (3, 4) or cat_ids.dim() != 2:
-            raise ValueError("expected cat_pred [B,N,C], mask_logits [B,N,G,G], cat_ids [B,M]")
-        B, N = cat_pred.shape[:2]
-        M = cat_ids.shape[1]
-        G = int(round(float(mask_logits.shape[2]) ** 0.5)) if mask_logits.dim() == 3 else int(mask_logits.shape[2])
-        if tuple(mask_logits.shape[:2]) != (B, N) or mask_logits[0, 0].numel() != G * G:
-            raise ValueError(f"mask_logits {tuple(mask_logits.shape)} do not fit cat_pred [B={B},N={N},C] with a square grid")
-        hw, Hm, Wm = self.check_batch(segments, image_hw_host, N)
-        if segments["kind"].shape != (B, M):
-            raise ValueError(f"segments: kind is {segments['kind'].shape}, cat_ids [B={B},M={M}]")
+        B, N, M, G, hw, Hm, Wm = image_mask_operands(self, cat_pred, mask_logits, cat_ids, segments, image_hw_host)
         device = cat_pred.device
         gt_bits, _ = K.mask_source_bits(segments["items"], segments["item_off"], segments["kind"], segments["hw"], Hm, Wm, device=device)
         hw_dev = torch.from_numpy(hw).to(device)

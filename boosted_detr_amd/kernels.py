@@ -1079,6 +1079,22 @@ def det_postprocess(cat_pred):
     return score, label
 
 
+def _match_outputs(score, thresholds, A=None):
+    """What the five match wrappers share: the host thresholds as contiguous fp64, and the outputs, allocated like score [B,N].
+    Returns (thr, T, order, class_rank, tp_bits, ig_bits, matched_gt); the per-range outputs gain a leading A when A is given
+    (the COCO kernels), otherwise class_rank and ig_bits are None."""
+    B, N = score.shape
+    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
+    T = int(thr.size)
+    lead = () if A is None else (max(A, 1),)
+    order = empty(B, N, like=score, dtype=torch.int32)
+    class_rank = None if A is None else empty(B, N, like=score, dtype=torch.int32)
+    tp_bits = empty(*lead, B, N, like=score, dtype=torch.int16)
+    ig_bits = None if A is None else empty(*lead, B, N, like=score, dtype=torch.int16)
+    matched = empty(*lead, B, max(T, 1), N, like=score, dtype=torch.int32)
+    return thr, T, order, class_rank, tp_bits, ig_bits, matched
+
+
 def det_match(score, label, box_pred, gt_label, gt_box, num_objects, thresholds, num_classes: int, max_dets: int, gt_count):
     """COCOeval's matching of one batch (include/bdetr.h, K14).  thresholds: host fp64 values; gt_count: int32 [num_classes] in HBM,
     the batch's per-class ground-truth counts are added to it.  Returns (order int32 [B,N], tp_bits int16 [B,N] - the uint16 bit
@@ -1087,14 +1103,10 @@ def det_match(score, label, box_pred, gt_label, gt_box, num_objects, thresholds,
     _chk(label, gt_label, num_objects, gt_count, dtype=torch.int32)
     B, N = score.shape
     M = gt_label.shape[1]
-    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
-    T = int(thr.size)
     if tuple(label.shape) != (B, N) or tuple(box_pred.shape) != (B, N, 4) or tuple(gt_label.shape) != (B, M) or tuple(gt_box.shape) != (B, M, 4) \
             or num_objects.numel() != B or gt_count.numel() != num_classes:
         raise _lib.BdetrError("det_match: operand shapes disagree")
-    order = empty(B, N, like=score, dtype=torch.int32)
-    tp_bits = empty(B, N, like=score, dtype=torch.int16)
-    matched = empty(B, max(T, 1), N, like=score, dtype=torch.int32)
+    thr, T, order, _, tp_bits, _, matched = _match_outputs(score, thresholds)
     check(_lib.lib().bdetr_det_match(_p(score), _p(label), _p(box_pred), _p(gt_label), _p(gt_box), _p(num_objects), thr.ctypes.data, B, N, M,
                                      int(num_classes), T, int(max_dets), _p(order), _p(tp_bits), _p(matched), _p(gt_count), _stream()), "det_match")
     return order, tp_bits, matched
@@ -1143,11 +1155,7 @@ def mask_match(score, label, det_bits, det_area, gt_label, gt_bits, gt_area, num
     _chk(score)
     _chk(label, det_area, gt_label, gt_area, num_objects, gt_count, dtype=torch.int32)
     _chk(det_bits, gt_bits, dtype=torch.int64)
-    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
-    T = int(thr.size)
-    order = empty(B, N, like=score, dtype=torch.int32)
-    tp_bits = empty(B, N, like=score, dtype=torch.int16)
-    matched = empty(B, max(T, 1), N, like=score, dtype=torch.int32)
+    thr, T, order, _, tp_bits, _, matched = _match_outputs(score, thresholds)
     check(_lib.lib().bdetr_mask_match(_p(score), _p(label), _p(det_bits), _p(det_area), _p(gt_label), _p(gt_bits), _p(gt_area), _p(num_objects),
                                       thr.ctypes.data, B, N, M, W, int(num_classes), T, int(max_dets), _p(order), _p(tp_bits), _p(matched),
                                       _p(gt_count), _stream()), "mask_match")
@@ -1187,17 +1195,11 @@ def det_match_coco(score, label, box_pred, gt_label, gt_box, gt_crowd, gt_area, 
     _chk(label, gt_label, num_objects, dtype=torch.int32)
     B, N = score.shape
     M = gt_label.shape[1]
-    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
-    T = int(thr.size)
     if tuple(label.shape) != (B, N) or tuple(box_pred.shape) != (B, N, 4) or tuple(gt_label.shape) != (B, M) or tuple(gt_box.shape) != (B, M, 4) \
             or num_objects.numel() != B:
         raise _lib.BdetrError("det_match_coco: operand shapes disagree")
     A = _coco_operands("det_match_coco", B, M, gt_crowd, gt_area, image_hw, area_ranges, gt_count, int(num_classes))
-    order = empty(B, N, like=score, dtype=torch.int32)
-    class_rank = empty(B, N, like=score, dtype=torch.int32)
-    tp_bits = empty(max(A, 1), B, N, like=score, dtype=torch.int16)
-    ig_bits = empty(max(A, 1), B, N, like=score, dtype=torch.int16)
-    matched = empty(max(A, 1), B, max(T, 1), N, like=score, dtype=torch.int32)
+    thr, T, order, class_rank, tp_bits, ig_bits, matched = _match_outputs(score, thresholds, A)
     check(_lib.lib().bdetr_det_match_coco(_p(score), _p(label), _p(box_pred), _p(gt_label), _p(gt_box), _p(gt_crowd), _p(gt_area), _p(num_objects),
                                           _p(image_hw), _p(area_ranges), thr.ctypes.data, B, N, M, int(num_classes), T, A, int(max_dets),
                                           _p(order), _p(class_rank), _p(tp_bits), _p(ig_bits), _p(matched), _p(gt_count), _stream()),
@@ -1224,13 +1226,7 @@ def mask_match_coco(score, label, det_bits, det_pop, gt_label, gt_bits, gt_pop, 
     _chk(score)
     _chk(label, det_pop, gt_label, gt_pop, num_objects, dtype=torch.int32)
     _chk(det_bits, gt_bits, dtype=torch.int64)
-    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
-    T = int(thr.size)
-    order = empty(B, N, like=score, dtype=torch.int32)
-    class_rank = empty(B, N, like=score, dtype=torch.int32)
-    tp_bits = empty(max(A, 1), B, N, like=score, dtype=torch.int16)
-    ig_bits = empty(max(A, 1), B, N, like=score, dtype=torch.int16)
-    matched = empty(max(A, 1), B, max(T, 1), N, like=score, dtype=torch.int32)
+    thr, T, order, class_rank, tp_bits, ig_bits, matched = _match_outputs(score, thresholds, A)
     check(_lib.lib().bdetr_mask_match_coco(_p(score), _p(label), _p(det_bits), _p(det_pop), _p(gt_label), _p(gt_bits), _p(gt_pop), _p(gt_crowd),
                                            _p(gt_area), _p(num_objects), _p(image_hw), _p(area_ranges), thr.ctypes.data, B, N, M, P,
                                            int(num_classes), T, A, int(max_dets), _p(order), _p(class_rank), _p(tp_bits), _p(ig_bits),
@@ -1459,13 +1455,7 @@ def mask_match_coco_inter(score, label, inter, det_pop, gt_label, gt_pop, gt_cro
     A = _coco_operands("mask_match_coco_inter", B, M, gt_crowd, gt_area, image_hw, area_ranges, gt_count, int(num_classes))
     _chk(score)
     _chk(label, inter, det_pop, gt_label, gt_pop, num_objects, pix, dtype=torch.int32)
-    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
-    T = int(thr.size)
-    order = empty(B, N, like=score, dtype=torch.int32)
-    class_rank = empty(B, N, like=score, dtype=torch.int32)
-    tp_bits = empty(max(A, 1), B, N, like=score, dtype=torch.int16)
-    ig_bits = empty(max(A, 1), B, N, like=score, dtype=torch.int16)
-    matched = empty(max(A, 1), B, max(T, 1), N, like=score, dtype=torch.int32)
+    thr, T, order, class_rank, tp_bits, ig_bits, matched = _match_outputs(score, thresholds, A)
     check(_lib.lib().bdetr_mask_match_coco_inter(_p(score), _p(label), _p(inter), _p(det_pop), _p(gt_label), _p(gt_pop), _p(gt_crowd), _p(gt_area),
                                                  _p(num_objects), _p(image_hw), _p(pix), _p(area_ranges), thr.ctypes.data, B, N, M,
                                                  int(num_classes), T, A, int(max_dets), _p(order), _p(class_rank), _p(tp_bits), _p(ig_bits),

@@ -673,6 +673,8 @@ int bdetr_adamw_clipnorm(const uint64_t* ptrs, const int64_t* sizes, int ntensor
 
 /* ------------------------------------------------------------------------
  * K14  detection metric: COCO-style box AP without a host hop per batch (csrc/detmetric.hip; evaluation.py accumulates).
+ *   The matching of K14-K17 and K22 is ONE kernel, csrc/coco_match.h: the five entries differ in where an IoU comes from and in
+ *   whether the ignore class (K16) is compiled in, nothing else.
  *   The reference has no evaluation at all; the rule restated here is pycocotools' COCOeval.evaluateImg for the no-crowd,
  *   all-areas case with one max_dets.
  *   bdetr_det_postprocess : cat_pred [B,N,C] probabilities -> label[B,N] = first-max argmax over classes 2 .. C-1 (0 = <PAD>, "no
@@ -711,7 +713,7 @@ int bdetr_det_match(const float* score, const int32_t* label, const float* box_p
  *                         x[p] > threshold (NaN: not set); the bits of the last word at and past P are zero; area[rows] int32 =
  *                         the row's number of set bits.  One wave per row: the wave's 64-bit ballot of the predicate IS the word.
  *                         Mask logits are cut at 0 (sigmoid > 0.5 without the exponential), [0,1] targets at 0.5.
- *   bdetr_mask_match    : bdetr_det_match with another IoU source.  det_bits [B,N,W], det_area [B,N], gt_bits [B,M,W], gt_area [B,M]
+ *   bdetr_mask_match    : bdetr_det_match (the same kernel, csrc/coco_match.h) with another IoU source.  det_bits [B,N,W], det_area [B,N], gt_bits [B,M,W], gt_area [B,M]
  *                         as bdetr_mask_binarize leaves them, in place of the boxes; score / label / gt_label / num_objects /
  *                         thresholds and the outputs order, tp_bits, matched_gt, gt_count exactly as in K14: the same ranking,
  *                         truncation, valid ground truths and matching rule (on equal IoU the LARGER ground-truth index).
@@ -819,14 +821,14 @@ int bdetr_mask_targets(const int32_t* items, int64_t n_items, const int32_t* ite
  *   bit for bit.  Along an axis with n target pixels, for the target pixel p:
  *       num = (2 p + 1) G - n;  D = 2 n;  i0 = floor(num / D) (floor division: -1 for a negative num);  r = num - i0 D;
  *       ia = max(i0, 0);  ib = min(i0 + 1, G - 1);  t = (double)r / (double)D
- *   and the value, in fp64 with every operation rounded on its own (no FMA: the file is compiled with -ffp-contract=off):
+ *   and the value, in fp64 with every operation rounded on its own (no FMA: csrc/mask_upsample.h switches contraction off):
  *       top = (1 - tx) L[ia_y, ia_x] + tx L[ia_y, ib_x];  bot = the same on row ib_y;  v = (1 - ty) top + ty bot
  *   The bit is set when v > 0 (NaN: not set; an infinite logit next to a zero weight gives NaN, by IEEE).  One wave ballot of the
  *   predicate over 64 consecutive x is the output word.  At h = w = G the rule returns finite logits exactly.
  *   Limits: B N <= 2^24, 1 <= G <= 32; anything else returns -1 (bdetr_last_error) without a launch.
  *
  * K20  bdetr_mask_source_bits: K18's segments pack (items, item_off, kind, hw - see K18) -> bits [B,M,Hm,Wm], pop int32 [B,M].
- *   The mask is K18's SOURCE MASK by the rule stated there (vertices snapped to 1/256 pixel, even-odd fill sampled at pixel
+ *   The mask is K18's SOURCE MASK by the rule stated there, from the same code (csrc/mask_scan.h) (vertices snapped to 1/256 pixel, even-odd fill sampled at pixel
  *   centres, rings ORed, RLE one-runs exact); nothing is placed and no coverage is computed.  pop = the set bits = K18's area.
  *   Objects of kind 0 get zeros and pop 0.  Limits: K18's (B M <= 2^24, n_items < 2^31), else -1 without a launch; per object
  *   K18's rules plus h <= Hm and ceil(w / 64) <= Wm: the kernel cannot report, so an object that breaks one of them gets zeros
@@ -839,7 +841,7 @@ int bdetr_mask_targets(const int32_t* items, int64_t n_items, const int32_t* ite
  *   loads when Hm Wm is even and both bases are 16-byte aligned, else 8-byte loads); tiles at or past num_objects leave at once.
  *   Limits: B <= 65535, N, M <= 1024.
  *
- * K22  bdetr_mask_match_coco_inter: K17's rule, operation for operation, with the IoU source replaced.  In place of det_bits /
+ * K22  bdetr_mask_match_coco_inter: K17's rule (the same kernel, csrc/coco_match.h) with the IoU source replaced.  In place of det_bits /
  *   gt_bits and the scalar P it takes inter int32 [B,N,M] (K21), det_pop / gt_pop (K19 / K20) and pix int32 [B], the number of
  *   pixels a mask of image b has (image mode: h_b w_b; >= 1):
  *       IoU        : union = det_pop + gt_pop - inter, in integers; iou = union > 0 ? (double)inter / (double)union : 0
@@ -884,7 +886,7 @@ int bdetr_mask_match_coco_inter(const float* score, const int32_t* label, const 
  * K24  bdetr_panoptic_merge: logits float [B,N,G,G], seg_of int32 [B,N], image_hw int32 [B,2] (clamped as in K19)
  *   -> ids int16 [B,Hm,64 Wm] (16-byte aligned), bits uint64 [B,N,Hm,Wm] (may be NULL: not written), pop int32 [B,N].
  *   A query is KEPT when seg_of[n] is in [0, N).  For every pixel inside the image every kept query's value v is K19's v, by the
- *   same axis rule and the same three fp64 lines, operation for operation (no FMA), bit for bit.
+ *   same axis rule and the same three fp64 lines - both kernels call csrc/mask_upsample.h - (no FMA), bit for bit.
  *       winner : the kept query with the largest v among those with v > 0; on an exact tie the LOWEST query index; NaN never wins
  *       ids    : seg_of[winner]; -1 when no kept query has v > 0, and -1 outside the image (x >= w_b or y >= h_b)
  *       bits   : bits[b,s] = the pixels with id s - the masks of one image are pairwise disjoint; rows of queries that are no

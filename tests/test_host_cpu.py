@@ -563,3 +563,19 @@ def test_every_kernel_switch_is_forced_by_some_test():
     assert not stale, f"allow-list entries without a getenv in csrc: {stale}"
     missing = sorted(names - forced - set(needs_no_variant_test))
     assert not missing, f"kernel switches no test forces: {missing}"
+
+
+def test_every_included_header_is_a_build_dependency():
+    """build() decides what to recompile from a digest of its sources and build.headers(): a header that a translation unit
+    includes but the list misses would never trigger a rebuild.  Every #include "x.h" in csrc/* must resolve to a listed file."""
+    import re
+    from boosted_detr_amd import build
+    listed = {p.resolve() for p in build.headers()}
+    assert all(p.is_file() for p in listed), sorted(str(p) for p in listed if not p.is_file())
+    includes = []
+    for path in sorted(build.CSRC.iterdir()):
+        if path.suffix in (".h", ".hip", ".cpp"):
+            includes += [(path.name, inc) for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', path.read_text(), flags=re.M)]
+    assert len(includes) >= len(build.SOURCES), includes         # the scan itself still finds the includes
+    missing = sorted((src, inc) for src, inc in includes if (build.CSRC / inc).resolve() not in listed)
+    assert not missing, f"headers included but not in build.headers(): {missing}"
