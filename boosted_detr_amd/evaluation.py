@@ -29,6 +29,31 @@ import numpy as np
 KEEP_BIT = 0x8000
 MAX_THRESHOLDS = 15
 RECALL_POINTS = np.linspace(0.0, 1.0, 101)
+_BIT_OF_THRESHOLD = np.arange(MAX_THRESHOLDS)[:, None]
+_EPS = np.spacing(1.0)
+
+
+def precision_recall(scores, tp_bits, ig_bits, npig: int, T: int):
+    """One class's curve, for both protocols: its detections (the caller has applied any rank cut) sorted by descending score with
+    a stable sort, cumulative TP / FP at each of the T thresholds (bit t of tp_bits; a detection whose bit t of ig_bits is set is
+    neither - ig_bits None: none is), the right-to-left envelope, the precision at the 101 recall points.  npig: the class's
+    non-ignored ground truths, > 0.  Returns (precision [T,R], recall [T])."""
+    rank = np.argsort(-scores.astype(np.float64), kind="stable")
+    shifts = _BIT_OF_THRESHOLD[:T]
+    tp = ((tp_bits[rank][None, :] >> shifts) & 1).astype(np.float64)             # [T, D]
+    counted = tp if ig_bits is None else np.maximum(tp, ((ig_bits[rank][None, :] >> shifts) & 1).astype(np.float64))
+    tp_sum, fp_sum = np.cumsum(tp, axis=1), np.cumsum(1.0 - counted, axis=1)    # fp = ~tp & ~ig
+    nd = rank.size
+    rc = tp_sum / float(npig)
+    pr = tp_sum / (fp_sum + tp_sum + _EPS)
+    pr = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]                     # the right-to-left monotone envelope
+    precision = np.zeros((T, RECALL_POINTS.size))
+    for t in range(T):
+        at = np.searchsorted(rc[t], RECALL_POINTS, side="left")
+        inside = at < nd
+        row = precision[t]                                                       # (a 1-D boolean store: the fast path)
+        row[inside] = pr[t, at[inside]]
+    return precision, (rc[:, -1] if nd else np.zeros(T))
 
 
 def accumulate(records: Sequence[tuple], gt_count, iou_thresholds) -> Dict[str, object]:
@@ -55,27 +80,11 @@ def accumulate(records: Sequence[tuple], gt_count, iou_thresholds) -> Dict[str, 
     labels = np.concatenate(labels) if labels else np.zeros(0, np.int64)
     bits = np.concatenate(bits) if bits else np.zeros(0, np.int64)
 
-    R = RECALL_POINTS.size
-    precision = np.full((T, R, C), -1.0)
+    precision = np.full((T, RECALL_POINTS.size, C), -1.0)
     recall = np.full((T, C), -1.0)
-    eps = np.spacing(1.0)
     for c in np.flatnonzero(gt_count > 0):
         sel = labels == c
-        rank = np.argsort(-scores[sel].astype(np.float64), kind="stable")
-        b = bits[sel][rank]
-        tp = ((b[None, :] >> np.arange(T)[:, None]) & 1).astype(np.float64)       # [T, D]
-        tp_sum, fp_sum = np.cumsum(tp, axis=1), np.cumsum(1.0 - tp, axis=1)
-        nd = b.size
-        rc = tp_sum / float(gt_count[c])
-        pr = tp_sum / (tp_sum + fp_sum + eps)
-        pr = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]                  # the right-to-left monotone envelope
-        recall[:, c] = rc[:, -1] if nd else 0.0
-        for t in range(T):
-            at = np.searchsorted(rc[t], RECALL_POINTS, side="left")
-            q = np.zeros(R)
-            inside = at < nd
-            q[inside] = pr[t, at[inside]]
-            precision[t, :, c] = q
+        precision[:, :, c], recall[:, c] = precision_recall(scores[sel], bits[sel], None, gt_count[c], T)
     valid = gt_count > 0
 
     def mean_ap(rows) -> float:
@@ -96,7 +105,70 @@ def accumulate(records: Sequence[tuple], gt_count, iou_thresholds) -> Dict[str, 
             "num_images": int(sum(np.asarray(rec[0]).shape[0] for rec in records)), "gt_count": gt_count.copy()}
 
 
-class DetectionEvaluator:
+def _words(t):
+    """A kept device tensor as flat int32 words: float32 by its bit pattern, int32 as it is, 16-bit integers widened."""
+    import torch
+    return (t.view(torch.int32) if t.dtype == torch.float32 else t.to(torch.int32)).reshape(-1)
+
+
+def _from_words(words: np.ndarray, t) -> np.ndarray:
+    """The host copy of _words(t) in t's shape: float32 by the bit pattern, int32 as it is, a 16-bit tensor as the uint16 pattern."""
+    words = words.reshape(tuple(t.shape))
+    if t.dtype.is_floating_point:
+        return words.view(np.float32)
+    return words if t.element_size() == 4 else (words & 0xFFFF).astype(np.uint16)
+
+
+class _KeptRecords:
+    """What every evaluator keeps and how it reaches the host.  ``_kept`` holds one record per batch, a tuple of device tensors
+    (float32, int32 or 16-bit integers); ``_gt_shape()`` is the shape of the running ground-truth counts ``_gt_count`` that follow
+    them (None: there are none).  ``result`` makes ONE device-to-host copy - every record field by field, then the counts, as
+    int32 words in one torch.cat - and hands ``result_from`` the records as host arrays (and the counts as int64); ``results``
+    does that for several evaluators with one copy between them."""
+
+    def _gt_shape(self) -> Optional[tuple]:
+        return None
+
+    def _device_parts(self) -> list:
+        parts = [_words(t) for rec in self._kept for t in rec]
+        return parts if self._gt_shape() is None else parts + [self._gt_count.reshape(-1)]
+
+    def _from_flat(self, flat: np.ndarray, o: int = 0):
+        """The host copy of _device_parts(), concatenated, from word o on -> (result_from's arguments, the word after them)."""
+        records = []
+        for rec in self._kept:
+            host = []
+            for t in rec:
+                host.append(_from_words(flat[o:o + t.numel()], t))
+                o += t.numel()
+            records.append(tuple(host))
+        shape = self._gt_shape()
+        if shape is None:
+            return (records,), o
+        n = int(np.prod(shape))
+        return (records, flat[o:o + n].astype(np.int64).reshape(shape)), o + n
+
+    def _nothing(self) -> tuple:
+        """result_from's arguments of an evaluator that saw no batch."""
+        shape = self._gt_shape()
+        return ([],) if shape is None else ([], np.zeros(shape, np.int64))
+
+    def _host_args(self) -> tuple:
+        import torch
+        if not self._kept:
+            return self._nothing()
+        return self._from_flat(torch.cat(self._device_parts()).cpu().numpy())[0]
+
+    def result(self) -> Dict[str, object]:
+        return self.result_from(*self._host_args())
+
+
+def _check_classes(num_classes: int, cat_pred) -> None:
+    if cat_pred.shape[-1] != num_classes:
+        raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {num_classes}")
+
+
+class DetectionEvaluator(_KeptRecords):
     """Running COCO-style box AP.  ``update`` launches bdetr_det_postprocess and bdetr_det_match on the current stream and keeps the
     per-batch score / label / tp_bits / order tensors and the running per-class ground-truth count in HBM; it reads nothing back.
     ``result`` makes one device-to-host copy and accumulates on the host (a few bytes per detection, once per evaluation)."""
@@ -120,12 +192,9 @@ class DetectionEvaluator:
     def update(self, cat_pred, box_pred, cat_ids, bbox, num_objects) -> None:
         """cat_pred [B,N,C] probabilities and box_pred [B,N,4] from ``Model.predict_raw``; cat_ids int32 [B,M], bbox f32 [B,M,4]
         (normalised COCO [x,y,w,h], -10 padding) and num_objects int32 [B] as ``_prepare_targets`` returns them.  All in HBM."""
-        import torch
         from . import kernels as K
-        if cat_pred.shape[-1] != self.num_classes:
-            raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {self.num_classes}")
-        if self._gt_count is None:
-            self._gt_count = torch.zeros(self.num_classes, dtype=torch.int32, device=cat_pred.device)
+        _check_classes(self.num_classes, cat_pred)
+        self._count_on(cat_pred.device)
         score, label = K.det_postprocess(cat_pred.contiguous())
         order, tp_bits, matched = K.det_match(score, label, box_pred.contiguous(), cat_ids.contiguous(), bbox.contiguous(),
                                               num_objects.reshape(-1).contiguous(), self.iou_thresholds, self.num_classes, self.max_dets,
@@ -133,54 +202,28 @@ class DetectionEvaluator:
         self._kept.append((score, label, tp_bits, order))
         self.last_matched_gt = matched
 
-    def _device_parts(self) -> list:
-        """What result() needs, as flat int32 device tensors: per batch score (bit pattern), label, tp_bits, order; then gt_count."""
+    def _gt_shape(self) -> tuple:
+        return (self.num_classes,)
+
+    def _count_on(self, device) -> None:
+        """The running ground-truth counts, int32 in HBM, allocated by the first update."""
         import torch
-        parts = []
-        for score, label, tp_bits, order in self._kept:
-            parts += [score.view(torch.int32).reshape(-1), label.reshape(-1), tp_bits.to(torch.int32).reshape(-1), order.reshape(-1)]
-        parts.append(self._gt_count)
-        return parts
-
-    def _from_flat(self, flat: np.ndarray):
-        """The host copy of _device_parts(), concatenated -> (records, gt_count) for accumulate."""
-        records, o = [], 0
-        for score, *_ in self._kept:
-            shape, n = tuple(score.shape), score.numel()
-            s, l, t, r = (flat[o + k * n: o + (k + 1) * n].reshape(shape) for k in range(4))
-            records.append((s.view(np.float32), l, (t & 0xFFFF).astype(np.uint16), r))
-            o += 4 * n
-        return records, flat[o:o + self.num_classes].astype(np.int64)
-
-    def _flat_size(self) -> int:
-        """Words in _device_parts()."""
-        return sum(4 * score.numel() for score, *_ in self._kept) + self.num_classes
-
-    def _nothing(self):
-        """(records, gt_count) of an evaluator that saw no batch."""
-        return [], np.zeros(self.num_classes, np.int64)
+        if self._gt_count is None:
+            self._gt_count = torch.zeros(*self._gt_shape(), dtype=torch.int32, device=device)
 
     def _to_host(self):
-        """One device-to-host copy: every kept tensor and the ground-truth counts, packed as int32 words."""
-        import torch
-        if not self._kept:
-            return self._nothing()
-        return self._from_flat(torch.cat(self._device_parts()).cpu().numpy())
+        """One device-to-host copy -> (records, gt_count)."""
+        return self._host_args()
 
     def result_from(self, records: Sequence[tuple], gt_count) -> Dict[str, object]:
         """The host half alone: accumulate over records as the kernels leave them (see ``accumulate``)."""
         return accumulate(records, gt_count, self.iou_thresholds)
 
-    def result(self) -> Dict[str, object]:
-        records, gt_count = self._to_host()
-        return self.result_from(records, gt_count)
-
 
 def grid_mask_operands(num_classes: int, cat_pred, mask_logits, cat_ids, masks):
     """The shape checks of a grid-mask update() (MaskEvaluator, CocoMaskEvaluator).  Returns (B, N, M, mask_logits [B,N,P],
     masks [B,M,P])."""
-    if cat_pred.shape[-1] != num_classes:
-        raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {num_classes}")
+    _check_classes(num_classes, cat_pred)
     if cat_pred.dim() != 3 or mask_logits.dim() not in (3, 4) or masks.dim() not in (3, 4) or cat_ids.dim() != 2:
         raise ValueError("expected cat_pred [B,N,C], mask_logits [B,N,P], cat_ids [B,M], masks [B,M,P]")
     B, N = cat_pred.shape[:2]
@@ -203,11 +246,9 @@ class MaskEvaluator(DetectionEvaluator):
         """cat_pred [B,N,C] probabilities from ``Model.predict_raw``; mask_logits f32 [B,N,P] (or [B,N,h,w]) from ``panoptic_masks``;
         cat_ids int32 [B,M]; masks f32 [B,M,P] (or [B,M,h,w]) targets in [0,1], row m belonging to cat_ids row m; num_objects
         int32 [B].  All in HBM."""
-        import torch
         from . import kernels as K
         B, N, M, mask_logits, masks = grid_mask_operands(self.num_classes, cat_pred, mask_logits, cat_ids, masks)
-        if self._gt_count is None:
-            self._gt_count = torch.zeros(self.num_classes, dtype=torch.int32, device=cat_pred.device)
+        self._count_on(cat_pred.device)
         score, label = K.det_postprocess(cat_pred.contiguous())
         det_bits, det_area = K.mask_binarize(mask_logits.contiguous(), self.LOGIT_THRESHOLD)
         gt_bits, gt_area = K.mask_binarize(masks.contiguous(), self.TARGET_THRESHOLD)
@@ -259,30 +300,13 @@ def accumulate_pair(lineup: _Lineup, npig, T: int, a: int, max_det: int):
     """COCOeval.accumulate for one area range and one max_det.  npig: the range's non-ignored ground truths per class [C].
     Returns (precision [T,R,C], recall [T,C]); -1 for a class with npig = 0."""
     npig = np.asarray(npig, np.int64).reshape(-1)
-    C, R = npig.size, RECALL_POINTS.size
-    precision = np.full((T, R, C), -1.0)
+    C = npig.size
+    precision = np.full((T, RECALL_POINTS.size, C), -1.0)
     recall = np.full((T, C), -1.0)
-    eps = np.spacing(1.0)
     within = lineup.ranks < max_det
-    shifts = np.arange(T)[:, None]
     for c in np.flatnonzero(npig > 0):
         sel = within & (lineup.labels == c)
-        rank = np.argsort(-lineup.scores[sel].astype(np.float64), kind="stable")
-        tpb, igb = lineup.tp[a][sel][rank], lineup.ig[a][sel][rank]
-        tp = ((tpb[None, :] >> shifts) & 1).astype(np.float64)                    # [T, D]
-        fp = 1.0 - np.maximum(tp, ((igb[None, :] >> shifts) & 1).astype(np.float64))      # fp = ~tp & ~ig
-        tp_sum, fp_sum = np.cumsum(tp, axis=1), np.cumsum(fp, axis=1)
-        nd = tpb.size
-        rc = tp_sum / float(npig[c])
-        pr = tp_sum / (fp_sum + tp_sum + eps)
-        pr = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]                  # the right-to-left monotone envelope
-        recall[:, c] = rc[:, -1] if nd else 0.0
-        for t in range(T):
-            at = np.searchsorted(rc[t], RECALL_POINTS, side="left")
-            q = np.zeros(R)
-            inside = at < nd
-            q[inside] = pr[t, at[inside]]
-            precision[t, :, c] = q
+        precision[:, :, c], recall[:, c] = precision_recall(lineup.scores[sel], lineup.tp[a][sel], lineup.ig[a][sel], npig[c], T)
     return precision, recall
 
 
@@ -321,14 +345,18 @@ def accumulate_coco(records: Sequence[tuple], gt_count, iou_thresholds, max_dets
     return res
 
 
+def crowd_flags(iscrowd, B: int, M: int, device):
+    """iscrowd [B,M] (non-zero = crowd region; host or device) -> uint8 [B,M] in HBM."""
+    import torch
+    return (torch.as_tensor(iscrowd).to(device) != 0).to(torch.uint8).reshape(B, M).contiguous()
+
+
 class CocoEvaluator(DetectionEvaluator):
     """Running box AP by the full COCO protocol: the 12 numbers of pycocotools' summarize.  ``update`` launches
     bdetr_det_postprocess and bdetr_det_match_coco (K16) on the current stream and reads nothing back; per batch it keeps score /
     label / class_rank / order [B,N] and tp_bits / ig_bits [A,B,N] in HBM.  ``result`` makes one device-to-host copy.
     area_ranges: a dict name -> (lo, hi) in pixels, the first entry being the base range (or a sequence of pairs, named all / small /
     medium / large by position); max_dets: ascending, the last one is the per-class truncation."""
-
-    WORDS_PER_DETECTION = 4          # score, label, class_rank, order; tp_bits and ig_bits add 2 A
 
     def __init__(self, num_classes: int, iou_thresholds=None, max_dets=(1, 10, 100), area_ranges=None):
         md = sorted({int(m) for m in (max_dets if np.ndim(max_dets) else [max_dets])})
@@ -351,14 +379,16 @@ class CocoEvaluator(DetectionEvaluator):
         super().reset()
         self._ranges_dev = None               # float64 [A,2] in HBM, allocated by the first update
 
+    def _gt_shape(self) -> tuple:
+        return (len(self.area_names), self.num_classes)
+
     def _coco_operands(self, device, B: int, M: int, iscrowd, area, image_hw):
         """iscrowd -> uint8 [B,M] (None: no crowd), area -> f32 [B,M] or None, image_hw -> int32 [B,2] ((H, W): every image's), all in HBM."""
         import torch
-        if self._gt_count is None:
-            self._gt_count = torch.zeros(len(self.area_names), self.num_classes, dtype=torch.int32, device=device)
+        self._count_on(device)
+        if self._ranges_dev is None:
             self._ranges_dev = torch.from_numpy(self.area_ranges).to(device)
-        crowd = torch.zeros(B, M, dtype=torch.uint8, device=device) if iscrowd is None \
-            else (torch.as_tensor(iscrowd).to(device) != 0).to(torch.uint8).reshape(B, M).contiguous()
+        crowd = torch.zeros(B, M, dtype=torch.uint8, device=device) if iscrowd is None else crowd_flags(iscrowd, B, M, device)
         if area is not None:
             area = torch.as_tensor(area).to(device=device, dtype=torch.float32).reshape(B, M).contiguous()
         if image_hw is None:
@@ -371,8 +401,7 @@ class CocoEvaluator(DetectionEvaluator):
         """As DetectionEvaluator.update, plus iscrowd [B,M] (non-zero = crowd region; None: none), area f32 [B,M] in pixels of the
         original image (None: from the box) and image_hw, the original (height, width): one pair for every image or int32 [B,2]."""
         from . import kernels as K
-        if cat_pred.shape[-1] != self.num_classes:
-            raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {self.num_classes}")
+        _check_classes(self.num_classes, cat_pred)
         B, M = cat_ids.shape
         crowd, area, hw = self._coco_operands(cat_pred.device, B, M, iscrowd, area, image_hw)
         score, label = K.det_postprocess(cat_pred.contiguous())
@@ -381,35 +410,6 @@ class CocoEvaluator(DetectionEvaluator):
             self._ranges_dev, self.iou_thresholds, self.num_classes, self.max_dets[-1], self._gt_count)
         self._kept.append((score, label, class_rank, tp_bits, ig_bits, order))
         self.last_matched_gt = matched
-
-    def _device_parts(self) -> list:
-        """Flat int32 device tensors: per batch score (bit pattern), label, class_rank, order, tp_bits, ig_bits; then gt_count [A,C]."""
-        import torch
-        parts = []
-        for score, label, class_rank, tp_bits, ig_bits, order in self._kept:
-            parts += [score.view(torch.int32).reshape(-1), label.reshape(-1), class_rank.reshape(-1), order.reshape(-1),
-                      tp_bits.to(torch.int32).reshape(-1), ig_bits.to(torch.int32).reshape(-1)]
-        parts.append(self._gt_count.reshape(-1))
-        return parts
-
-    def _flat_size(self) -> int:
-        A = len(self.area_names)
-        return sum((self.WORDS_PER_DETECTION + 2 * A) * score.numel() for score, *_ in self._kept) + A * self.num_classes
-
-    def _nothing(self):
-        return [], np.zeros((len(self.area_names), self.num_classes), np.int64)
-
-    def _from_flat(self, flat: np.ndarray):
-        A = len(self.area_names)
-        records, o = [], 0
-        for score, *_ in self._kept:
-            shape, n = tuple(score.shape), score.numel()
-            s, l, c, r = (flat[o + k * n: o + (k + 1) * n].reshape(shape) for k in range(4))
-            o += 4 * n
-            t, g = (flat[o + k * A * n: o + (k + 1) * A * n].reshape((A,) + shape) for k in range(2))
-            o += 2 * A * n
-            records.append((s.view(np.float32), l, c, (t & 0xFFFF).astype(np.uint16), (g & 0xFFFF).astype(np.uint16), r))
-        return records, flat[o:o + A * self.num_classes].astype(np.int64).reshape(A, self.num_classes)
 
     def result_from(self, records: Sequence[tuple], gt_count) -> Dict[str, object]:
         return accumulate_coco(records, gt_count, self.iou_thresholds, self.max_dets, self.area_names)
@@ -461,6 +461,14 @@ def host_image_hw(height, width) -> np.ndarray:
     return np.stack(parts, axis=1).astype(np.int32)
 
 
+def check_max_mask_bytes(max_mask_bytes: Optional[int]) -> int:
+    """An evaluator's max_mask_bytes argument (None: CocoImageMaskEvaluator.DEFAULT_MAX_MASK_BYTES) -> the budget in bytes."""
+    max_mask_bytes = CocoImageMaskEvaluator.DEFAULT_MAX_MASK_BYTES if max_mask_bytes is None else int(max_mask_bytes)
+    if max_mask_bytes < 1:
+        raise ValueError("max_mask_bytes must be positive")
+    return max_mask_bytes
+
+
 def check_image_mask_batch(segments, image_hw_host, N: int, max_mask_bytes: int):
     """Every refusal of an image-resolution update() that needs no device (CocoImageMaskEvaluator, PanopticEvaluator): the segments
     pack, the images' sizes, that every segmented object was annotated on its image's own (height, width), and the byte budget
@@ -498,8 +506,7 @@ def check_image_mask_batch(segments, image_hw_host, N: int, max_mask_bytes: int)
 def image_mask_operands(evaluator, cat_pred, mask_logits, cat_ids, segments, image_hw_host):
     """The checks of an image-resolution update() (CocoImageMaskEvaluator, PanopticEvaluator): the operands' shapes with the square
     grid G, then the evaluator's check_batch, then that the pack has cat_ids' rows.  Returns (B, N, M, G, image_hw int32 [B,2], Hm, Wm)."""
-    if cat_pred.shape[-1] != evaluator.num_classes:
-        raise ValueError(f"cat_pred has {cat_pred.shape[-1]} classes, the evaluator was built for {evaluator.num_classes}")
+    _check_classes(evaluator.num_classes, cat_pred)
     if cat_pred.dim() != 3 or mask_logits.dim() not in (3, 4) or cat_ids.dim() != 2:
         raise ValueError("expected cat_pred [B,N,C], mask_logits [B,N,G,G], cat_ids [B,M]")
     B, N = cat_pred.shape[:2]
@@ -530,9 +537,7 @@ class CocoImageMaskEvaluator(CocoEvaluator):
 
     def __init__(self, num_classes: int, iou_thresholds=None, max_dets=(1, 10, 100), area_ranges=None, max_mask_bytes: Optional[int] = None):
         super().__init__(num_classes, iou_thresholds, max_dets, area_ranges)
-        self.max_mask_bytes = self.DEFAULT_MAX_MASK_BYTES if max_mask_bytes is None else int(max_mask_bytes)
-        if self.max_mask_bytes < 1:
-            raise ValueError("max_mask_bytes must be positive")
+        self.max_mask_bytes = check_max_mask_bytes(max_mask_bytes)
 
     def check_batch(self, segments, image_hw_host, N: int):
         """Every refusal of update() that needs no device: the segments pack, the images' sizes, that every segmented object was
@@ -617,7 +622,23 @@ def accumulate_pq(records: Sequence[tuple], num_classes: int, stuff_classes=()) 
     return out
 
 
-class PanopticEvaluator:
+def check_min_area(min_area) -> int:
+    if int(min_area) != min_area or int(min_area) < 0:
+        raise ValueError(f"min_area must be a non-negative integer, got {min_area}")
+    return int(min_area)
+
+
+def stuff_flags(stuff_classes, num_classes: int, device):
+    """The checked stuff class ids -> uint8 [C] in HBM, 1 for a stuff class; None when there is none."""
+    import torch
+    if not stuff_classes:
+        return None
+    flags = np.zeros(num_classes, np.uint8)
+    flags[list(stuff_classes)] = 1
+    return torch.from_numpy(flags).to(device)
+
+
+class PanopticEvaluator(_KeptRecords):
     """Running panoptic quality (PQ / SQ / RQ of the COCO panoptic task) at image resolution.  ``update`` chains, on the current
     stream: the ground truths' exact source bitmasks (bdetr_mask_source_bits, K20) made exclusive in place
     (bdetr_panoptic_gt_exclusive, K25), bdetr_det_postprocess, the selection of the queries that become segments
@@ -639,13 +660,9 @@ class PanopticEvaluator:
             raise ValueError("num_classes counts <PAD> and <OOV>: at least 3")
         if not 0.0 <= float(score_threshold) < 1.0:
             raise ValueError(f"score_threshold must be in [0, 1), got {score_threshold}")
-        if int(min_area) != min_area or int(min_area) < 0:
-            raise ValueError(f"min_area must be a non-negative integer, got {min_area}")
-        self.num_classes, self.score_threshold, self.min_area = int(num_classes), float(score_threshold), int(min_area)
+        self.num_classes, self.score_threshold, self.min_area = int(num_classes), float(score_threshold), check_min_area(min_area)
         self.stuff_classes = self.check_stuff_classes(stuff_classes, self.num_classes)
-        self.max_mask_bytes = self.DEFAULT_MAX_MASK_BYTES if max_mask_bytes is None else int(max_mask_bytes)
-        if self.max_mask_bytes < 1:
-            raise ValueError("max_mask_bytes must be positive")
+        self.max_mask_bytes = check_max_mask_bytes(max_mask_bytes)
         self.reset()
 
     @staticmethod
@@ -677,11 +694,9 @@ class PanopticEvaluator:
         device = cat_pred.device
         gt_bits, _ = K.mask_source_bits(segments["items"], segments["item_off"], segments["kind"], segments["hw"], Hm, Wm, device=device)
         hw_dev = torch.from_numpy(hw).to(device)
-        crowd = None if iscrowd is None else (torch.as_tensor(iscrowd).to(device) != 0).to(torch.uint8).reshape(B, M).contiguous()
-        if self.stuff_classes and self._is_stuff is None:
-            flags = np.zeros(self.num_classes, np.uint8)
-            flags[list(self.stuff_classes)] = 1
-            self._is_stuff = torch.from_numpy(flags).to(device)
+        crowd = None if iscrowd is None else crowd_flags(iscrowd, B, M, device)
+        if self._is_stuff is None:
+            self._is_stuff = stuff_flags(self.stuff_classes, self.num_classes, device)
         num_objects = num_objects.reshape(-1).contiguous()
         gt_label = cat_ids.contiguous()
         gt_pop = K.panoptic_gt_exclusive(gt_bits, gt_label, num_objects, self.num_classes)
@@ -694,52 +709,22 @@ class PanopticEvaluator:
         self._kept.append((gt_state, pred_state, match_inter, match_union, gt_label, label))
         self.last = {"seg_of": seg_of, "pred_pop": pop, "gt_pop": gt_pop, "inter": inter, "score": score}
 
-    # the protocol of evaluation.results(): one copy for several evaluators
-    def _device_parts(self) -> list:
-        return [t.reshape(-1) for rec in self._kept for t in rec]
-
-    def _flat_size(self) -> int:
-        return sum(t.numel() for rec in self._kept for t in rec)
-
-    def _nothing(self):
-        return ([],)
-
-    def _from_flat(self, flat: np.ndarray):
-        records, o = [], 0
-        for rec in self._kept:
-            host = []
-            for t in rec:
-                host.append(flat[o:o + t.numel()].reshape(tuple(t.shape)))
-                o += t.numel()
-            records.append(tuple(host))
-        return (records,)
-
-    def _to_host(self):
-        """One device-to-host copy: every kept tensor, packed as int32 words."""
-        import torch
-        if not self._kept:
-            return []
-        return self._from_flat(torch.cat(self._device_parts()).cpu().numpy())[0]
+    def _to_host(self) -> list:
+        """One device-to-host copy -> the records."""
+        return self._host_args()[0]
 
     def result_from(self, records: Sequence[tuple]) -> Dict[str, object]:
         """The host half alone: accumulate_pq over records as the kernels leave them (host int32 arrays; no device is needed)."""
         return accumulate_pq(records, self.num_classes, self.stuff_classes)
 
-    def result(self) -> Dict[str, object]:
-        return self.result_from(self._to_host())
 
-
-def results(evaluators: Sequence[DetectionEvaluator]) -> List[Dict[str, object]]:
+def results(evaluators: Sequence[_KeptRecords]) -> List[Dict[str, object]]:
     """result() of several evaluators with ONE device-to-host copy between them: every evaluator's kept tensors in one torch.cat."""
     import torch
     live = [ev for ev in evaluators if ev._kept]
     flat = torch.cat([p for ev in live for p in ev._device_parts()]).cpu().numpy() if live else np.zeros(0, np.int32)
     out, o = [], 0
     for ev in evaluators:
-        if not ev._kept:
-            out.append(ev.result_from(*ev._nothing()))
-            continue
-        n = ev._flat_size()
-        out.append(ev.result_from(*ev._from_flat(flat[o:o + n])))
-        o += n
+        args, o = ev._from_flat(flat, o) if ev._kept else (ev._nothing(), o)
+        out.append(ev.result_from(*args))
     return out

@@ -25,6 +25,7 @@ from . import _lib
 from . import engine
 from . import kernels as K
 from . import ops
+from .inference import Inference
 from .engine import Layer, Tape, Variable, bump_weights_version, device, join_side_stream, recording, to_device
 
 
@@ -641,7 +642,24 @@ class TensorBoard(Callback):
             f.write(json.dumps({"epoch": epoch, **{k: float(v) for k, v in (logs or {}).items()}}) + "\n")
 
 
-class DetectionAP(Callback):
+class _HeldOutMetric(Callback):
+    """A metric on a held-out set at the end of every `every`-th epoch: ``measure()`` -> the val_ entries that join that epoch's logs
+    and ``history``."""
+
+    def __init__(self, validation_data, every: int, steps: Optional[int], evaluator):
+        self.validation_data, self.every, self.steps, self.evaluator = validation_data, max(1, int(every)), steps, evaluator
+        self.history: List[dict] = []
+
+    def on_epoch_end(self, epoch, logs=None):
+        if (epoch + 1) % self.every:
+            return
+        vals = self.measure()
+        self.history.append({"epoch": epoch, **vals})
+        if logs is not None:
+            logs.update(vals)
+
+
+class DetectionAP(_HeldOutMetric):
     """COCO-style box AP on a held-out set at the end of an epoch: Model.evaluate over `validation_data` (at most `steps` batches),
     every `every` epochs; adds val_AP, val_AP50, val_AP75 and val_AR to that epoch's logs.  Unlike fit(validation_data=...), whose
     test_step trains (the reference's quirk), this leaves the model as it found it.  Put it before the callbacks that write the logs.
@@ -651,38 +669,21 @@ class DetectionAP(Callback):
 
     def __init__(self, validation_data, every: int = 1, steps: Optional[int] = None, evaluator=None, iou_types=("bbox",), mask_evaluator=None,
                  coco: bool = False, mask_resolution: str = "grid"):
-        self.validation_data, self.every, self.steps, self.evaluator = validation_data, max(1, int(every)), steps, evaluator
+        super().__init__(validation_data, every, steps, evaluator)
         self.iou_types, self.mask_evaluator, self.coco = Model._check_iou_types(iou_types), mask_evaluator, bool(coco)
         self.mask_resolution = Model._check_mask_resolution(mask_resolution, self.coco)
-        self.history: List[dict] = []
 
-    def on_epoch_end(self, epoch, logs=None):
-        if (epoch + 1) % self.every:
-            return
-        if self.coco:
-            extra = {} if self.mask_resolution == "grid" else {"mask_resolution": self.mask_resolution}
-            res = self.model.evaluate(self.validation_data, steps=self.steps, evaluator=self.evaluator, iou_types=self.iou_types,
-                                      mask_evaluator=self.mask_evaluator, coco=True, **extra)
-            prefixes = [p for p, t in (("", "bbox"), ("mask_", "segm")) if t in self.iou_types]
-            vals = {f"val_{k}": float(res[k]) for p in prefixes for k in res
-                    if k.startswith(p) and (k[len(p):] in ("AP", "AP50", "AP75", "AR") or k[len(p):].startswith(("AP_", "AR_")))}
-            self.history.append({"epoch": epoch, **vals})
-            if logs is not None:
-                logs.update(vals)
-            return
-        if self.iou_types == ("bbox",):
-            res = self.model.evaluate(self.validation_data, steps=self.steps, evaluator=self.evaluator)
-        else:
-            res = self.model.evaluate(self.validation_data, steps=self.steps, evaluator=self.evaluator, iou_types=self.iou_types,
-                                      mask_evaluator=self.mask_evaluator)
+    def measure(self) -> Dict[str, float]:
+        # (the short protocol's box-only call never named a mask evaluator: its class would select the protocol)
+        mask_evaluator = self.mask_evaluator if self.coco or "segm" in self.iou_types else None
+        res = self.model.evaluate(self.validation_data, steps=self.steps, evaluator=self.evaluator, iou_types=self.iou_types,
+                                  mask_evaluator=mask_evaluator, coco=self.coco, mask_resolution=self.mask_resolution)
         prefixes = [p for p, t in (("", "bbox"), ("mask_", "segm")) if t in self.iou_types]
-        vals = {f"val_{p}{k}": float(res[p + k]) for p in prefixes for k in ("AP", "AP50", "AP75", "AR")}
-        self.history.append({"epoch": epoch, **vals})
-        if logs is not None:
-            logs.update(vals)
+        return {f"val_{k}": float(res[k]) for p in prefixes for k in res
+                if k.startswith(p) and (k[len(p):] in ("AP", "AP50", "AP75", "AR") or k[len(p):].startswith(("AP_", "AR_")))}
 
 
-class PanopticQuality(Callback):
+class PanopticQuality(_HeldOutMetric):
     """Panoptic quality on a held-out set at the end of an epoch: Model.evaluate_panoptic over `validation_data` (at most `steps`
     batches), every `every` epochs; adds val_PQ, val_SQ and val_RQ to that epoch's logs.  Like DetectionAP it leaves the model as
     it found it; put it before the callbacks that write the logs.  evaluator / score_threshold / min_area / stuff_classes: as
@@ -690,19 +691,13 @@ class PanopticQuality(Callback):
 
     def __init__(self, validation_data, every: int = 1, steps: Optional[int] = None, evaluator=None, score_threshold: float = 0.85,
                  min_area: int = 5, stuff_classes=()):
-        self.validation_data, self.every, self.steps, self.evaluator = validation_data, max(1, int(every)), steps, evaluator
+        super().__init__(validation_data, every, steps, evaluator)
         self.score_threshold, self.min_area, self.stuff_classes = float(score_threshold), int(min_area), tuple(stuff_classes)
-        self.history: List[dict] = []
 
-    def on_epoch_end(self, epoch, logs=None):
-        if (epoch + 1) % self.every:
-            return
+    def measure(self) -> Dict[str, float]:
         res = self.model.evaluate_panoptic(self.validation_data, steps=self.steps, evaluator=self.evaluator, score_threshold=self.score_threshold,
                                            min_area=self.min_area, stuff_classes=self.stuff_classes)
-        vals = {f"val_{k}": float(res[k]) for k in ("PQ", "SQ", "RQ")}
-        self.history.append({"epoch": epoch, **vals})
-        if logs is not None:
-            logs.update(vals)
+        return {f"val_{k}": float(res[k]) for k in ("PQ", "SQ", "RQ")}
 
 
 def latest_checkpoint(checkpoint_dir: str) -> Optional[str]:
@@ -944,7 +939,7 @@ def _forwarded(obj: str, name: str) -> property:
 # ----------------------------------------------------------------------------------------
 # Model
 # ----------------------------------------------------------------------------------------
-class Model(Layer):
+class Model(Layer, Inference):
     def __init__(self, name=None, **kwargs):
         super().__init__(name=name, **kwargs)
         self.optimizer: Optional[Optimizer] = None
@@ -1252,306 +1247,6 @@ class Model(Layer):
 
     def test_step(self, data):
         return self.train_step(data)        # model.py:235-236: validation also trains (quirk kept)
-
-    # -- inference and evaluation ------------------------------------------------------------
-    def predict_raw(self, inputs: dict) -> List[torch.Tensor]:
-        """[cat_preds [B,N,C], attribute_preds [B,N,A], box_preds [B,N,4]] of an inference-mode forward pass, left in HBM (call(training=
-        False) decodes them to strings on the host).  Needs inputs["image"] only."""
-        return self(inputs, training=False, raw=True)
-
-    def detections(self, inputs: dict) -> Dict[str, torch.Tensor]:
-        """Every query as a detection, in HBM: scores f32 [B,N] and labels int32 [B,N] (the most probable class among the vocabulary's,
-        ids >= 2: never <PAD> or <OOV>), boxes f32 [B,N,4] normalised COCO [x,y,w,h]."""
-        cat_preds, _, box_preds = self.predict_raw(inputs)
-        scores, labels = K.det_postprocess(cat_preds.contiguous())
-        return {"scores": scores, "labels": labels, "boxes": box_preds}
-
-    IOU_TYPES = ("bbox", "segm")
-
-    @classmethod
-    def _check_iou_types(cls, iou_types) -> tuple:
-        types = (iou_types,) if isinstance(iou_types, str) else tuple(iou_types)
-        bad = [t for t in types if t not in cls.IOU_TYPES]
-        if bad or not types:
-            raise ValueError(f"iou_types must name one or both of {cls.IOU_TYPES}, got {iou_types!r}")
-        return tuple(t for t in cls.IOU_TYPES if t in types)
-
-    MASK_RESOLUTIONS = ("grid", "image")
-
-    @classmethod
-    def _check_mask_resolution(cls, mask_resolution, coco: bool) -> str:
-        if mask_resolution not in cls.MASK_RESOLUTIONS:
-            raise ValueError(f"mask_resolution must be one of {cls.MASK_RESOLUTIONS}, got {mask_resolution!r}")
-        if mask_resolution == "image" and not coco:
-            raise ValueError('mask_resolution="image" needs coco=True: the short protocol scores masks on the grid only')
-        return mask_resolution
-
-    @staticmethod
-    def _image_mask_fields(batch: dict):
-        """(segments, image_hw int32 [B,2] on the HOST) of a batch for the image-resolution path; a ValueError says what is missing."""
-        from . import evaluation
-        segments = batch.get("segments")
-        if segments is None:
-            raise ValueError('mask_resolution="image" needs every batch\'s \'segments\', the host pack of pipeline.pad_annotations(..., '
-                             "with_masks=True); dense 'masks' are grid data and are not enough")
-        return segments, evaluation.host_image_hw(batch.get("height"), batch.get("width"))
-
-    def _require_panoptic_head(self) -> None:
-        """Raises unless the model can produce masks (DETR with a panoptic head overrides this)."""
-        raise RuntimeError(f"{type(self).__name__} has no mask head: iou_types with 'segm' and segmentations() need a DETR built with "
-                           "with_panoptic_head=True or train_panoptic_head=True")
-
-    def segmentations(self, inputs: dict, resolution: str = "grid") -> Dict[str, torch.Tensor]:
-        """detections(inputs) plus every query's mask, in HBM: mask_logits f32 [B,N,23,23] from the panoptic head and masks int64
-        [B,N,W], the logits cut at 0 (sigmoid > 0.5) and packed 64 pixels to a word, row-major (bit p mod 64 of word p div 64;
-        W = ceil(529/64) = 9).  Afterwards panoptic_masks() answers for this call.
-        resolution="image": also image_masks int64 [B,N,Hm,Wm], the logits upsampled to each image's own height x width and cut at 0
-        (include/bdetr.h, K19: Hm = max height, Wm = ceil(max width / 64), pixel (x, y) is bit x mod 64 of word [y, x div 64], zero
-        outside the image), image_mask_area int32 [B,N], their pixel counts, and image_hw int32 [B,2].  It needs inputs["height"] and
-        inputs["width"] as host arrays or sequences."""
-        from .panoptic_neck import MASK_GRID
-        if resolution not in self.MASK_RESOLUTIONS:
-            raise ValueError(f"resolution must be one of {self.MASK_RESOLUTIONS}, got {resolution!r}")
-        self._require_panoptic_head()
-        if resolution == "image":
-            from . import evaluation
-            hw = evaluation.host_image_hw(inputs.get("height"), inputs.get("width"))
-            Hm, Wm = K.mask_layout(hw)
-        out = self.detections(inputs)
-        logits = self.panoptic_masks()
-        B, N = logits.shape[:2]
-        bits, _ = K.mask_binarize(logits.contiguous(), 0.0)
-        out.update(mask_logits=logits.reshape(B, N, MASK_GRID, MASK_GRID), masks=bits)
-        if resolution == "image":
-            if hw.shape[0] != B:
-                raise ValueError(f"'height' / 'width' have {hw.shape[0]} entries, the batch has {B} images")
-            from .engine import to_device
-            hw_dev = to_device(hw, torch.int32)
-            image_bits, image_area = K.mask_upsample_bits(out["mask_logits"].contiguous(), hw_dev, Hm, Wm)
-            out.update(image_masks=image_bits, image_mask_area=image_area, image_hw=hw_dev)
-        return out
-
-    def evaluate(self, x: Iterable[dict], steps: Optional[int] = None, evaluator=None, return_dict: bool = True, verbose: int = 0,
-                 iou_types=("bbox",), mask_evaluator=None, coco: bool = False, mask_resolution: str = "grid"):
-        """COCO-style AP over the batches of `x` (dicts as for training: strings or pre-tokenised ids).  Per batch: an inference-mode
-        forward pass and the two kernels of csrc/detmetric.hip, nothing read back; one device-to-host copy at the end (evaluation.py).
-        Changes nothing: weights, moving statistics, optimizer slots and counters, the step seed, captured steps and what
-        panoptic_masks() answers for stay as they were.
-        evaluator: a DetectionEvaluator (other thresholds / max_dets); it is reset first.  Returns its result() dict, or with
-        return_dict=False the list [AP, AP50, AP75, AR].
-        iou_types: "bbox" (box AP, the default), "segm" (mask AP on the panoptic head's 23 x 23 grid) or both.  "segm" needs a DETR
-        with a panoptic head and inputs["masks"] in every batch (as train_panoptic_head does); per batch it adds the head's forward on
-        that same call's features and the kernels of csrc/maskmetric.hip.  The dict gains mask_AP, mask_AP50, mask_AP75, mask_AR and
-        per_class_mask_AP (with "segm" alone it holds those and the counts), the list the four mask numbers after the box ones;
-        still one device-to-host copy.  mask_evaluator: a MaskEvaluator, as `evaluator` is for boxes.
-        coco=True (or a passed CocoEvaluator / CocoMaskEvaluator): the full COCO protocol - crowd regions, area ranges, AR at several
-        max_dets - through the kernels of K16 / K17 instead.  Optional batch keys: iscrowd [B,M] (non-zero: a crowd region, which is
-        ignored rather than matched), area [B,M] in pixels of the original image, height / width [B] the original size; missing keys
-        mean no crowd, the area of the box (or mask) and the model's image_size.  The dict gains AP_small, AP_medium, AP_large, AR_1,
-        AR_10, AR_100, AR_small, AR_medium, AR_large and stats, the 12 numbers in pycocotools' summarize order (with "segm" the
-        mask_ counterparts and mask_stats); return_dict=False returns stats, followed by mask_stats.
-        mask_resolution: "grid" (the default: everything above) or "image", with coco=True only: "segm" is scored at image resolution,
-        as a COCO user compares it - every query's logits upsampled to its image's height x width and cut at 0, every ground truth
-        its exact source bitmask, areas in pixels (evaluation.CocoImageMaskEvaluator; csrc/maskimage.hip, K19-K22).  Every batch
-        then needs 'segments' (pipeline.pad_annotations(with_masks=True); 'masks' are not read) and 'height' / 'width' as HOST arrays
-        (with_eval_fields=True), each segmentation annotated on that size; a batch that lacks them, or whose bitmasks would exceed
-        the evaluator's max_mask_bytes, is a ValueError before anything is launched for it.  Same keys in the result, still one
-        device-to-host copy.  mask_evaluator: then a CocoImageMaskEvaluator."""
-        from . import evaluation
-        from .model import _prepare_masks, _prepare_targets
-        types = self._check_iou_types(iou_types)
-        coco = bool(coco) or isinstance(evaluator, evaluation.CocoEvaluator) or isinstance(mask_evaluator, evaluation.CocoEvaluator)
-        self._check_mask_resolution(mask_resolution, coco)
-        if coco:
-            image_masks = mask_resolution == "image" or isinstance(mask_evaluator, evaluation.CocoImageMaskEvaluator)      # its class selects the path
-            return self._evaluate_coco(x, steps, evaluator, return_dict, verbose, types, mask_evaluator, image_masks)
-        box_ev = mask_ev = None
-        if "bbox" in types:
-            box_ev = evaluator if evaluator is not None else evaluation.DetectionEvaluator(self.num_categories)
-            box_ev.reset()
-        if "segm" in types:
-            self._require_panoptic_head()
-            mask_ev = mask_evaluator if mask_evaluator is not None else evaluation.MaskEvaluator(self.num_categories)
-            mask_ev.reset()
-        keep_panoptic = self._panoptic_inputs
-        t0, n = time.time(), 0
-        try:
-            for step, batch in enumerate(x):
-                if steps is not None and step >= steps:
-                    break
-                cat_ids, _, bbox, num_objects = _prepare_targets(self, batch)
-                masks = _prepare_masks(batch, bbox.shape[0], bbox.shape[1]) if mask_ev is not None else None
-                cat_preds, _, box_preds = self.predict_raw(batch)
-                if box_ev is not None:
-                    box_ev.update(cat_preds, box_preds, cat_ids, bbox, num_objects)
-                if mask_ev is not None:
-                    mask_ev.update(cat_preds, self.panoptic_masks(), cat_ids, masks, num_objects)      # the head on this call's features
-                n += 1
-        finally:
-            self._panoptic_inputs = keep_panoptic      # panoptic_masks() keeps answering for the last call the user made
-        if mask_ev is None:
-            res = box_ev.result()
-        else:
-            parts = evaluation.results([ev for ev in (box_ev, mask_ev) if ev is not None])      # one copy for both
-            mres = parts[-1]
-            res = parts[0] if box_ev is not None else {k: mres[k] for k in ("num_detections", "num_ground_truths", "num_images", "gt_count")}
-            res.update({f"mask_{k}": mres[k] for k in ("AP", "AP50", "AP75", "AR")}, per_class_mask_AP=mres["per_class_AP"])
-        keys = [p + k for p, ev in (("", box_ev), ("mask_", mask_ev)) if ev is not None for k in ("AP", "AP50", "AP75", "AR")]
-        if verbose:
-            print(f"evaluate - {time.time() - t0:.1f}s - {n} steps - " + " - ".join(f"{k}: {res[k]:.4f}" for k in keys))
-        return res if return_dict else [res[k] for k in keys]
-
-    def _coco_fields(self, batch: dict, B: int, M: int):
-        """(iscrowd, area, image_hw) of a batch for the COCO evaluators: the optional keys iscrowd / area [B,M] and height / width [B]."""
-        from .engine import to_device
-
-        def dev(v, dtype):
-            return to_device(v if isinstance(v, torch.Tensor) else np.asarray(v), dtype)
-
-        iscrowd = dev(batch["iscrowd"], torch.int32).reshape(B, M) if batch.get("iscrowd") is not None else None
-        area = dev(batch["area"], torch.float32).reshape(B, M) if batch.get("area") is not None else None
-        if (batch.get("height") is None) != (batch.get("width") is None):
-            raise ValueError("a batch carries both of 'height' and 'width' or neither")
-        if batch.get("height") is not None:
-            hw = torch.stack([dev(batch["height"], torch.int32).reshape(B), dev(batch["width"], torch.int32).reshape(B)], 1).contiguous()
-        else:
-            hw = tuple(int(v) for v in self.image_size[:2])
-        return iscrowd, area, hw
-
-    def _evaluate_coco(self, x, steps, evaluator, return_dict, verbose, types, mask_evaluator, image_masks: bool = False):
-        """evaluate(coco=True): the same loop over CocoEvaluator / CocoMaskEvaluator (image_masks: CocoImageMaskEvaluator)."""
-        from . import evaluation
-        from .model import _prepare_masks, _prepare_targets
-        box_ev = mask_ev = None
-        if "bbox" in types:
-            box_ev = evaluator if evaluator is not None else evaluation.CocoEvaluator(self.num_categories)
-            if not isinstance(box_ev, evaluation.CocoEvaluator):
-                raise ValueError("coco=True needs a CocoEvaluator as evaluator")
-            box_ev.reset()
-        if "segm" in types:
-            self._require_panoptic_head()
-            mask_class = evaluation.CocoImageMaskEvaluator if image_masks else evaluation.CocoMaskEvaluator
-            mask_ev = mask_evaluator if mask_evaluator is not None else mask_class(self.num_categories)
-            if not isinstance(mask_ev, mask_class):
-                raise ValueError(f"coco=True needs a {mask_class.__name__} as mask_evaluator" + (' with mask_resolution="image"' if image_masks else ""))
-            mask_ev.reset()
-        image_masks = image_masks and mask_ev is not None
-        keep_panoptic = self._panoptic_inputs
-        t0, n = time.time(), 0
-        try:
-            for step, batch in enumerate(x):
-                if steps is not None and step >= steps:
-                    break
-                if image_masks:                               # every refusal of this batch before anything is launched for it
-                    segments, hw_host = self._image_mask_fields(batch)
-                    mask_ev.check_batch(segments, hw_host, self.num_object_preds)
-                cat_ids, _, bbox, num_objects = _prepare_targets(self, batch)
-                masks = _prepare_masks(batch, bbox.shape[0], bbox.shape[1]) if mask_ev is not None and not image_masks else None
-                iscrowd, area, hw = self._coco_fields(batch, bbox.shape[0], bbox.shape[1])
-                cat_preds, _, box_preds = self.predict_raw(batch)
-                if box_ev is not None:
-                    box_ev.update(cat_preds, box_preds, cat_ids, bbox, num_objects, iscrowd, area, hw)
-                if image_masks:
-                    mask_ev.update(cat_preds, self.panoptic_masks(), cat_ids, segments, num_objects, hw_host, iscrowd, area)
-                elif mask_ev is not None:
-                    mask_ev.update(cat_preds, self.panoptic_masks(), cat_ids, masks, num_objects, iscrowd, area, hw)
-                n += 1
-        finally:
-            self._panoptic_inputs = keep_panoptic      # panoptic_masks() keeps answering for the last call the user made
-        parts = evaluation.results([ev for ev in (box_ev, mask_ev) if ev is not None])      # one copy for both
-        counts = ("num_detections", "num_ground_truths", "num_images", "gt_count", "gt_count_per_range")
-        if mask_ev is None:
-            res = parts[0]
-        else:
-            mres = parts[-1]
-            res = parts[0] if box_ev is not None else {k: mres[k] for k in counts}
-            res.update({f"mask_{k}": v for k, v in mres.items() if k not in counts and k != "per_class_AP"}, per_class_mask_AP=mres["per_class_AP"])
-        if verbose:
-            keys = [p + k for p, ev in (("", box_ev), ("mask_", mask_ev)) if ev is not None for k in ("AP", "AP50", "AP75", "AR")]
-            print(f"evaluate - {time.time() - t0:.1f}s - {n} steps - " + " - ".join(f"{k}: {res[k]:.4f}" for k in keys))
-        if return_dict:
-            return res
-        return [v for p, ev in (("", box_ev), ("mask_", mask_ev)) if ev is not None for v in res[p + "stats"]]
-
-    def panoptic_segmentation(self, inputs: dict, score_threshold: float = 0.85, min_area: int = 5, stuff_classes=()) -> Dict[str, torch.Tensor]:
-        """One id per pixel, in HBM: the queries with score > score_threshold become segments (the kept queries of a class in
-        stuff_classes are one segment, the lowest of them), and per pixel the segment whose query has the largest positive
-        upsampled logit wins (include/bdetr.h, K23 / K24).  Returns panoptic_ids int16 [B,Hm,64 Wm] (the segment's query index; -1:
-        void, or outside the image; Hm = max height, Wm = ceil(max width / 64)), segment_label int32 [B,N] and segment_score f32
-        [B,N] (every query's; a segment's are those of its query), segment_area int32 [B,N] (pixels; 0 where n is no segment or has
-        fewer than min_area pixels - the pixels of such a segment are -1 in panoptic_ids) and image_hw int32 [B,2].  Needs the
-        panoptic head and inputs["height"] / inputs["width"] as host arrays or sequences.  Afterwards panoptic_masks() answers for
-        this call."""
-        from . import evaluation
-        from .engine import to_device
-        from .panoptic_neck import MASK_GRID
-        self._require_panoptic_head()
-        stuff = evaluation.PanopticEvaluator.check_stuff_classes(stuff_classes, self.num_categories)
-        if int(min_area) != min_area or int(min_area) < 0:
-            raise ValueError(f"min_area must be a non-negative integer, got {min_area}")
-        hw = evaluation.host_image_hw(inputs.get("height"), inputs.get("width"))
-        Hm, Wm = K.mask_layout(hw)
-        cat_preds, _, _ = self.predict_raw(inputs)
-        logits = self.panoptic_masks()
-        B, N = logits.shape[:2]
-        if hw.shape[0] != B:
-            raise ValueError(f"'height' / 'width' have {hw.shape[0]} entries, the batch has {B} images")
-        hw_dev = to_device(hw, torch.int32)
-        is_stuff = None
-        if stuff:
-            flags = np.zeros(self.num_categories, np.uint8)
-            flags[list(stuff)] = 1
-            is_stuff = to_device(flags, torch.uint8)
-        score, label = K.det_postprocess(cat_preds.contiguous())
-        seg_of = K.panoptic_select(score, label, float(score_threshold), self.num_categories, is_stuff)
-        ids, _, pop = K.panoptic_merge(logits.reshape(B, N, MASK_GRID, MASK_GRID).contiguous(), seg_of, hw_dev, Hm, Wm, with_bits=False)
-        own = seg_of == torch.arange(N, device=seg_of.device, dtype=torch.int32)[None, :]
-        is_segment = own & (pop >= max(int(min_area), 1))
-        area = torch.where(is_segment, pop, torch.zeros_like(pop))
-        # a small elementwise pass: the pixels of a segment below min_area become void
-        flat = ids.reshape(B, -1)
-        dropped = (flat >= 0) & ~torch.gather(is_segment, 1, flat.clamp(min=0).long())
-        ids = torch.where(dropped, torch.full_like(flat, -1), flat).reshape(ids.shape)
-        return {"panoptic_ids": ids, "segment_label": label, "segment_score": score, "segment_area": area, "image_hw": hw_dev}
-
-    def evaluate_panoptic(self, x: Iterable[dict], steps: Optional[int] = None, evaluator=None, score_threshold: float = 0.85,
-                          min_area: int = 5, stuff_classes=(), return_dict: bool = True, verbose: int = 0):
-        """Panoptic quality (PQ / SQ / RQ of the COCO panoptic task) over the batches of `x`, at image resolution
-        (evaluation.PanopticEvaluator; csrc/panopticmerge.hip, K23-K26).  Per batch: an inference-mode forward pass, the head on that
-        call's features and the evaluator's kernels, nothing read back; one device-to-host copy at the end.  Changes nothing, as
-        evaluate(): weights, moving statistics, optimizer slots and counters, the step seed and what panoptic_masks() answers for
-        stay as they were.  Every batch needs what evaluate(coco=True, mask_resolution="image") needs: 'segments'
-        (pipeline.pad_annotations(with_masks=True)), 'height' / 'width' as HOST arrays (with_eval_fields=True) and optionally
-        'iscrowd'; a batch that lacks them, or whose bitmasks would exceed the evaluator's max_mask_bytes, is a ValueError before
-        anything is launched for it.  evaluator: a PanopticEvaluator (it is reset first; its own threshold, min_area and stuff
-        classes hold); otherwise one is built from score_threshold / min_area / stuff_classes.  Returns its result() dict, or with
-        return_dict=False the list [PQ, SQ, RQ]."""
-        from . import evaluation
-        from .model import _prepare_targets
-        self._require_panoptic_head()
-        ev = evaluator if evaluator is not None else evaluation.PanopticEvaluator(self.num_categories, score_threshold, min_area, stuff_classes)
-        if not isinstance(ev, evaluation.PanopticEvaluator):
-            raise ValueError("evaluate_panoptic needs a PanopticEvaluator as evaluator")
-        ev.reset()
-        keep_panoptic = self._panoptic_inputs
-        t0, n = time.time(), 0
-        try:
-            for step, batch in enumerate(x):
-                if steps is not None and step >= steps:
-                    break
-                segments, hw_host = self._image_mask_fields(batch)      # every refusal of this batch before anything is launched for it
-                ev.check_batch(segments, hw_host, self.num_object_preds)
-                cat_ids, _, bbox, num_objects = _prepare_targets(self, batch)
-                iscrowd, _, _ = self._coco_fields(batch, bbox.shape[0], bbox.shape[1])
-                cat_preds, _, _ = self.predict_raw(batch)
-                ev.update(cat_preds, self.panoptic_masks(), cat_ids, segments, num_objects, hw_host, iscrowd)
-                n += 1
-        finally:
-            self._panoptic_inputs = keep_panoptic      # panoptic_masks() keeps answering for the last call the user made
-        res = ev.result()
-        if verbose:
-            print(f"evaluate_panoptic - {time.time() - t0:.1f}s - {n} steps - " + " - ".join(f"{k}: {res[k]:.4f}" for k in ("PQ", "SQ", "RQ")))
-        return res if return_dict else [res[k] for k in ("PQ", "SQ", "RQ")]
 
     def step_logs(self) -> Dict[str, list]:
         """name -> list of per-image [B] device tensors (one per weak learner).  Nothing is copied to

@@ -223,3 +223,140 @@ def test_pipeline_carries_eval_fields_only_when_asked():
     assert batch["iscrowd"].tolist() == [[1, 0, 0], [0, 0, 0]] and batch["area"].tolist() == [[4321.5, 200.0, 0.0], [0.0, 0.0, 0.0]]
     assert batch["height"].tolist() == [100, 50] and batch["width"].tolist() == [200, 50] and batch["iscrowd"].dtype == np.int32
     assert np.array_equal(batch["bbox"], pipeline.pad_annotations(plain, 3)["bbox"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 6. one precision / recall curve: the short form is the COCO form without ignore bits and without a rank cut
+# ---------------------------------------------------------------------------------------------------------------------
+SHORT_FORM = json.loads((ROOT / "tests" / "golden" / "short_form_ap.json").read_text())["cases"]
+
+
+def unhex(v):
+    return float("nan") if v is None else float.fromhex(v)
+
+
+@pytest.mark.parametrize("name", sorted(CS.BOX_CASES))
+def test_one_curve_serves_both_protocols(name):
+    from boosted_detr_amd import evaluation
+    c, images = CS.BOX_CASES[name], CS.reference(name)
+    for b, im in enumerate(images):
+        im.update(score=c["score"][b], label=c["label"][b])
+    T, N = len(c["thresholds"]), c["score"].shape[1]
+    gt_count = sum(im["gt_count"] for im in images)[0]
+    short = [(im["score"][None].astype(np.float32), np.asarray(im["label"], np.int32)[None], R.pack_bits(im["keep"], im["tp"][0])[None],
+              np.asarray(im["order"], np.int32)[None]) for im in images]
+    full = [(s, l, im["class_rank"][None].astype(np.int32), t[None], np.zeros_like(t)[None], o) for (s, l, t, o), im in zip(short, images)]
+    got = evaluation.DetectionEvaluator(c["C"], c["thresholds"], N).result_from(short, gt_count)
+    want = SHORT_FORM[name]                                                      # what the short form's own loop gave before there was one
+    for k in ("AP", "AP50", "AP75", "AR"):
+        assert exactly(got[k], unhex(want[k])), (k, got[k], unhex(want[k]))
+    assert np.array_equal(got["per_class_AP"], [unhex(v) for v in want["per_class_AP"]], equal_nan=True)
+    assert got["num_detections"] == want["num_detections"] and np.array_equal(got["gt_count"], gt_count)
+    # the function both call, class by class, against the arrays of accumulate_pair
+    lineup = evaluation._Lineup(full, 1)
+    precision, recall = evaluation.accumulate_pair(lineup, gt_count, T, 0, N)
+    assert precision.shape == (T, 101, c["C"]) and (gt_count > 0).any()
+    for cls in range(c["C"]):
+        if gt_count[cls] == 0:
+            assert (precision[:, :, cls] == -1).all() and (recall[:, cls] == -1).all()
+            continue
+        sel = lineup.labels == cls
+        for ig in (None, lineup.ig[0][sel]):                                     # no ignore words, or all-zero ones
+            p, r = evaluation.precision_recall(lineup.scores[sel], lineup.tp[0][sel], ig, int(gt_count[cls]), T)
+            assert p.shape == (T, 101) and r.shape == (T,)
+            assert np.array_equal(p, precision[:, :, cls]) and np.array_equal(r, recall[:, cls]), cls
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. the one device-to-host copy: every kept tensor comes back with its shape, its host dtype and its bits
+# ---------------------------------------------------------------------------------------------------------------------
+def _filled_evaluators():
+    """A DetectionEvaluator, a CocoEvaluator with two ranges and a PanopticEvaluator, two batches each of different shapes, with
+    host tensors standing in for device tensors and values that a careless widening would change."""
+    import torch
+    from boosted_detr_amd import evaluation
+    rng = np.random.default_rng(5)
+    C, A = 5, 2
+    det = evaluation.DetectionEvaluator(C)
+    coco = evaluation.CocoEvaluator(C, area_ranges={"all": (0.0, 1e10), "small": (0.0, 1024.0)})
+    pq = evaluation.PanopticEvaluator(C, stuff_classes=(4,))
+
+    def i32(*shape, lo=2, hi=C):
+        return torch.from_numpy(rng.integers(lo, hi, shape).astype(np.int32))
+
+    def words(*shape):                                                           # uint16 patterns as the kernels store them: int16
+        w = rng.integers(0, 1 << 10, shape).astype(np.uint16) | np.uint16(evaluation.KEEP_BIT)
+        w.reshape(-1)[1] &= np.uint16(0x7FFF)                                    # one detection that was not kept
+        return torch.from_numpy(w.view(np.int16).copy())
+
+    for B, N, M in ((1, 3, 2), (2, 5, 4)):
+        score = rng.random((B, N)).astype(np.float32)
+        score[0, 0], score[0, 1] = -0.25, np.float32(np.nan)
+        score.view(np.uint32)[0, 1] = 0x7FC00123                                 # a NaN with a payload
+        score = torch.from_numpy(score)
+        order = np.stack([rng.permutation(N) for _ in range(B)]).astype(np.int32)
+        order[:, -1] = -1                                                        # a rank that holds no detection
+        order = torch.from_numpy(order)
+        label = i32(B, N)
+        det._kept.append((score, label, words(B, N), order))
+        coco._kept.append((score, label, i32(B, N, lo=0, hi=N), words(A, B, N), words(A, B, N), order))
+        union = i32(B, M, lo=1, hi=1 << 30)
+        pq._kept.append((i32(B, M, lo=-2, hi=N), i32(B, N, lo=-2, hi=M), (union.double() * 0.7).to(torch.int32), union, i32(B, M), i32(B, N)))
+    det._gt_count = torch.tensor([0, 0, 3, 1, 2], dtype=torch.int32)
+    coco._gt_count = torch.tensor([[0, 0, 3, 1, 2], [0, 0, 1, 0, 2]], dtype=torch.int32)
+    return det, coco, pq
+
+
+def _same_result(got, want):
+    assert list(got) == list(want)
+    for k, w in want.items():
+        g = got[k]
+        if isinstance(w, np.ndarray):
+            assert isinstance(g, np.ndarray) and g.dtype == w.dtype and np.array_equal(g, w, equal_nan=True), k
+        elif isinstance(w, list):
+            assert len(g) == len(w) and all(exactly(x, y) for x, y in zip(g, w)), k
+        else:
+            assert type(g) is type(w) and (exactly(g, w) if isinstance(w, float) else g == w), k
+
+
+def test_the_host_copy_returns_every_field_as_it_went_in(monkeypatch):
+    import torch
+    from boosted_detr_amd import evaluation
+    det, coco, pq = _filled_evaluators()
+    host16 = {torch.float32: np.float32, torch.int32: np.int32, torch.int16: np.uint16}
+
+    def check_records(ev, records):
+        assert len(records) == len(ev._kept) == 2
+        for rec, kept in zip(records, ev._kept):
+            assert len(rec) == len(kept)
+            for k, (h, d) in enumerate(zip(rec, kept)):
+                assert h.dtype == host16[d.dtype] and h.shape == tuple(d.shape), (k, h.dtype, h.shape)
+                assert h.tobytes() == d.numpy().tobytes(), k                     # bit for bit, NaN payloads and bit 15 included
+
+    for ev, shape in ((det, (5,)), (coco, (2, 5))):
+        records, gt_count = ev._to_host()
+        check_records(ev, records)
+        assert gt_count.dtype == np.int64 and gt_count.shape == shape and np.array_equal(gt_count, ev._gt_count.numpy())
+    records = pq._to_host()
+    assert isinstance(records, list)
+    check_records(pq, records)
+    assert records[1][0].min() < 0 and det._to_host()[0][0][3].min() == -1 and (det._to_host()[0][0][2] & evaluation.KEEP_BIT).any()
+
+    alone = [ev.result() for ev in (det, coco, pq)]
+    assert alone[0]["num_images"] == alone[1]["num_images"] == alone[2]["num_images"] == 3 and alone[0]["num_detections"] > 0
+    copies = []
+    cat = torch.cat
+    monkeypatch.setattr(torch, "cat", lambda *a, **k: copies.append(1) or cat(*a, **k))
+    together = evaluation.results([det, coco, pq])
+    assert len(copies) == 1                                                      # one torch.cat(...).cpu() for the three
+    for got, want in zip(together, alone):
+        _same_result(got, want)
+    empty = evaluation.CocoEvaluator(5, area_ranges={"all": (0.0, 1e10), "small": (0.0, 1024.0)})
+    for middle, fresh in ((empty, evaluation.CocoEvaluator(5, area_ranges={"all": (0.0, 1e10), "small": (0.0, 1024.0)}).result()),
+                          (evaluation.PanopticEvaluator(5), evaluation.PanopticEvaluator(5).result()),
+                          (evaluation.DetectionEvaluator(5), evaluation.DetectionEvaluator(5).result())):
+        got = evaluation.results([det, middle, pq, coco])
+        for g, w in zip(got, [alone[0], fresh, alone[2], alone[1]]):
+            _same_result(g, w)
+    assert empty._to_host()[0] == [] and empty._to_host()[1].shape == (2, 5) and evaluation.PanopticEvaluator(5)._to_host() == []
+    assert [r for r in evaluation.results([evaluation.DetectionEvaluator(5)])][0]["num_detections"] == 0

@@ -213,3 +213,49 @@ def test_model_refusals_come_before_the_library(no_library):
         Model.segmentations(model, {"image": None}, resolution="image")
     with pytest.raises(ValueError, match="must be one of"):
         Model.segmentations(model, {"image": None}, resolution="pixel")
+
+
+def test_detection_ap_asks_evaluate_for_what_its_arguments_say():
+    """The callback's one call of Model.evaluate, with evaluate's defaults filled in, per way of building it; and the logs it leaves."""
+    import inspect
+    from boosted_detr_amd.training import DetectionAP, Model
+    data, box_ev, mask_ev, both = [object()], object(), object(), ("bbox", "segm")
+    four = ("AP", "AP50", "AP75", "AR")
+    summary = four[:3] + ("AP_small", "AP_medium", "AP_large", "AR_1", "AR_10", "AR_100", "AR_small", "AR_medium", "AR_large") + four[3:]
+
+    class Stub:
+        def evaluate(self, *args, **kw):
+            bound = inspect.signature(Model.evaluate).bind(self, *args, **kw)
+            bound.apply_defaults()
+            self.asked = {k: v for k, v in bound.arguments.items() if k != "self"}
+            keys = summary if self.asked["coco"] else four
+            res = {}
+            for p, t in (("", "bbox"), ("mask_", "segm")):
+                if t in self.asked["iou_types"]:
+                    res.update({p + k: len(res) + 0.5 for k in keys})
+                    res.update({f"per_class_{p}AP": np.zeros(3), p + "stats": [0.0], "num_images": 2})
+            return res
+
+    def run(keys, **kw):
+        cb, model, logs = DetectionAP(data, steps=3, evaluator=box_ev, **kw), Stub(), {"loss": 1.0}
+        cb.set_model(model)
+        cb.on_epoch_end(0, logs)
+        assert list(logs) == ["loss"] + ["val_" + k for k in keys] and cb.history == [{"epoch": 0, **{k: v for k, v in logs.items() if k != "loss"}}]
+        assert all(type(logs[k]) is float for k in logs)
+        return model.asked
+
+    base = dict(x=data, steps=3, evaluator=box_ev, return_dict=True, verbose=0, iou_types=("bbox",), mask_evaluator=None, coco=False,
+                mask_resolution="grid")
+    assert run(four) == base
+    assert run(four, mask_evaluator=mask_ev) == base                                         # without "segm" the short form never passed it on
+    assert run(four + tuple("mask_" + k for k in four), iou_types=both, mask_evaluator=mask_ev) == dict(base, iou_types=both, mask_evaluator=mask_ev)
+    assert run(tuple("mask_" + k for k in four), iou_types="segm") == dict(base, iou_types=("segm",))
+    assert run(summary, coco=True, mask_evaluator=mask_ev) == dict(base, coco=True, mask_evaluator=mask_ev)
+    assert run(summary + tuple("mask_" + k for k in summary), coco=True, iou_types=both, mask_resolution="image") == \
+        dict(base, coco=True, iou_types=both, mask_resolution="image")
+    cb = DetectionAP(data, every=2)
+    cb.set_model(Stub())
+    cb.on_epoch_end(0, {})
+    assert cb.history == [] and not hasattr(cb.model, "asked")
+    cb.on_epoch_end(1, None)
+    assert [h["epoch"] for h in cb.history] == [1]
