@@ -218,6 +218,10 @@ SIGNATURES = {
     "bdetr_panoptic_merge": (I, [P, P, P, I, I, I, I, I, P, P, P, P]),
     "bdetr_panoptic_gt_exclusive": (I, [P, P, P, I, I, I, I, I, P, P]),
     "bdetr_panoptic_match": (I, [P] * 8 + [I] * 5 + [P] * 5),
+    # K27-K28 (csrc/maskrle.hip): COCO's rleEncode on the bitmasks of K19 / K24.  K27: runs per mask (bit-parallel popcounts);
+    # K28: the run lengths, column-major, at the offsets the prefix sum of K27 gives
+    "bdetr_mask_rle_count": (I, [P, P, P, I, I, I, I, P, P]),
+    "bdetr_mask_rle_encode": (I, [P, P, P, P, I, I, I, I, L, P, P]),
 }
 
 

@@ -19,6 +19,9 @@ query's mask shares its box's class and score (DETR's convention).
 
 ``PanopticEvaluator`` (K23-K26) is the COCO panoptic task's PQ / SQ / RQ at image resolution: the kept queries' upsampled logits merged
 into one id per pixel, the ground truths made disjoint, panopticapi's matching in integers; ``accumulate_pq`` is its host half.
+
+``CocoResults`` (K27 / K28) is the way out to the official tools: the entries of a COCO results file, every query's image-resolution
+mask run-length encoded on the GPU so that only the runs reach the host.
 """
 from __future__ import annotations
 
@@ -716,6 +719,171 @@ class PanopticEvaluator(_KeptRecords):
     def result_from(self, records: Sequence[tuple]) -> Dict[str, object]:
         """The host half alone: accumulate_pq over records as the kernels leave them (host int32 arrays; no device is needed)."""
         return accumulate_pq(records, self.num_classes, self.stuff_classes)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# result files (K27 / K28)
+# ---------------------------------------------------------------------------------------------------------------------
+def category_id_table(vocabulary: Sequence[str], category_ids=None) -> List[int]:
+    """The dataset's category id of every label: entry l - 2 belongs to label l >= 2, the vocabulary's entry l - 2.  category_ids:
+    a dict name -> id or a COCO ``categories`` list of {"id", "name"}; None: the id is l - 2.  A vocabulary name the mapping lacks
+    is a ValueError."""
+    names = [str(n) for n in vocabulary]
+    if category_ids is None:
+        return list(range(len(names)))
+    if isinstance(category_ids, dict):
+        ids = dict(category_ids)
+    else:
+        try:
+            ids = {c["name"]: c["id"] for c in category_ids}
+        except (TypeError, KeyError):
+            raise ValueError("category_ids must be a dict name -> id or a COCO 'categories' list of {'id', 'name'} entries") from None
+    missing = [n for n in names if n not in ids]
+    if missing:
+        raise ValueError(f"category_ids has no id for {len(missing)} of the model's categories: {missing[:5]}")
+    return [int(ids[n]) for n in names]
+
+
+def batch_image_ids(batch: dict) -> list:
+    """The batch's 'image_id' entry (pad_annotations(with_image_ids=True)) as a list of built-in values; a batch without one is a
+    ValueError that names the key."""
+    ids = batch.get("image_id")
+    if ids is None:
+        raise ValueError("a result file needs every batch's 'image_id', one per image (pipeline.pad_annotations(..., with_image_ids=True))")
+    if hasattr(ids, "is_cuda"):
+        ids = ids.cpu().numpy()
+    ids = ids.tolist() if isinstance(ids, np.ndarray) else list(ids)
+    return [v.item() if isinstance(v, np.generic) else v for v in ids]
+
+
+class CocoResults:
+    """The entries of a COCO results file, accumulated batch by batch: one per (image, query) in batch, image, query order,
+        {"image_id", "category_id", "score", "bbox": [x, y, w, h] in pixels}
+    and with masks also "segmentation": {"size": [h, w], "counts": ...}, the query's image-resolution mask as COCO's column-major
+    RLE - what pycocotools' loadRes and the COCO servers take.  Everything is built-in Python types.
+
+    ``update`` runs bdetr_det_postprocess and, with mask logits, bdetr_mask_upsample_bits (K19) and the run-length encoder
+    (bdetr_mask_rle_count / bdetr_mask_rle_encode, K27 / K28) on the current stream: the bitmasks never leave HBM, only the run
+    lengths do.  Per batch it reads the total of the counts back (to size their buffer) and makes ONE device-to-host copy of
+    (counts, offset, scores, labels, boxes); the compressed strings are made on the host (pipeline.encode_rle_counts).
+    ``update_from`` is the host half alone.
+
+    vocabulary: the model's category names (label l >= 2 is entry l - 2); category_ids: see ``category_id_table``;
+    score_threshold: only queries with score > (float32)score_threshold get an entry, and only their masks are encoded (None:
+    every query); compress: counts as the compressed string (False: the list of ints); max_mask_bytes: the budget of one batch's
+    bitmask buffer, 8 Hm Wm B N bytes, and of its run lengths - a batch over it is a ValueError before the launch that would need it."""
+
+    def __init__(self, vocabulary: Sequence[str], category_ids=None, score_threshold: Optional[float] = None, compress: bool = True,
+                 max_mask_bytes: Optional[int] = None):
+        self.category_table = category_id_table(vocabulary, category_ids)
+        if score_threshold is not None and not float(score_threshold) == float(score_threshold):
+            raise ValueError("score_threshold must be a number or None")
+        self.score_threshold = None if score_threshold is None else np.float32(score_threshold)
+        self.compress = bool(compress)
+        self.max_mask_bytes = check_max_mask_bytes(max_mask_bytes)
+        self.reset()
+
+    def reset(self) -> None:
+        self._entries: List[dict] = []
+
+    def check_batch(self, image_ids, image_hw_host, B: int, N: int, with_masks: bool):
+        """Every refusal of update() that needs no device.  Returns (image_hw int32 [B,2], Hm, Wm); Hm = Wm = 0 without masks."""
+        from . import kernels as K
+        hw = np.asarray(image_hw_host)
+        if hw.shape != (B, 2) or not np.issubdtype(hw.dtype, np.integer):
+            raise ValueError(f"image_hw_host must be integers [B={B},2] (height, width), got {hw.dtype} {hw.shape}")
+        if len(image_ids) != B:
+            raise ValueError(f"'image_id' has {len(image_ids)} entries, the batch has {B} images")
+        hw = hw.astype(np.int32)
+        if not with_masks:
+            return hw, 0, 0
+        Hm, Wm = K.mask_layout(hw)
+        need = 8 * Hm * Wm * B * int(N)
+        if need > self.max_mask_bytes:
+            raise ValueError(f"the bitmask buffer of this batch needs {need} bytes (8 Hm Wm B N with Hm={Hm}, Wm={Wm}, B={B}, N={N}); "
+                             f"max_mask_bytes is {self.max_mask_bytes}")
+        return hw, Hm, Wm
+
+    def update(self, cat_pred, box_pred, image_ids, image_hw_host, mask_logits=None) -> None:
+        """cat_pred [B,N,C] probabilities and box_pred [B,N,4] from ``Model.predict_raw``, in HBM; image_ids: B values; image_hw_host:
+        HOST integers [B,2], every image's (height, width); mask_logits f32 [B,N,G,G] (or [B,N,G*G]) from ``panoptic_masks``, or None
+        for entries without a segmentation.  Every refusal comes before the first launch."""
+        import torch
+        from . import kernels as K
+        if cat_pred.dim() != 3 or tuple(box_pred.shape) != tuple(cat_pred.shape[:2]) + (4,):
+            raise ValueError("expected cat_pred [B,N,C] and box_pred [B,N,4]")
+        B, N = cat_pred.shape[:2]
+        if cat_pred.shape[2] != len(self.category_table) + 2:
+            raise ValueError(f"cat_pred has {cat_pred.shape[2]} classes, the vocabulary has {len(self.category_table)} + 2")
+        if mask_logits is not None:
+            if mask_logits.dim() not in (3, 4) or tuple(mask_logits.shape[:2]) != (B, N):
+                raise ValueError(f"mask_logits {tuple(mask_logits.shape)} do not fit cat_pred [B={B},N={N},C]")
+            G = int(round(float(mask_logits.shape[2]) ** 0.5)) if mask_logits.dim() == 3 else int(mask_logits.shape[2])
+            if mask_logits[0, 0].numel() != G * G:
+                raise ValueError(f"mask_logits {tuple(mask_logits.shape)} are no square grid")
+        hw, Hm, Wm = self.check_batch(image_ids, image_hw_host, B, N, mask_logits is not None)
+        score, label = K.det_postprocess(cat_pred.contiguous())
+        parts = [score, label, box_pred.contiguous()]
+        if mask_logits is not None:
+            hw_dev = torch.from_numpy(hw).to(cat_pred.device)
+            keep = None if self.score_threshold is None else (score > float(self.score_threshold)).to(torch.uint8)
+            bits, _ = K.mask_upsample_bits(mask_logits.reshape(B, N, G, G).contiguous(), hw_dev, Hm, Wm)
+            counts, offset = K.mask_rle_encode(bits, hw_dev, keep, max_bytes=self.max_mask_bytes)
+            parts += [offset.view(torch.int32), counts]
+        flat = torch.cat([_words(t) for t in parts]).cpu().numpy()          # the one copy
+        o = 0
+        host = []
+        for t in parts:
+            host.append(_from_words(flat[o:o + t.numel()], t))
+            o += t.numel()
+        if mask_logits is None:
+            self.update_from(host[0], host[1], host[2], image_ids, hw)
+        else:
+            self.update_from(host[0], host[1], host[2], image_ids, hw, host[4], np.ascontiguousarray(host[3]).view(np.int64))
+
+    def update_from(self, score, label, box, image_ids, image_hw, counts=None, offset=None) -> None:
+        """The host half alone: score f32 [B,N], label int [B,N], box f32 [B,N,4] (normalised COCO [x,y,w,h]), image_ids [B], image_hw
+        int [B,2] and, for masks, counts int32 [total] / offset int64 [B N + 1] as kernels.mask_rle_encode leaves them (a kept
+        query's span must not be empty).  bbox is the box times [w, h, w, h], in Python floats from the fp32 values."""
+        from .pipeline import encode_rle_counts
+        score, label = np.asarray(score, np.float32), np.asarray(label, np.int64)
+        box, hw = np.asarray(box, np.float32), np.asarray(image_hw, np.int64)
+        B, N = score.shape
+        if label.shape != (B, N) or box.shape != (B, N, 4) or hw.shape != (B, 2) or len(image_ids) != B:
+            raise ValueError("expected score [B,N], label [B,N], box [B,N,4], image_ids [B] and image_hw [B,2]")
+        if (counts is None) != (offset is None):
+            raise ValueError("counts and offset come together")
+        if offset is not None:
+            counts, offset = np.asarray(counts), np.asarray(offset, np.int64).reshape(-1)
+            if offset.shape != (B * N + 1,) or offset[0] != 0 or (np.diff(offset) < 0).any() or offset[-1] > counts.size:
+                raise ValueError("offset must be the exclusive prefix sum [B N + 1] of the masks' run counts, inside counts")
+        table = self.category_table
+        if label.size and (int(label.min()) < 2 or int(label.max()) >= len(table) + 2):
+            raise ValueError(f"labels must be in [2, {len(table) + 2}): <PAD> and <OOV> are no detection's class")
+        kept = np.ones((B, N), bool) if self.score_threshold is None else score > self.score_threshold
+        for b in range(B):
+            image_id = image_ids[b].item() if isinstance(image_ids[b], np.generic) else image_ids[b]
+            h, w = int(hw[b, 0]), int(hw[b, 1])
+            scale = (float(w), float(h), float(w), float(h))
+            for n in np.flatnonzero(kept[b]):
+                entry = {"image_id": image_id, "category_id": table[int(label[b, n]) - 2], "score": float(score[b, n]),
+                         "bbox": [float(box[b, n, k]) * scale[k] for k in range(4)]}
+                if offset is not None:
+                    runs = counts[offset[b * N + n]:offset[b * N + n + 1]]
+                    if runs.size == 0:
+                        raise ValueError(f"query {int(n)} of image {b} is kept but has no run lengths")
+                    entry["segmentation"] = {"size": [h, w], "counts": encode_rle_counts(runs) if self.compress else [int(v) for v in runs]}
+                self._entries.append(entry)
+
+    def result(self) -> List[dict]:
+        """The entries so far, in arrival order (a new list of the same dicts)."""
+        return list(self._entries)
+
+    def dump(self, path) -> None:
+        """result() as JSON at `path`: a COCO results file."""
+        import json
+        with open(path, "w") as f:
+            json.dump(self._entries, f)
 
 
 def results(evaluators: Sequence[_KeptRecords]) -> List[Dict[str, object]]:

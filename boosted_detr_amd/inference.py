@@ -1,7 +1,8 @@
 """Inference and evaluation of a training.Model: raw predictions, detections, segmentations and the panoptic merge, and the loops
-of ``evaluate`` (box and mask AP, short and full COCO protocol) and ``evaluate_panoptic`` (PQ) over the evaluators of evaluation.py.
+of ``evaluate`` (box and mask AP, short and full COCO protocol), ``evaluate_panoptic`` (PQ) and ``coco_results`` (the entries of a
+COCO results file) over the evaluators of evaluation.py.
 ``Inference`` is a stateless base class of training.Model: it defines no __init__ and adds no attribute; what it reads
-(num_categories, num_object_preds, image_size, _panoptic_inputs, panoptic_masks()) is the model's."""
+(num_categories, num_object_preds, image_size, vocab_dict, _panoptic_inputs, panoptic_masks()) is the model's."""
 from __future__ import annotations
 
 import time
@@ -208,6 +209,49 @@ class Inference:
         else:
             hw = tuple(int(v) for v in self.image_size[:2])
         return iscrowd, area, hw
+
+    def coco_results(self, x: Iterable[dict], steps: Optional[int] = None, iou_types=("bbox",), score_threshold: Optional[float] = None,
+                     category_ids=None, compress: bool = True, path=None) -> List[dict]:
+        """The entries of a COCO results file over the batches of `x` (the dicts evaluate() takes) - what pycocotools' loadRes and the
+        COCO servers read (evaluation.CocoResults).  One entry per image and query, in batch, image, query order:
+        {"image_id", "category_id", "score", "bbox": [x, y, w, h] in pixels}; with "segm" in iou_types also "segmentation":
+        {"size": [h, w], "counts": str}, the query's mask at image resolution (segmentations(resolution="image")'s image_masks) as
+        COCO's column-major RLE.  Built-in Python types throughout: json.dumps takes the list, and path= writes it.
+        Every batch needs 'image_id', one per image (pipeline.pad_annotations(with_image_ids=True)); 'height' / 'width' give the
+        pixel size of each image (absent: the model's image_size).  category_id: label l >= 2 is entry l - 2 of the model's category
+        vocabulary, mapped through category_ids - a dict name -> id or a COCO 'categories' list; a name it lacks is a ValueError
+        before the first batch - or l - 2 itself with None.  score_threshold: only the queries with score > threshold (as float32)
+        get an entry, and only their masks are encoded.  compress=False: counts is the list of run lengths.
+        "segm" needs the panoptic head and 'height' / 'width' as HOST arrays, and refuses otherwise before a launch.  Per batch it
+        runs the forward pass, the head, K19 and the run-length encoder (csrc/maskrle.hip, K27 / K28): the bitmasks stay in HBM, the
+        total of the run counts is read back to size their buffer, and one device-to-host copy brings (counts, offset, scores,
+        labels, boxes); the compressed strings are made on the host.  "bbox" alone works on every model.
+        Changes nothing, as evaluate(): weights, moving statistics, optimizer slots and counters, the step seed and what
+        panoptic_masks() answers for stay as they were."""
+        types = self._check_iou_types(iou_types)
+        segm = "segm" in types
+        if segm:
+            self._require_panoptic_head()
+        res = evaluation.CocoResults(self.vocab_dict["category"], category_ids, score_threshold, compress)
+
+        def per_batch(batch: dict) -> None:
+            image_ids = evaluation.batch_image_ids(batch)         # every refusal of this batch before anything is launched for it
+            if segm or batch.get("height") is not None or batch.get("width") is not None:
+                height, width = (v.cpu() if getattr(v, "is_cuda", False) and not segm else v for v in (batch.get("height"), batch.get("width")))
+                hw = evaluation.host_image_hw(height, width)
+            else:
+                hw = np.tile(np.asarray([int(v) for v in self.image_size[:2]], np.int32), (len(image_ids), 1))
+            res.check_batch(image_ids, hw, len(image_ids), self.num_object_preds, segm)
+            cat_preds, _, box_preds = self.predict_raw(batch)
+            res.update(cat_preds, box_preds, image_ids, hw, self.panoptic_masks() if segm else None)
+
+        def result() -> dict:
+            return {"entries": res.result()}
+
+        entries = self._evaluation_loop("coco_results", x, steps, per_batch, result, (), 0)["entries"]
+        if path is not None:
+            res.dump(path)
+        return entries
 
     def panoptic_segmentation(self, inputs: dict, score_threshold: float = 0.85, min_area: int = 5, stuff_classes=()) -> Dict[str, torch.Tensor]:
         """One id per pixel, in HBM: the queries with score > score_threshold become segments (the kept queries of a class in

@@ -1464,6 +1464,61 @@ def mask_match_coco_inter(score, label, inter, det_pop, gt_label, gt_pop, gt_cro
 
 
 # --------------------------------------------------------------------------------------
+# COCO run-length encoding of bitmasks - csrc/maskrle.hip (K27, K28)
+# --------------------------------------------------------------------------------------
+def _rle_operands(what: str, bits, image_hw, keep):
+    """The operands K27 and K28 share, checked; returns (B, N, Hm, Wm)."""
+    _dtypes(what, bits=(bits, torch.int64), image_hw=(image_hw, torch.int32))
+    if bits.dim() != 4 or bits.numel() == 0:
+        raise _lib.BdetrError(f"{what}: bits must be [B,N,Hm,Wm] with at least one element, got {tuple(bits.shape)}")
+    B, N, Hm, Wm = bits.shape
+    if tuple(image_hw.shape) != (B, 2):
+        raise _lib.BdetrError(f"{what}: operand shapes disagree (bits [B,N,Hm,Wm], image_hw [B,2])")
+    if keep is not None:
+        _dtypes(what, keep=(keep, torch.uint8))
+        if tuple(keep.shape) != (B, N):
+            raise _lib.BdetrError(f"{what}: keep must be [B,N]")
+        _chk(keep, dtype=torch.uint8)
+    _check_layout(what, Hm, Wm)
+    _chk(bits, dtype=torch.int64)
+    _chk(image_hw, dtype=torch.int32)
+    return B, N, Hm, Wm
+
+
+def _mask_rle_count(what: str, bits, image_hw, keep):
+    B, N, Hm, Wm = _rle_operands(what, bits, image_hw, keep)
+    n_counts = empty(B, N, like=bits, dtype=torch.int32)
+    check(_lib.lib().bdetr_mask_rle_count(_p(bits), _p(image_hw), _p(keep), B, N, Hm, Wm, _p(n_counts), _stream()), "mask_rle_count")
+    return n_counts
+
+
+def mask_rle_count(bits, image_hw, keep=None):
+    """bits int64 [B,N,Hm,Wm] (mask_upsample_bits / panoptic_merge), image_hw int32 [B,2], keep uint8 [B,N] or None in HBM ->
+    n_counts int32 [B,N] (include/bdetr.h, K27): the number of run lengths COCO's rleEncode gives every kept mask - its transitions
+    in column-major order plus one -, 0 for a mask with keep == 0.  For callers that only size buffers; nothing is read back."""
+    return _mask_rle_count("mask_rle_count", bits, image_hw, keep)
+
+
+def mask_rle_encode(bits, image_hw, keep=None, max_bytes: int = 1 << 30):
+    """bits int64 [B,N,Hm,Wm], image_hw int32 [B,2], keep uint8 [B,N] or None in HBM -> (counts int32 [total], offset int64 [B N + 1]),
+    both in HBM (include/bdetr.h, K27 / K28): COCO's rleEncode of every kept mask - the run lengths of its pixels in column-major
+    order, zeros first -, mask o's at counts[offset[o] : offset[o+1]]; a mask with keep == 0 has an empty span.  Only the pixels
+    inside the image are looked at.  K27, a prefix sum on the device, then the total is read back - the one small synchronising
+    copy of this path - to size counts; 4 * total > max_bytes is a ValueError before K28 is launched."""
+    n_counts = _mask_rle_count("mask_rle_encode", bits, image_hw, keep)
+    B, N, Hm, Wm = bits.shape
+    offset = torch.zeros(B * N + 1, dtype=torch.int64, device=bits.device)
+    torch.cumsum(n_counts.reshape(-1), 0, dtype=torch.int64, out=offset[1:])
+    total = int(offset[-1].item())
+    if 4 * total > int(max_bytes):
+        raise ValueError(f"mask_rle_encode: the run lengths of this batch need {4 * total} bytes (4 x {total} counts); max_bytes is {int(max_bytes)}")
+    counts = empty(total, like=bits, dtype=torch.int32)
+    check(_lib.lib().bdetr_mask_rle_encode(_p(bits), _p(image_hw), _p(keep), _p(offset), B, N, Hm, Wm, total, _p(counts) if total else None,
+                                           _stream()), "mask_rle_encode")
+    return counts, offset
+
+
+# --------------------------------------------------------------------------------------
 # panoptic merge and panoptic quality - csrc/panopticmerge.hip (K23-K26)
 # --------------------------------------------------------------------------------------
 PANOPTIC_MAX_ROWS = 1024          # queries / ground-truth rows per image

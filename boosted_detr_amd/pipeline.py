@@ -139,7 +139,7 @@ def _segment_items(seg, h: int, w: int):
 
 
 def pad_annotations(records: Sequence[dict], max_objects: Optional[int] = None, with_eval_fields: bool = False,
-                    with_masks: bool = False) -> Dict[str, np.ndarray]:
+                    with_masks: bool = False, with_image_ids: bool = False) -> Dict[str, np.ndarray]:
     """pipeline.py:139-181: ragged per-image lists -> uniform arrays.  category [B,M,1] (pad '<PAD>'),
     attribute [B,M,Amax] (pad '<PAD>'), bbox [B,M,4] (pad -10), num_objects [B].  with_eval_fields: also iscrowd int32 [B,M]
     (pad 0), area f32 [B,M] in pixels (pad 0) and height / width int32 [B], from records of coco_records(with_eval_fields=True).
@@ -147,7 +147,9 @@ def pad_annotations(records: Sequence[dict], max_objects: Optional[int] = None, 
     int32 arrays in the layout of bdetr_mask_targets (include/bdetr.h, K18): items [T], item_off [B M + 1], kind [B,M] (0 none /
     1 polygon / 2 RLE), hw [B,M,2], with the same M and the same truncation as bbox.  Polygon vertices are snapped to 1/256 pixel
     here; RLE counts (list or compressed string) become (start, length) one-runs.  An RLE whose size differs from the record's
-    height, width, counts that do not sum to h * w, and sizes beyond 4096 are a ValueError."""
+    height, width, counts that do not sum to h * w, and sizes beyond 4096 are a ValueError.
+    with_image_ids: also image_id, a list [B] of the records' 'image_id' as they are (what Model.coco_results writes into every
+    entry of a result file); a record without one is a ValueError."""
     B = len(records)
     n = [len(r.get("bbox", [])) for r in records]
     M = max_objects if max_objects is not None else max(max(n), 1)
@@ -186,6 +188,10 @@ def pad_annotations(records: Sequence[dict], max_objects: Optional[int] = None, 
             raise ValueError("segmentations of one batch exceed 2^31 items")
         out["segments"] = {"items": np.concatenate(chunks + [np.zeros(0, np.int32)]).astype(np.int32),
                            "item_off": np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32), "kind": kind, "hw": hw}
+    if with_image_ids:
+        if any("image_id" not in r for r in records):
+            raise ValueError("pad_annotations(with_image_ids=True) needs records with an 'image_id' (coco_records gives them)")
+        out["image_id"] = [r["image_id"] for r in records]
     return out
 
 

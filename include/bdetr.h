@@ -937,6 +937,42 @@ int bdetr_panoptic_match(const int32_t* inter, const int32_t* pred_pop, const in
                          int M, int C, int min_area, int32_t* gt_state, int32_t* pred_state, int32_t* match_inter, int32_t* match_union,
                          void* stream);
 
+/* ------------------------------------------------------------------------
+ * K27-K28  COCO run-length encoding of bitmasks, for result files (csrc/maskrle.hip; kernels.mask_rle_encode chains K27, a prefix
+ *   sum on the device and K28; evaluation.CocoResults is the user).  Additions to ABI 8: nothing that existed changed.
+ *   Input of both: bits uint64 [B,N,Hm,Wm] in the layout of K19-K22, exactly as bdetr_mask_upsample_bits (K19) and
+ *   bdetr_panoptic_merge (K24) write it - pixel (x, y) of image b is bit (x mod 64) of word [y, x div 64] -; image_hw int32 [B,2]
+ *   (h_b, w_b; clamped to [0, Hm] x [0, 64 Wm] as in K19); keep uint8 [B,N] or NULL (NULL: every mask is kept; a mask with keep == 0
+ *   produces nothing).  Only the pixels with y < h_b and x < w_b are looked at: the kernels do not rely on the zero padding.
+ *   Rule (COCO's rleEncode), in integers.  The h w pixels of a mask are taken in column-major order, p = x h + y.  `counts` holds
+ *   the lengths of the alternating runs of 0 and 1, starting with a run of 0 - of length 0 when pixel p = 0 is set -, and the last
+ *   run closes at h w.  With T = the number of p in [0, h w) whose pixel differs from pixel p - 1 (pixel -1 counts as 0) and
+ *   pos[0] < ... < pos[T-1] those p:
+ *       counts has T + 1 entries;  counts[i] = pos[i] - pos[i-1] with pos[-1] = 0 and pos[T] = h w;  they sum to h w;
+ *       an all-zero mask is [h w], an all-one mask [0, h w].  A run is at most 2^24: int32 holds it.
+ *
+ * K27  bdetr_mask_rle_count -> n_counts int32 [B,N]: T + 1 for a kept mask, 0 otherwise.  Bit-parallel: the pixel before (x, y) is
+ *   (x, y - 1) for y >= 1, so 64 columns of row y give popcount((row[y] ^ row[y-1]) & columns x < w); for y = 0 it is
+ *   (x - 1, h - 1): row h - 1 moved up by one column (bit x takes bit x - 1, the carry crosses the word boundary, column 0 takes
+ *   0).  One workgroup per mask; the rows 1 .. h - 1 stream from memory once (16-byte loads when Wm is even and the base is 16-byte
+ *   aligned, else 8-byte loads), the row above comes through the caches; integer adds only.
+ *
+ * K28  bdetr_mask_rle_encode: the same operands plus offset int64 [B N + 1], the exclusive prefix sum of K27's n_counts, and
+ *   total, the number of int32 the buffer `counts` holds (>= offset[B N]; counts may be NULL when total = 0, and nothing is launched
+ *   then).  Mask o's run lengths go, in order, to counts[offset[o] : offset[o+1]].  One workgroup per mask; a wave takes a word
+ *   column, loads 64 rows of it and transposes the 64 x 64 bits over its lanes, so that lane l holds 64 consecutive pixels of
+ *   column 64 wd + l; the transitions are col ^ (col << 1 | carry).  A first walk counts them per column, a workgroup scan turns
+ *   the counts into slots, a second walk writes every transition's p to its slot (and h w to slot T), and the differences are
+ *   taken in place.  A pure function of the input: no atomics on the output, two calls give the same bits.  Nothing is written
+ *   outside a mask's own span, nor outside [0, total), whatever offset holds (a span shorter than T + 1 is filled and the rest
+ *   dropped).
+ *   Limits of both: B N <= 2^24, 1 <= Hm <= 4096, 1 <= Wm <= 64; anything else returns -1 (bdetr_last_error) without a launch.
+ * ---------------------------------------------------------------------- */
+int bdetr_mask_rle_count(const uint64_t* bits, const int32_t* image_hw, const uint8_t* keep, int B, int N, int Hm, int Wm,
+                         int32_t* n_counts, void* stream);
+int bdetr_mask_rle_encode(const uint64_t* bits, const int32_t* image_hw, const uint8_t* keep, const int64_t* offset, int B, int N, int Hm,
+                          int Wm, int64_t total, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
