@@ -38,13 +38,14 @@ class _ConvBN(Layer):
         self.built = True
 
     def call(self, inputs, training=False, relu=True, residual=None, x_needs_grad=True, want_fp32=True, want_p16=False, defer_apply=False,
-             next_is_identity_unit=False, want_bf16=False):
+             next_is_identity_unit=False, next_reads_even_pixels=False, want_bf16=False):
         x = inputs[0]
         # S18: BN uses batch statistics only when training AND the layer is trainable
         return ops.conv_bn(x, self.kernel, self.bias, self.bn, self.stride, self.pad, relu, residual=residual,
                            training=training, bn_batch_stats=training and self.trainable, x_needs_grad=x_needs_grad,
                            want_fp32=want_fp32, want_p16=want_p16, defer_apply=defer_apply,
-                           sole_consumer_is_identity_unit=next_is_identity_unit, want_bf16=want_bf16)
+                           sole_consumer_is_identity_unit=next_is_identity_unit, consumers_read_even_pixels=next_reads_even_pixels,
+                           want_bf16=want_bf16)
 
 
 class ResNet(Layer):
@@ -92,8 +93,11 @@ class ResNet(Layer):
             y = blk["c1"]([x], training=training, relu=True, want_fp32=False, want_p16=True, want_bf16=True)
             y = blk["c2"]([y], training=training, relu=True, want_fp32=False, want_p16=True)
             nxt_identity = not last and self.blocks[i + 1]["short"] is None       # the next unit reads x through its c1 and its identity skip only
+            # a stage's last unit: the next stage's stride-2 c1 and projection shortcut are the only readers, at the pixels (2i, 2j)
+            nxt = None if last else self.blocks[i + 1]
+            nxt_even = nxt is not None and nxt["short"] is not None and nxt["short"].stride == 2 and nxt["c1"].stride == 2
             x = blk["c3"]([y], training=training, relu=True, residual=sc, want_fp32=last, want_p16=not last,
-                          next_is_identity_unit=nxt_identity)                                 # BN -> Add([shortcut, x]) -> ReLU
+                          next_is_identity_unit=nxt_identity, next_reads_even_pixels=nxt_even)       # BN -> Add([shortcut, x]) -> ReLU
         return x
 
 

@@ -516,8 +516,20 @@ __global__ __launch_bounds__(256) void bn_apply_p16_kernel(const float* __restri
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            const void* __restrict__ residual, int residual_p16, bdetr_bn_affine rbn, int relu, float* __restrict__ out32,
                                                            void* __restrict__ out_f16, void* __restrict__ out_bf16, unsigned long long* __restrict__ relu_mask,
-                                                           int* __restrict__ overflow_flag, int64_t n4, int c4n) {
+                                                           int* __restrict__ overflow_flag, int64_t n4, int c4n, int eH, int eW) {
     // n4 is even and the stride is even: the two lanes of a pair (one 8-element group) always run together
+    // eH > 0: only the pixels (2h', 2w') of the [N, eH, eW] map are read and written - the output of a stage's last unit, which the next
+    // stage's stride-2 1x1 convolutions (and their weight gradients) read at those pixels alone.  n4 then counts the COMPACT index space
+    // [N, eH/2, eW/2, c4n]; `at` maps a compact index to the float4 index of its pixel in the full tensors, which is what every load,
+    // `body` and every store see.  (host: eH, eW even, c4n % 64 == 0 - an aligned 64-index group stays inside one pixel and keeps its
+    // position i & 63, so the wave's __ballot, the mask word it stores and the P16 lane pairs are those of the dense pass - and the
+    // full count < 2^32)
+    auto at = [&](int64_t k) -> int64_t {
+        if (eH <= 0) return k;
+        const unsigned ku = (unsigned)k, row = ku / (unsigned)c4n, cc = ku - row * (unsigned)c4n;
+        const unsigned w2 = (unsigned)eW >> 1, h2 = (unsigned)eH >> 1, w = row % w2, t = row / w2, h = t % h2, n = t / h2;
+        return (int64_t)((n * (unsigned)eH + 2u * h) * (unsigned)eW + 2u * w) * c4n + cc;
+    };
     struct Affine { f32x4 m, rs, g, b; };
     auto affine_of = [&](const float* pm, const float* prs, const float* pg, const float* pb, int c) {
         return Affine{*reinterpret_cast<const f32x4*>(pm + c), *reinterpret_cast<const f32x4*>(prs + c), *reinterpret_cast<const f32x4*>(pg + c), *reinterpret_cast<const f32x4*>(pb + c)};
@@ -580,21 +592,23 @@ __global__ __launch_bounds__(256) void bn_apply_p16_kernel(const float* __restri
         const Affine p = affine_of(mean, rstd, gamma, beta, c);
         const Affine p2 = rb ? affine_of(rbn.mean, rbn.rstd, rbn.gamma, rbn.beta, c) : p;
         for (; (i | 63) + stride < n4; i += 2 * stride) {
-            const f32x4 v0 = reinterpret_cast<const f32x4*>(x)[i], v1 = reinterpret_cast<const f32x4*>(x)[i + stride];
-            const f32x4 r0 = load_res(i), r1 = load_res(i + stride);
-            body(i, v0, r0, p, p2);
-            body(i + stride, v1, r1, p, p2);
+            const int64_t i0 = at(i), i1 = at(i + stride);
+            const f32x4 v0 = reinterpret_cast<const f32x4*>(x)[i0], v1 = reinterpret_cast<const f32x4*>(x)[i1];
+            const f32x4 r0 = load_res(i0), r1 = load_res(i1);
+            body(i0, v0, r0, p, p2);
+            body(i1, v1, r1, p, p2);
         }
-        for (; i < n4; i += stride) { const f32x4 v0 = reinterpret_cast<const f32x4*>(x)[i]; const f32x4 r0 = load_res(i); body(i, v0, r0, p, p2); }
+        for (; i < n4; i += stride) { const int64_t i0 = at(i); const f32x4 v0 = reinterpret_cast<const f32x4*>(x)[i0]; const f32x4 r0 = load_res(i0); body(i0, v0, r0, p, p2); }
         return;
     }
     for (; i < n4; i += stride) {
-        const int c = (int)(i % c4n) * 4;
+        const int c = (int)(i % c4n) * 4;              // (the channel group of a compact index is that of its pixel's index)
         const Affine p = affine_of(mean, rstd, gamma, beta, c);
         const Affine p2 = rb ? affine_of(rbn.mean, rbn.rstd, rbn.gamma, rbn.beta, c) : p;
-        const f32x4 v0 = reinterpret_cast<const f32x4*>(x)[i];
-        const f32x4 r0 = load_res(i);
-        body(i, v0, r0, p, p2);
+        const int64_t i0 = at(i);
+        const f32x4 v0 = reinterpret_cast<const f32x4*>(x)[i0];
+        const f32x4 r0 = load_res(i0);
+        body(i0, v0, r0, p, p2);
     }
 }
 
@@ -622,17 +636,21 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_p16_kernel(const float* __re
     struct In { f32x4 g, xv, o; unsigned pm; };
     auto load_in = [&](int64_t i) {
         In q;
+        bool masked = relu && !recompute;
         if (cH > 0) {
             const unsigned iu = (unsigned)i, row = iu / (unsigned)c4n, cc = iu - row * (unsigned)c4n;      // (host: n4 < 2^32 in this mode)
             const unsigned w = row % (unsigned)cW, t = row / (unsigned)cW, h = t % (unsigned)cH, n = t / (unsigned)cH;
             q.g = f32x4{0.f, 0.f, 0.f, 0.f};
             if (((h | w) & 1u) == 0u) q.g = reinterpret_cast<const f32x4*>(dout)[((int64_t)(n * (unsigned)(cH >> 1) + (h >> 1)) * (cW >> 1) + (w >> 1)) * c4n + cc];
+            // an odd pixel's g is zero whatever its mask says, and the forward may never have written that mask (bn_apply_p16_kernel eH > 0):
+            // it is not read - q.pm / q.o stay zero, which clears the zero
+            else masked = false;
         } else {
             q.g = reinterpret_cast<const f32x4*>(dout)[i];
         }
         q.xv = need_x ? reinterpret_cast<const f32x4*>(x)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
         q.o = f32x4{0.f, 0.f, 0.f, 0.f}; q.pm = 0u;
-        if (relu && !recompute) {
+        if (masked) {
             if (out_p16) q.pm = out_p16 == 2 ? relu_mask_bits4(out, i) : p16_positive4_bf16(out, i);
             else q.o = reinterpret_cast<const f32x4*>(out)[i];
         }
@@ -1000,20 +1018,44 @@ static int channel_aligned_grid(int64_t n4, int C) {
     return grid;
 }
 
-extern "C" int bdetr_bn_apply_p16(const float* x, const float* mean, const float* rstd, const float* gamma,
-                                  const float* beta, const void* residual, int residual_p16, const bdetr_bn_affine* residual_bn, int relu,
-                                  float* out32, void* out_f16, void* out_bf16,
-                                  uint64_t* relu_mask, int* overflow_flag, int64_t rows, int C, void* stream) {
+// even_h > 0: the even-pixel launch over an [rows / (even_h * even_w), even_h, even_w, C] map (bdetr_bn_apply_p16_even_pixels)
+static int bn_apply_p16_impl(const float* x, const float* mean, const float* rstd, const float* gamma,
+                             const float* beta, const void* residual, int residual_p16, const bdetr_bn_affine* residual_bn, int relu,
+                             float* out32, void* out_f16, void* out_bf16,
+                             uint64_t* relu_mask, int* overflow_flag, int64_t rows, int C, int even_h, int even_w, void* stream) {
     BDETR_CHECK_ARG(x && mean && rstd && gamma && beta && (out32 || out_f16 || out_bf16) && rows > 0 && C > 0 && C % 8 == 0,
                     "bdetr_bn_apply_p16: bad arguments (C %% 8 == 0 required)");
     BDETR_CHECK_ARG(residual_p16 != 2 || (residual && residual_bn && residual_bn->mean && residual_bn->rstd && residual_bn->gamma && residual_bn->beta),
                     "bdetr_bn_apply_p16: residual_p16 = 2 needs the raw shortcut tensor and its BatchNorm");
     const bdetr_bn_affine rbn = residual_p16 == 2 ? *residual_bn : bdetr_bn_affine{nullptr, nullptr, nullptr, nullptr};
-    const int64_t n4 = rows * C / 4;
+    int64_t n4 = rows * C / 4;
+    if (even_h > 0) {
+        // a wave's 64 float4 indices must lie in one pixel at the positions the dense pass gives them (ballot, mask words, lane pairs)
+        BDETR_CHECK_ARG(even_h % 2 == 0 && even_w % 2 == 0 && C % 256 == 0 && n4 < ((int64_t)1 << 32),
+                        "bdetr_bn_apply_p16_even_pixels: needs H and W even, C %% 256 == 0 and fewer than 2^32 float4s");
+        n4 /= 4;                                                   // the compact index space [N, H/2, W/2, C/4]
+    }
     const int grid = channel_aligned_grid(n4, C);
     hipLaunchKernelGGL(bn_apply_p16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma, beta, residual, residual_p16, rbn, relu,
-                       out32, out_f16, out_bf16, reinterpret_cast<unsigned long long*>(relu_mask), overflow_flag, n4, C / 4);
+                       out32, out_f16, out_bf16, reinterpret_cast<unsigned long long*>(relu_mask), overflow_flag, n4, C / 4, even_h, even_w);
     return bdetr_launch_status("bn_apply_p16");
+}
+
+extern "C" int bdetr_bn_apply_p16(const float* x, const float* mean, const float* rstd, const float* gamma,
+                                  const float* beta, const void* residual, int residual_p16, const bdetr_bn_affine* residual_bn, int relu,
+                                  float* out32, void* out_f16, void* out_bf16,
+                                  uint64_t* relu_mask, int* overflow_flag, int64_t rows, int C, void* stream) {
+    return bn_apply_p16_impl(x, mean, rstd, gamma, beta, residual, residual_p16, residual_bn, relu, out32, out_f16, out_bf16, relu_mask, overflow_flag,
+                             rows, C, 0, 0, stream);
+}
+
+extern "C" int bdetr_bn_apply_p16_even_pixels(const float* x, const float* mean, const float* rstd, const float* gamma,
+                                              const float* beta, const void* residual, int residual_p16, const bdetr_bn_affine* residual_bn, int relu,
+                                              float* out32, void* out_f16, void* out_bf16,
+                                              uint64_t* relu_mask, int* overflow_flag, int64_t rows, int C, int H, int W, void* stream) {
+    BDETR_CHECK_ARG(H > 0 && W > 0 && rows > 0 && rows % ((int64_t)H * W) == 0, "bdetr_bn_apply_p16_even_pixels: bad geometry (rows = N * H * W)");
+    return bn_apply_p16_impl(x, mean, rstd, gamma, beta, residual, residual_p16, residual_bn, relu, out32, out_f16, out_bf16, relu_mask, overflow_flag,
+                             rows, C, H, W, stream);
 }
 
 namespace {

@@ -348,11 +348,14 @@ def p16_pack_conv_weights(w, want_fwd=True, want_bwd=True):
 
 
 def bn_apply_p16(x2d, mean, rstd, gamma, beta, residual=None, relu=False, want_fp32=True, want_f16=True, want_bf16=True,
-                 residual_p16=False, want_mask=False, residual_bn=None):
+                 residual_p16=False, want_mask=False, residual_bn=None, even_pixels=None, zero_unwritten=False):
     """bn_apply with P16 outputs: returns (out32 | None, out_f16 | None, out_bf16 | None[, relu bit mask]).  residual_p16:
     `residual` is the f16 pair copy of the shortcut tensor.  residual_bn = (mean, rstd, gamma, beta): `residual` is the RAW
     output of the projection shortcut's convolution, normalised here.  want_mask: also return the 1-bit-per-element ReLU mask
-    (int64 words) the backward pass of a residual unit reads instead of the forward output."""
+    (int64 words) the backward pass of a residual unit reads instead of the forward output.
+    even_pixels = (H, W): the rows are an [N, H, W] map of which only the pixels (2i, 2j) are read and written (the outputs keep
+    their full shape; every other pixel and its mask words stay as allocated - or, with zero_unwritten, are zero-filled first: for
+    diagnostics that fingerprint whole tensors).  The library refuses odd maps and C % 256 != 0."""
     _chk(x2d, mean, rstd, gamma, beta, residual)
     rbn = None
     if residual_bn is not None:
@@ -365,8 +368,17 @@ def bn_apply_p16(x2d, mean, rstd, gamma, beta, residual=None, relu=False, want_f
     of = torch.empty_like(x2d) if want_f16 else None
     ob = torch.empty_like(x2d) if want_bf16 else None
     mask = torch.empty(((rows * Cc // 4 + 63) // 64) * 4, dtype=torch.int64, device=x2d.device) if want_mask else None
-    check(_lib.lib().bdetr_bn_apply_p16(_p(x2d), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(residual), int(residual_p16), rbn, int(relu), _p(o32),
-                                        _p(of), _p(ob), _p(mask), _p(overflow_flag()) if want_f16 else None, rows, Cc, _stream()), "bn_apply_p16")
+    args = (_p(x2d), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(residual), int(residual_p16), rbn, int(relu), _p(o32),
+            _p(of), _p(ob), _p(mask), _p(overflow_flag()) if want_f16 else None, rows, Cc)
+    if even_pixels is not None:
+        H, W = even_pixels
+        if zero_unwritten:
+            for t in (o32, of, ob, mask.view(torch.float32) if mask is not None else None):
+                if t is not None:
+                    zero_(t)
+        check(_lib.lib().bdetr_bn_apply_p16_even_pixels(*args, int(H), int(W), _stream()), "bn_apply_p16_even_pixels")
+    else:
+        check(_lib.lib().bdetr_bn_apply_p16(*args, _stream()), "bn_apply_p16")
     return (o32, of, ob, mask) if want_mask else (o32, of, ob)
 
 

@@ -161,6 +161,7 @@ P16_ENABLED = [os.environ.get("BDETR_P16", "1") != "0"]
 WGRAD_XF16 = os.environ.get("BDETR_WGRAD_XF16", "1") != "0"
 BF16_FOR_3X3 = os.environ.get("BDETR_BF16_3X3", "1") != "0"       # ... except in front of a 3x3 convolution (conv_bn want_bf16)
 EVEN_PIXELS = os.environ.get("BDETR_EVEN_PIXELS", "1") != "0"  # stage-last BatchNorm backward reduces over the even pixels only (_p16_bn_backward)
+EVEN_APPLY = os.environ.get("BDETR_EVEN_APPLY", "1") != "0"    # stage-last BatchNorm apply writes the even pixels only (_conv_bn_p16)
 LAZY_SKIP = os.environ.get("BDETR_LAZY_SKIP", "1") != "0"      # residual units hand their skip gradient on unmasked (_p16_bn_backward)
 BN_FUSE = os.environ.get("BDETR_BN_FUSE", "1") != "0"          # BatchNorm-backward sums in the consumer's backward-data epilogue (ActInfo.bn_ctx, bn_ctx_bits)
 BN_FUSE2 = os.environ.get("BDETR_BN_FUSE2", "1") != "0"        # ... also those of a deferred projection-shortcut BatchNorm (ActInfo.bn_ctx_bits2)
@@ -304,12 +305,16 @@ def _param_grads_task(w: Variable, b: Variable, write_dw, bias_from: Optional[to
 def conv_bn(x: torch.Tensor, w: Variable, b: Variable, bn: BNState, stride: int, pad: int, relu: bool,
             residual: Optional[torch.Tensor] = None, training: bool = False, bn_batch_stats: Optional[bool] = None,
             x_needs_grad: bool = True, want_fp32: bool = True, want_p16: bool = False, defer_apply: bool = False,
-            sole_consumer_is_identity_unit: bool = False, want_bf16: bool = False) -> torch.Tensor:
+            sole_consumer_is_identity_unit: bool = False, consumers_read_even_pixels: bool = False, want_bf16: bool = False) -> torch.Tensor:
     """Conv2D(+bias) -> BatchNormalization -> [+ residual] -> [ReLU]  (keras ResNet-50 block unit).
 
     sole_consumer_is_identity_unit (residual units): the only consumers of this output are the next unit's first 1x1
     convolution and its identity skip - the masked accumulate that completes this output's gradient there can then also do
     THIS unit's BatchNorm-backward reduction (ctx attached to the handle as `bn_ctx_bits`).
+    consumers_read_even_pixels (a stage's last unit): the only consumers of this output are stride-2 1x1 convolutions, which read the
+    pixels (2i, 2j) and nothing else - on the pre-split path with a P16-only output on an even map with C % 256 == 0 the BatchNorm apply
+    pass then reads and writes those pixels alone (EVEN_APPLY).  The handle keeps its full [N, H, W, C] shape; its other pixels, and
+    their ReLU mask words, hold whatever the allocation held.  Everything else takes the dense pass.
     defer_apply (projection shortcut, no ReLU, no residual; P16 path only): the statistics are reduced but the normalised
     tensor is not written - the returned handle is the RAW convolution output tagged `deferred_bn`, and the unit that takes
     it as `residual` applies both BatchNorms in its one pass (bn_apply_p16 residual_bn; as_fp32 is the fallback).
@@ -325,7 +330,7 @@ def conv_bn(x: torch.Tensor, w: Variable, b: Variable, bn: BNState, stride: int,
     use_batch = training if bn_batch_stats is None else bn_batch_stats
     if training and use_batch and _p16_active() and K.p16_supported(g):
         return _conv_bn_p16(x, w, b, bn, g, relu, residual, x_needs_grad, want_fp32, want_p16, defer_apply, sole_consumer_is_identity_unit,
-                            want_bf16)
+                            consumers_read_even_pixels, want_bf16)
     return _conv_bn_fp32(x, w, b, bn, g, relu, residual, use_batch, x_needs_grad)
 
 
@@ -370,7 +375,7 @@ def _conv_bn_backward_fp32(g_out, acc, x32, w: Variable, b: Variable, bn: BNStat
 
 
 def _conv_bn_p16(x, w: Variable, b: Variable, bn: BNState, g, relu: bool, residual, x_needs_grad: bool, want_fp32: bool, want_p16: bool,
-                 defer_apply: bool, sole_consumer_is_identity_unit: bool, want_bf16: bool) -> torch.Tensor:
+                 defer_apply: bool, sole_consumer_is_identity_unit: bool, consumers_read_even_pixels: bool, want_bf16: bool) -> torch.Tensor:
     """conv_bn on the pre-split operand path (training with batch statistics under the 'split' policy)."""
     ra = act_info(residual)
     res_p16, res_bn = ra.p16_only, ra.deferred_bn
@@ -387,9 +392,16 @@ def _conv_bn_p16(x, w: Variable, b: Variable, bn: BNState, g, relu: bool, residu
         out = y.view(g.N, g.OH, g.OW, g.K)               # (a fresh handle: y itself stays this unit's own tensor)
         _act_tag(out).deferred_bn = (mean, rstd, bn.gamma.value, bn.beta.value)
     else:
+        # the even-pixel pass: only where every reader of the output is known to take the pixels (2i, 2j) alone and the kernel admits the map
+        even = (g.OH, g.OW) if (consumers_read_even_pixels and EVEN_APPLY and not fp32_out and g.OH % 2 == 0 and g.OW % 2 == 0
+                                and g.K % 256 == 0) else None
+        from . import engine as _engine
+        # (diagnostic: engine.DebugLog fingerprints every layer's WHOLE output - the pixels the pass skips then hold zeros, not what the
+        # allocation held, so that an eager step and its replay still log the same words)
         out2d, of, ob, *rest = K.bn_apply_p16(y2d, mean, rstd, bn.gamma.value, bn.beta.value, res2d, relu, want_fp32=fp32_out, want_f16=want_p16,
                                               want_bf16=want_p16 and ((want_bf16 and BF16_FOR_3X3) or not WGRAD_XF16), residual_p16=res_p16,
-                                              want_mask=want_mask, residual_bn=res_bn)
+                                              want_mask=want_mask, residual_bn=res_bn, even_pixels=even,
+                                              zero_unwritten=even is not None and _engine._DEBUG_LOG[0] is not None)
         relu_bits = rest[0] if want_mask else None
         out = (out2d if fp32_out else of).view(g.N, g.OH, g.OW, g.K)
     if want_p16:

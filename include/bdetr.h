@@ -202,6 +202,16 @@ int bdetr_bn_apply_p16(const float* x, const float* mean, const float* rstd, con
                        const float* beta, const void* residual, int residual_p16, const bdetr_bn_affine* residual_bn, int relu, float* out32,
                        void* out_f16, void* out_bf16, uint64_t* relu_mask, int* overflow_flag, int64_t rows, int C,
                        void* stream);
+/* The same pass over the pixels (2i, 2j) of an [N,H,W,C] map alone (rows = N*H*W): the closing BatchNorm + Add + ReLU of a stage's last
+ * unit (keras ResNet50 conv2_block3_out, conv3_block4_out, conv4_block6_out), whose only readers are the next stage's stride-2 1x1
+ * convolutions conv{3,4,5}_block1_{0,1}_conv and their weight gradients.  Every tensor keeps its full [N,H,W,C] shape and layout; the odd
+ * pixels of x and residual are not read, those of out32 / out_f16 / out_bf16 and their relu_mask words are not written, and an even pixel
+ * gets exactly what bdetr_bn_apply_p16 gives it - a quarter of the bytes.  Requires H and W even, C % 256 == 0 (a wave's 64 float4s lie
+ * in one pixel: mask words and lane pairs are those of the dense pass) and rows*C/4 < 2^32; anything else is an argument error. */
+int bdetr_bn_apply_p16_even_pixels(const float* x, const float* mean, const float* rstd, const float* gamma,
+                                   const float* beta, const void* residual, int residual_p16, const bdetr_bn_affine* residual_bn, int relu,
+                                   float* out32, void* out_f16, void* out_bf16, uint64_t* relu_mask, int* overflow_flag, int64_t rows, int C,
+                                   int H, int W, void* stream);
 int bdetr_bn_bwd_p16(const float* dout, const void* out, int out_p16, const float* x, const float* mean,
                      const float* rstd, const float* gamma, const float* beta, int relu, int frozen,
                      float* dx32, void* dx_bf16, float* dgamma, float* dbeta, float* dresidual,
@@ -210,7 +220,9 @@ int bdetr_bn_bwd_p16(const float* dout, const void* out, int out_p16, const floa
  * epilogue that wrote dout (bdetr_p16_conv2d_bwd_data_bnstats); the reduction pass over dout and x is skipped. */
 /* The same for a dout [N,H,W,C] that is zero outside the pixels (2i, 2j): the gradient of a stage's last unit, which reaches it only
  * through the backward-data of the next stage's stride-2 1x1 convolutions (keras ResNet50 conv{3,4,5}_block1_{0,1}_conv).  The
- * reduction pass visits those N * ceil(H/2) * ceil(W/2) rows only - a quarter of the bytes; the apply pass is the dense one. */
+ * reduction pass visits those N * ceil(H/2) * ceil(W/2) rows only - a quarter of the bytes; the apply pass is the dense one.  With
+ * dout_compact neither pass reads the ReLU mask source at a pixel off (2i, 2j): its gradient is zero whatever the mask says, and after
+ * bdetr_bn_apply_p16_even_pixels that part of the mask was never written. */
 int bdetr_bn_bwd_p16_even_pixels(const float* dout, const void* out, int out_p16, const float* x, const float* mean,
                                  const float* rstd, const float* gamma, const float* beta, int relu, int frozen,
                                  float* dx32, void* dx_bf16, float* dgamma, float* dbeta, float* dresidual,

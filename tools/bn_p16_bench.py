@@ -37,3 +37,18 @@ for rows, C, n, nres in [(409600, 64, 6, 0), (409600, 256, 1, 3), (102400, 128, 
     d = bench(f"bwd (reduce + apply) bit mask    {rows}x{C}", lambda: k.bn_bwd_p16(dy, bits, x, mean, rstd, gamma, True, False, beta=beta, out_p16=2), 5 * T)
     tot += a * n + b * nres + c * n + d * nres
 print("model mix, isolated kernels: %.2f ms per step" % tot)
+
+# the closing pass of a stage's last unit (f16 pair residual -> f16 pair + bits, batch 16 at 640 x 640): every pixel against the pixels
+# (2i, 2j) the next stage's stride-2 1x1 convolutions read (even_pixels; 12 bytes per element of a quarter of the tensor)
+saved = 0.0
+for N, H, C in [(16, 160, 256), (16, 80, 512), (16, 40, 1024)]:
+    rows = N * H * H
+    x = torch.randn(rows, C, device="cuda")
+    mean, rstd, gamma, beta = [torch.rand(C, device="cuda") + 0.5 for _ in range(4)]
+    _, resf, _ = k.bn_apply_p16(torch.randn(rows, C, device="cuda"), mean, rstd, gamma, beta, None, True, want_fp32=False, want_bf16=False)
+    T = rows * C * 4
+    kw = dict(want_fp32=False, want_bf16=False, residual_p16=True, want_mask=True)
+    a = bench(f"stage end, dense       {N}x{H}x{H}x{C}", lambda: k.bn_apply_p16(x, mean, rstd, gamma, beta, resf, True, **kw), 3 * T)
+    b = bench(f"stage end, even pixels {N}x{H}x{H}x{C}", lambda: k.bn_apply_p16(x, mean, rstd, gamma, beta, resf, True, even_pixels=(H, H), **kw), 3 * T // 4)
+    saved += a - b
+print("stage ends, even-pixel apply: %.3f ms per step less" % saved)
