@@ -79,10 +79,10 @@ def __getattr__(name):
         from .boosted_model import BoostedDETR
         return BoostedDETR
     if name in ("SGD", "AdamW", "Adam", "CosineDecayRestarts", "ModelCheckpoint", "TerminateOnNaN", "TensorBoard", "latest_checkpoint", "DetectionAP",
-                "PanopticQuality"):
+                "PanopticQuality", "AttributeAP"):
         from . import training
         return getattr(training, name)
-    if name in ("DetectionEvaluator", "MaskEvaluator", "PanopticEvaluator"):
+    if name in ("DetectionEvaluator", "MaskEvaluator", "PanopticEvaluator", "AttributeEvaluator", "AttributeMaskEvaluator"):
         from . import evaluation
         return getattr(evaluation, name)
     raise AttributeError(name)

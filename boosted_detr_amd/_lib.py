@@ -223,6 +223,11 @@ SIGNATURES = {
     # K28: the run lengths, column-major, at the offsets the prefix sum of K27 gives
     "bdetr_mask_rle_count": (I, [P, P, P, I, I, I, I, P, P]),
     "bdetr_mask_rle_encode": (I, [P, P, P, P, I, I, I, I, L, P, P]),
+    # K29-K31 (csrc/attrmetric.hip): attribute-aware AP.  K29: attribute rows -> bit words, one ballot per word (>= 0.5, never
+    # <PAD> / <OOV>); K30 / K31: K16 / K17's matching with the attribute F1 gate, one workgroup per (image, range, F1 threshold)
+    "bdetr_attr_pack": (I, [P, L, I, P, P, P]),
+    "bdetr_det_match_attr": (I, [P] * 16 + [C.c_double] + [I] * 9 + [P] * 7),
+    "bdetr_mask_match_attr": (I, [P] * 18 + [C.c_double] + [I] * 10 + [P] * 7),
 }
 
 

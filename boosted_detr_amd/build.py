@@ -16,15 +16,16 @@ from pathlib import Path
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libbdetr.so"
 OBJ_DIR = CSRC / "_obj"
-SOURCES = ["common.cpp", "igemm.hip", "sgemm.hip", "hconv.hip", "hwgrad.hip", "p16.hip", "attention.hip", "rowchain.hip", "augment.hip", "norm.hip", "groupnorm_rows.hip", "elementwise.hip", "panoptic.hip", "matcher.hip", "optim.hip", "detmetric.hip", "maskmetric.hip", "maskraster.hip", "maskimage.hip", "panopticmerge.hip", "maskrle.hip"]
+SOURCES = ["common.cpp", "igemm.hip", "sgemm.hip", "hconv.hip", "hwgrad.hip", "p16.hip", "attention.hip", "rowchain.hip", "augment.hip", "norm.hip", "groupnorm_rows.hip", "elementwise.hip", "panoptic.hip", "matcher.hip", "optim.hip", "detmetric.hip", "maskmetric.hip", "maskraster.hip", "maskimage.hip", "panopticmerge.hip", "maskrle.hip", "attrmetric.hip"]
 ARCH = "gfx950"
 COMMON_FLAGS = ["-O3", "-fPIC", f"--offload-arch={ARCH}", "-std=c++20", "-Wall", "-Wno-unused-function"] + os.environ.get("BDETR_CXXFLAGS", "").split()
-# the matcher must not contract a*b+c into fma (scipy / numpy evaluate unfused); see matcher.hip.  detmetric.hip, maskmetric.hip
-# and maskimage.hip: the same, for the fp64 IoU of coco_match.h; maskraster.hip: for its one fp64 division; maskimage.hip and
+# the matcher must not contract a*b+c into fma (scipy / numpy evaluate unfused); see matcher.hip.  detmetric.hip, maskmetric.hip,
+# maskimage.hip and attrmetric.hip: the same, for the fp64 IoU of coco_match.h; maskraster.hip: for its one fp64 division; maskimage.hip and
 # panopticmerge.hip: for the fp64 bilinear rule of mask_upsample.h (every product and sum rounded on its own).  The two headers
 # switch contraction off themselves; the flags stay so that the files' own arithmetic does not depend on it either
 PER_FILE_FLAGS = {"matcher.hip": ["-ffp-contract=off"], "detmetric.hip": ["-ffp-contract=off"], "maskmetric.hip": ["-ffp-contract=off"],
-                  "maskraster.hip": ["-ffp-contract=off"], "maskimage.hip": ["-ffp-contract=off"], "panopticmerge.hip": ["-ffp-contract=off"]}
+                  "maskraster.hip": ["-ffp-contract=off"], "maskimage.hip": ["-ffp-contract=off"], "panopticmerge.hip": ["-ffp-contract=off"],
+                  "attrmetric.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -1,12 +1,15 @@
 // coco_match.h - COCOeval's greedy matching on gfx950, written once: every query becomes a detection (score, label), and per
 // image the detections are ranked, truncated per class and matched to the ground truths at every IoU threshold.  What is left
-// for the host is the accumulate over a few bytes per detection (evaluation.py).  Three translation units launch it:
+// for the host is the accumulate over a few bytes per detection (evaluation.py).  Four translation units launch it:
 //   detmetric.hip   K14 / K16  coco_match_kernel<box_iou, false / true>           IoU of box corners in fp64
 //   maskmetric.hip  K15 / K17  coco_match_kernel<words_iou, false / true>         popcounts of packed mask words in LDS
 //   maskimage.hip   K22        coco_match_kernel<inter_iou<STAGED>, true>         a precomputed inter [N,M] (K21), in LDS or in HBM
+//   attrmetric.hip  K30 / K31  coco_match_kernel<box_iou / words_iou, true, f1_gate>   K16 / K17 with the attribute F1 gate
 // `COCO` is the full protocol - crowd regions, area ranges, class ranks for several max_dets: the ignore class.  Without it the
 // phase loop, the ig words, the ground truths' flag bytes, class_rank, the area flags and the (B, A) grid are compiled out, so
 // the plain kernels keep their registers and their LDS.  An IoU source is a struct with only what differs (see box_iou).
+// `Gate` is one more test a ground truth has to pass to be a candidate (see no_gate / f1_gate); the default, no_gate, has an empty
+// source, no LDS and a pass() that is true, so for the five kernels without one the promise above covers the gate as well.
 //
 // Exactness does not depend on who includes this: no a*b+c below is contracted into an fma, so the fp64 IoU is the one an unfused
 // NumPy fp64 evaluation gives, bit for bit - a match decided at `iou >= threshold` flips on the last bit.  (build.py also passes
@@ -22,6 +25,8 @@ constexpr int MAX_M = 1024;      // ground-truth rows per image (16 matched bits
 constexpr int MAX_C = 65536;     // classes
 constexpr int MAX_T = 15;        // thresholds: bits 0..14 of tp_bits, bit 15 = keep
 constexpr int MAX_A = 4;         // area ranges
+constexpr int MAX_F = 16;        // F1 thresholds of the attribute gate: blockIdx.z
+constexpr int MAX_WA = 64;       // 64-bit words of an attribute set (4096 attributes)
 constexpr unsigned KEEP_BIT = 0x8000u;
 constexpr size_t LDS_LIMIT = 64 * 1024;      // the default dynamic LDS of a workgroup (no opt-in to the CU's 160 KiB)
 constexpr unsigned char F_KEEP = 1, F_OUT = 2;       // detection flags: kept; own area outside the range
@@ -34,24 +39,96 @@ struct match_thresholds {
     }
 };
 
-// The dynamic LDS of coco_match_kernel<Iou, COCO>, as byte offsets; the entry points size the launch with the same object the
+// A gate is a struct like an IoU source: `source` (its operands, a kernel argument), ON, its share of the LDS (TAIL_ALIGN, bytes),
+// stage(src, f, b, ...) (carve that share and fill it, before the kernel's first synchronise; f = blockIdx.z selects the gate's own
+// threshold), begin(d) (the per-detection set-up) and pass(m): whether ground truth m may be matched to detection d at all.
+struct no_gate {
+    struct source {};
+    static constexpr bool ON = false;
+    static constexpr unsigned TAIL_ALIGN = 1;
+    static __host__ __device__ size_t bytes(size_t, size_t, const source&) { return 0; }
+    __device__ __forceinline__ void stage(const source&, int, int, int, int, unsigned char*, int, int) {}
+    __device__ __forceinline__ void begin(int) {}
+    __device__ __forceinline__ bool pass(int) const { return true; }
+};
+
+// The attribute F1 gate (K30 / K31): det_attr [B,N,Wa] / det_count [B,N] and gt_attr [B,M,Wa] / gt_count [B,M] as bdetr_attr_pack
+// (K29) leaves them.  F1 = 2 tp / (count_d + count_g) with tp the popcount of the common bits: ONE IEEE fp64 division of exact
+// integers, as the mask IoU is, so equal rationals are equal doubles and 2 * 1 / (2 + 2) meets 0.5; two empty sets score empty_f1.
+// LDS: det words, gt words, then det counts, gt counts.
+struct f1_gate {
+    struct source {
+        const unsigned long long* det_attr;
+        const int32_t* det_count;
+        const unsigned long long* gt_attr;
+        const int32_t* gt_count;
+        int Wa;
+        double empty_f1;
+        double thr[MAX_F];
+    };
+    static constexpr bool ON = true;
+    static constexpr unsigned TAIL_ALIGN = 8;
+    static __host__ __device__ size_t bytes(size_t Np, size_t Mp, const source& src) { return (8 * (size_t)src.Wa + 4) * (Np + Mp); }
+
+    const unsigned long long *s_bits, *g_bits, *dw;
+    const int *s_cnt, *g_cnt;
+    int Wa, dcount;
+    double th, empty;
+
+    __device__ __forceinline__ void stage(const source& src, int f, int b, int N, int M, unsigned char* at, int tid, int nthr) {
+        const size_t Np = (size_t)((N + 3) & ~3), Mp = (size_t)((M + 3) & ~3);
+        Wa = src.Wa;
+        th = fmin(src.thr[f], 1.0 - 1e-10);
+        empty = src.empty_f1;
+        unsigned long long* sb = reinterpret_cast<unsigned long long*>(at);
+        unsigned long long* gb = sb + Np * Wa;
+        int* sc = reinterpret_cast<int*>(gb + Mp * Wa);
+        int* gc = sc + Np;
+        for (int k = tid; k < N * Wa; k += nthr) sb[k] = src.det_attr[(int64_t)b * N * Wa + k];
+        for (int k = tid; k < M * Wa; k += nthr) gb[k] = src.gt_attr[(int64_t)b * M * Wa + k];
+        for (int k = tid; k < N; k += nthr) sc[k] = src.det_count[(int64_t)b * N + k];
+        for (int k = tid; k < M; k += nthr) gc[k] = src.gt_count[(int64_t)b * M + k];
+        s_bits = sb;
+        g_bits = gb;
+        s_cnt = sc;
+        g_cnt = gc;
+    }
+    __device__ __forceinline__ void begin(int d) {
+        dw = s_bits + (size_t)d * Wa;
+        dcount = s_cnt[d];
+    }
+    __device__ __forceinline__ bool pass(int m) const {
+        const unsigned long long* gw = g_bits + (size_t)m * Wa;
+        int tp = 0;
+        for (int w = 0; w < Wa; ++w) tp += __popcll(dw[w] & gw[w]);
+        const int both = dcount + g_cnt[m];
+        const double f1 = both > 0 ? (double)(2 * tp) / (double)both : empty;
+        return f1 >= th;
+    }
+};
+
+// The dynamic LDS of coco_match_kernel<Iou, COCO, Gate>, as byte offsets; the entry points size the launch with the same object the
 // kernel carves with.  N and M are rounded up to 4, so every 4-byte carve is a multiple of 16 bytes:
 //   [0, words)       scores, labels, order, tp words (COCO: ig words) [N]; gt labels [M] (-1 = not a ground truth)
 //   [words, flags)   the source's 4- and 16-byte carves
-//   [flags, tail)    det flag bytes [N] (COCO: gt flag bytes [M]), rounded up to the source's TAIL_ALIGN
-//   [tail, total)    the source's 8-byte carves
+//   [flags, tail)    det flag bytes [N] (COCO: gt flag bytes [M]), rounded up to the source's (and the gate's) TAIL_ALIGN
+//   [tail, gate)     the source's 8-byte carves (with a gate rounded up to 8 bytes)
+//   [gate, total)    the gate's carves; nothing without one
 // The offsets are 32-bit on purpose (at most 61 KiB before the tail): from 64-bit arithmetic the compiler no longer sees the carves'
 // 16- and 8-byte alignment and splits a box's one 16-byte LDS read in the matching loop.  Only the tail's size can be large.
-template <class Iou, bool COCO>
+template <class Iou, bool COCO, class Gate = no_gate>
 struct carve {
     unsigned words, flags, tail;
-    size_t total;
-    __host__ __device__ carve(int N, int M, const typename Iou::source& src) {
+    size_t gate, total;
+    __host__ __device__ carve(int N, int M, const typename Iou::source& src, const typename Gate::source& gsrc = typename Gate::source()) {
+        constexpr unsigned ALIGN = Iou::TAIL_ALIGN > Gate::TAIL_ALIGN ? Iou::TAIL_ALIGN : Gate::TAIL_ALIGN;
         const unsigned Np = (unsigned)((N + 3) & ~3), Mp = (unsigned)((M + 3) & ~3);
         words = (COCO ? 20 : 16) * Np + 4 * Mp;
         flags = words + Iou::word_bytes(Np, Mp);
-        tail = flags + ((Np + (COCO ? Mp : 0) + Iou::TAIL_ALIGN - 1) & ~(Iou::TAIL_ALIGN - 1));
-        total = tail + Iou::tail_bytes(N, M, Np, Mp, src);
+        tail = flags + ((Np + (COCO ? Mp : 0) + ALIGN - 1) & ~(ALIGN - 1));
+        gate = tail + Iou::tail_bytes(N, M, Np, Mp, src);
+        if constexpr (Gate::ON) gate = (gate + 7) & ~(size_t)7;
+        total = gate + Gate::bytes(Np, Mp, gsrc);
     }
 };
 
@@ -230,8 +307,11 @@ struct inter_iou : pixel_counts {
 // Outputs: order [B,N]; tp_bits [B,N], matched_gt [B,T,N]; gt_count [C] is added to.  With COCO also class_rank [B,N], ig_bits, and
 // the per-range outputs gain a leading A: tp_bits / ig_bits [A,B,N], matched_gt [A,B,T,N], gt_count [A,C].  Without COCO gt_crowd,
 // gt_area, image_hw, area_ranges, class_rank and ig_bits are not read (null).
+// With a gate the grid is (B, A, F): blockIdx.z = f selects the gate's threshold, every (t, f) pair is matched on its own, and tp_bits /
+// ig_bits [F,A,B,N], matched_gt [F,A,B,T,N] gain a leading F.  order, class_rank and gt_count do not depend on f: the f = 0 workgroups
+// write them.
 // ---------------------------------------------------------------------------------------------------------------------
-template <class Iou, bool COCO>
+template <class Iou, bool COCO, class Gate = no_gate>
 __global__ __launch_bounds__(1024) void coco_match_kernel(typename Iou::source src, const float* __restrict__ score, const int32_t* __restrict__ label,
                                                           const int32_t* __restrict__ gt_label, const uint8_t* __restrict__ gt_crowd,
                                                           const float* __restrict__ gt_area, const int32_t* __restrict__ num_objects,
@@ -239,9 +319,10 @@ __global__ __launch_bounds__(1024) void coco_match_kernel(typename Iou::source s
                                                           match_thresholds thr, int B, int N, int M, int C, int T, int max_dets,
                                                           int32_t* __restrict__ order, int32_t* __restrict__ class_rank,
                                                           uint16_t* __restrict__ tp_bits, uint16_t* __restrict__ ig_bits,
-                                                          int32_t* __restrict__ matched_gt, int32_t* __restrict__ gt_count) {
+                                                          int32_t* __restrict__ matched_gt, int32_t* __restrict__ gt_count,
+                                                          typename Gate::source gsrc = typename Gate::source()) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const carve<Iou, COCO> at(N, M, src);
+    const carve<Iou, COCO, Gate> at(N, M, src, gsrc);
     const int Np = (N + 3) & ~3;
     float* s_score = reinterpret_cast<float*>(smem);
     int* s_label = reinterpret_cast<int*>(s_score + Np);
@@ -253,9 +334,10 @@ __global__ __launch_bounds__(1024) void coco_match_kernel(typename Iou::source s
     unsigned char* g_flag = s_flag + Np;                       // COCO only
 
     const int b = blockIdx.x, a = COCO ? blockIdx.y : 0, tid = threadIdx.x, nthr = blockDim.x;
+    const int gf = Gate::ON ? blockIdx.z : 0;      // the gate's threshold
     const int n_obj = max(0, min(num_objects[b], M));
     const int64_t dbase = (int64_t)b * N, gbase = (int64_t)b * M;
-    const int64_t abase = ((int64_t)a * B + b) * N;            // into tp_bits / ig_bits [A,B,N]
+    const int64_t abase = ((int64_t)(Gate::ON ? gf * (int)gridDim.y + a : a) * B + b) * N;      // into tp_bits / ig_bits [A,B,N] ([F,A,B,N])
     double scale = 0.0, lo = 0.0, hi = 0.0;
     if constexpr (COCO) {
         scale = (double)image_hw[2 * b] * (double)image_hw[2 * b + 1];
@@ -265,6 +347,8 @@ __global__ __launch_bounds__(1024) void coco_match_kernel(typename Iou::source s
 
     Iou iou;
     iou.stage(src, b, N, M, smem + at.words, smem + at.tail, tid, nthr);
+    Gate gate;
+    gate.stage(gsrc, gf, b, N, M, smem + at.gate, tid, nthr);
     for (int n = tid; n < N; n += nthr) {
         s_score[n] = score[dbase + n];
         s_label[n] = label[dbase + n];
@@ -290,7 +374,7 @@ __global__ __launch_bounds__(1024) void coco_match_kernel(typename Iou::source s
         }
         g_label[m] = real ? gl : -1;
         iou.stage_gt(m);
-        if (real && !ignore) atomicAdd(&gt_count[(int64_t)a * C + gl], 1);
+        if (real && !ignore && gf == 0) atomicAdd(&gt_count[(int64_t)a * C + gl], 1);
     }
     for (int64_t k = tid; k < (int64_t)T * N; k += nthr) matched_gt[abase * T + k] = -1;
     __syncthreads();
@@ -312,12 +396,12 @@ __global__ __launch_bounds__(1024) void coco_match_kernel(typename Iou::source s
         if constexpr (COCO) {
             const double ar = iou.det_area(n, scale);
             f |= (ar < lo || ar > hi) ? F_OUT : 0;
-            if (a == 0) class_rank[dbase + n] = crank;
+            if (a == 0 && gf == 0) class_rank[dbase + n] = crank;
         }
         s_flag[n] = f;
     }
     __syncthreads();
-    if (a == 0)
+    if (a == 0 && gf == 0)
         for (int n = tid; n < N; n += nthr) order[dbase + n] = s_order[n];
 
     const int wave = tid >> 6, lane = tid & 63;
@@ -330,6 +414,7 @@ __global__ __launch_bounds__(1024) void coco_match_kernel(typename Iou::source s
             if (d < 0 || !(s_flag[d] & F_KEEP)) continue;   // wave-uniform
             const int dl = s_label[d];
             iou.begin(d);
+            gate.begin(d);
             // phase 0: the non-ignored ground truths; phase 1 (COCO), only when phase 0 found none: the ignored ones (COCOeval sorts
             // the ignored ground truths last and breaks out of its scan on reaching them with a match in hand).  `phase` and `bestm`
             // after the butterfly are the same in every lane, so the whole wave takes the same path into each reduction.
@@ -347,7 +432,7 @@ __global__ __launch_bounds__(1024) void coco_match_kernel(typename Iou::source s
                     }
                     if (((taken >> k) & 1u) && !crowd) continue;
                     const double v = iou.iou(m, crowd);
-                    if (v >= th && v >= best) { best = v; bestm = m; }      // ascending m: on equal IoU the larger index stays
+                    if (v >= th && v >= best && gate.pass(m)) { best = v; bestm = m; }      // ascending m: on equal IoU the larger index stays
                 }
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) {

@@ -17,6 +17,9 @@ boundary rule of K18 (boundary pixels can differ from pycocotools' scan conversi
 project's own (bilinear in fp64, reproducible bit for bit; it agrees with torch's interpolate except within rounding of zero).  A
 query's mask shares its box's class and score (DETR's convention).
 
+``AttributeEvaluator`` / ``AttributeMaskEvaluator`` (K29-K31) score the third head: the full protocol with one more test for a true
+positive, the F1 of the predicted attribute set against the ground truth's, averaged over a grid of IoU and F1 thresholds.
+
 ``PanopticEvaluator`` (K23-K26) is the COCO panoptic task's PQ / SQ / RQ at image resolution: the kept queries' upsampled logits merged
 into one id per pixel, the ground truths made disjoint, panopticapi's matching in integers; ``accumulate_pq`` is its host half.
 
@@ -435,6 +438,135 @@ class CocoMaskEvaluator(CocoEvaluator):
         order, class_rank, tp_bits, ig_bits, matched = K.mask_match_coco(
             score, label, det_bits, det_pop, cat_ids.contiguous(), gt_bits, gt_pop, crowd, area, num_objects.reshape(-1).contiguous(), hw,
             self._ranges_dev, self.iou_thresholds, int(mask_logits.shape[2]), self.num_classes, self.max_dets[-1], self._gt_count)
+        self._kept.append((score, label, class_rank, tp_bits, ig_bits, order))
+        self.last_matched_gt = matched
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# attribute-aware AP: the IoU test AND an F1 test on the attribute sets (K29-K31)
+# ---------------------------------------------------------------------------------------------------------------------
+MAX_F1_THRESHOLDS = 16
+
+
+def accumulate_attr(records: Sequence[tuple], gt_count, iou_thresholds, f1_thresholds, max_dets, area_names) -> Dict[str, object]:
+    """accumulate_coco over what the K30 / K31 kernels left: the same per-range, per-max_det accumulate, run once per F1 threshold.
+
+    records: per batch, in arrival order, ``(score f32 [B,N], label i32 [B,N], class_rank i32 [B,N], tp_bits u16 [F,A,B,N], ig_bits u16
+    [F,A,B,N], order i32 [B,N])`` host arrays; gt_count [A,C] (it does not depend on f).  Every mean is COCO's mean over the entries
+    > -1 with f pooled into it: AP over all T x F, AP_IoU50 / AP_IoU75 over F at that IoU, AP_F1_50 / AP_F1_75 over T at that F1."""
+    thr = np.asarray(iou_thresholds, np.float64).reshape(-1)
+    f1 = np.asarray(f1_thresholds, np.float64).reshape(-1)
+    gt_count = np.asarray(gt_count, np.int64)
+    A, C = gt_count.shape
+    T, F, last = thr.size, f1.size, max_dets[-1]
+    lineups = [_Lineup([(s, l, cr, np.asarray(tp)[f], np.asarray(ig)[f], o) for s, l, cr, tp, ig, o in records], A) for f in range(F)]
+    base = [accumulate_pair(lineups[f], gt_count[0], T, 0, last) for f in range(F)]
+    base_p, base_r = np.stack([p for p, _ in base]), np.stack([r for _, r in base])            # [F,T,R,C], [F,T,C]
+
+    def where(values, value: float):
+        hit = np.flatnonzero(np.isclose(values, value, rtol=0.0, atol=1e-9))
+        return int(hit[0]) if hit.size else None
+
+    def at_iou(value: float) -> float:
+        t = where(thr, value)
+        return _mean_valid(base_p[:, t]) if t is not None else float("nan")
+
+    def at_f1(value: float) -> float:
+        f = where(f1, value)
+        return _mean_valid(base_p[f]) if f is not None else float("nan")
+
+    res = {"AP": _mean_valid(base_p), "AP_IoU50": at_iou(0.5), "AP_IoU75": at_iou(0.75), "AP_F1_50": at_f1(0.5), "AP_F1_75": at_f1(0.75)}
+    ranged = [[accumulate_pair(lineups[f], gt_count[a], T, a, last) for f in range(F)] for a in range(1, A)]
+    for name, per_f in zip(area_names[1:], ranged):
+        res[f"AP_{name}"] = _mean_valid(np.stack([p for p, _ in per_f]))
+    for m in max_dets:
+        res[f"AR_{m}"] = _mean_valid(base_r if m == last else np.stack([accumulate_pair(lineups[f], gt_count[0], T, 0, m)[1] for f in range(F)]))
+    for name, per_f in zip(area_names[1:], ranged):
+        res[f"AR_{name}"] = _mean_valid(np.stack([r for _, r in per_f]))
+    res["stats"] = [res[k] for k in list(res)]
+    valid = gt_count[0] > 0
+    res.update(AR=res[f"AR_{last}"], AP_table=[[_mean_valid(base_p[f, t]) for f in range(F)] for t in range(T)],
+               per_class_AP=np.asarray([_mean_valid(base_p[:, :, :, c]) for c in range(C)]), num_detections=int(lineups[0].scores.size),
+               num_ground_truths=int(gt_count[0][valid].sum()), num_images=int(sum(np.asarray(rec[0]).shape[0] for rec in records)),
+               gt_count=gt_count[0].copy(), gt_count_per_range=gt_count.copy())
+    return res
+
+
+class AttributeEvaluator(CocoEvaluator):
+    """Running attribute-aware box AP (Fashionpedia's AP_IoU+F1, in this project's own words - include/bdetr.h, K29-K31; not claimed
+    to equal fashionpedia-api bit for bit): CocoEvaluator with one more test for a true positive, the F1 of the detection's predicted
+    attribute set (probability >= 0.5, never <PAD> / <OOV>) against the ground truth's at each of F thresholds.  ``update`` launches
+    bdetr_det_postprocess, two bdetr_attr_pack (K29) and bdetr_det_match_attr (K30) on the current stream and reads nothing back; per
+    batch it keeps score / label / class_rank / order [B,N] and tp_bits / ig_bits [F,A,B,N] in HBM.  ``result`` makes one
+    device-to-host copy (it joins ``results``) and runs CocoEvaluator's accumulate per F1 threshold (``accumulate_attr``).
+    num_attributes counts <PAD> and <OOV>; both threshold grids default to 0.5:0.05:0.95; empty_f1: the F1 of two empty sets, 1.0
+    (they agree: many objects carry no attribute) or 0.0."""
+
+    def __init__(self, num_classes: int, num_attributes: int, iou_thresholds=None, f1_thresholds=None, empty_f1: float = 1.0,
+                 max_dets=(1, 10, 100), area_ranges=None):
+        from . import kernels as K
+        super().__init__(num_classes, iou_thresholds, max_dets, area_ranges)
+        f1 = np.linspace(0.5, 0.95, 10) if f1_thresholds is None else np.asarray(f1_thresholds, np.float64).reshape(-1)
+        if not 1 <= f1.size <= MAX_F1_THRESHOLDS:
+            raise ValueError(f"1 to {MAX_F1_THRESHOLDS} F1 thresholds, got {f1.size}")
+        if float(empty_f1) not in (0.0, 1.0):
+            raise ValueError(f"empty_f1 is the F1 of two empty attribute sets, 0.0 or 1.0, got {empty_f1}")
+        self.attr_words = K.attr_words(num_attributes)          # a ValueError outside [3, 4096]
+        self.num_attributes, self.f1_thresholds, self.empty_f1 = int(num_attributes), f1.astype(np.float64), float(empty_f1)
+
+    def _check_attributes(self, what: str, N: int, M: int, attribute_pred, attribute_hot, mask_words=None) -> None:
+        """Every refusal of the gate, before anything is launched."""
+        from . import kernels as K
+        for name, t, rows in (("attribute_pred", attribute_pred, N), ("attribute_hot", attribute_hot, M)):
+            if t.dim() != 3 or t.shape[1] != rows or t.shape[2] != self.num_attributes:
+                raise ValueError(f"{name} is {tuple(t.shape)}, expected [B,{rows},{self.num_attributes}]: the evaluator was built for "
+                                 f"{self.num_attributes} attributes")
+        K.check_attr_gate(what, N, M, self.attr_words, self.f1_thresholds, self.empty_f1, mask_words)
+
+    def update(self, cat_pred, attribute_pred, box_pred, cat_ids, attribute_hot, bbox, num_objects, iscrowd=None, area=None, image_hw=None) -> None:
+        """As CocoEvaluator.update, plus attribute_pred f32 [B,N,A] probabilities from ``Model.predict_raw`` and attribute_hot f32
+        [B,M,A], the multi-hot targets ``_prepare_targets`` returns (row m belonging to cat_ids row m).  All in HBM."""
+        from . import kernels as K
+        _check_classes(self.num_classes, cat_pred)
+        B, M = cat_ids.shape
+        self._check_attributes("AttributeEvaluator.update", cat_pred.shape[1], M, attribute_pred, attribute_hot)
+        crowd, area, hw = self._coco_operands(cat_pred.device, B, M, iscrowd, area, image_hw)
+        score, label = K.det_postprocess(cat_pred.contiguous())
+        det_attr, det_count = K.attr_pack(attribute_pred.contiguous())
+        gt_attr, gt_attr_count = K.attr_pack(attribute_hot.contiguous())
+        order, class_rank, tp_bits, ig_bits, matched = K.det_match_attr(
+            score, label, box_pred.contiguous(), det_attr, det_count, cat_ids.contiguous(), bbox.contiguous(), gt_attr, gt_attr_count, crowd, area,
+            num_objects.reshape(-1).contiguous(), hw, self._ranges_dev, self.iou_thresholds, self.f1_thresholds, self.empty_f1, self.num_classes,
+            self.max_dets[-1], self._gt_count)
+        self._kept.append((score, label, class_rank, tp_bits, ig_bits, order))
+        self.last_matched_gt = matched
+
+    def result_from(self, records: Sequence[tuple], gt_count) -> Dict[str, object]:
+        return accumulate_attr(records, gt_count, self.iou_thresholds, self.f1_thresholds, self.max_dets, self.area_names)
+
+
+class AttributeMaskEvaluator(AttributeEvaluator):
+    """Running attribute-aware mask AP on the panoptic head's grid: CocoMaskEvaluator's kernels with bdetr_mask_match_attr (K31) in
+    place of bdetr_mask_match_coco; what it keeps, and ``result``, are AttributeEvaluator's."""
+
+    LOGIT_THRESHOLD, TARGET_THRESHOLD = MaskEvaluator.LOGIT_THRESHOLD, MaskEvaluator.TARGET_THRESHOLD
+
+    def update(self, cat_pred, attribute_pred, mask_logits, cat_ids, attribute_hot, masks, num_objects, iscrowd=None, area=None, image_hw=None) -> None:
+        """As CocoMaskEvaluator.update, plus attribute_pred / attribute_hot as AttributeEvaluator.update takes them."""
+        from . import kernels as K
+        B, N, M, mask_logits, masks = grid_mask_operands(self.num_classes, cat_pred, mask_logits, cat_ids, masks)
+        P = int(mask_logits.shape[2])
+        self._check_attributes("AttributeMaskEvaluator.update", N, M, attribute_pred, attribute_hot, mask_words=(P + 63) // 64)
+        crowd, area, hw = self._coco_operands(cat_pred.device, B, M, iscrowd, area, image_hw)
+        score, label = K.det_postprocess(cat_pred.contiguous())
+        det_bits, det_pop = K.mask_binarize(mask_logits.contiguous(), self.LOGIT_THRESHOLD)
+        gt_bits, gt_pop = K.mask_binarize(masks.contiguous(), self.TARGET_THRESHOLD)
+        det_attr, det_count = K.attr_pack(attribute_pred.contiguous())
+        gt_attr, gt_attr_count = K.attr_pack(attribute_hot.contiguous())
+        order, class_rank, tp_bits, ig_bits, matched = K.mask_match_attr(
+            score, label, det_bits, det_pop, det_attr, det_count, cat_ids.contiguous(), gt_bits, gt_pop, gt_attr, gt_attr_count, crowd, area,
+            num_objects.reshape(-1).contiguous(), hw, self._ranges_dev, self.iou_thresholds, self.f1_thresholds, self.empty_f1, P,
+            self.num_classes, self.max_dets[-1], self._gt_count)
         self._kept.append((score, label, class_rank, tp_bits, ig_bits, order))
         self.last_matched_gt = matched
 

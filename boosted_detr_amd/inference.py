@@ -1,6 +1,6 @@
 """Inference and evaluation of a training.Model: raw predictions, detections, segmentations and the panoptic merge, and the loops
-of ``evaluate`` (box and mask AP, short and full COCO protocol), ``evaluate_panoptic`` (PQ) and ``coco_results`` (the entries of a
-COCO results file) over the evaluators of evaluation.py.
+of ``evaluate`` (box and mask AP, short and full COCO protocol), ``evaluate_panoptic`` (PQ), ``evaluate_attributes`` (AP with
+the attribute F1 gate) and ``coco_results`` (the entries of a COCO results file) over the evaluators of evaluation.py.
 ``Inference`` is a stateless base class of training.Model: it defines no __init__ and adds no attribute; what it reads
 (num_categories, num_object_preds, image_size, vocab_dict, _panoptic_inputs, panoptic_masks()) is the model's."""
 from __future__ import annotations
@@ -28,6 +28,15 @@ class Inference:
         cat_preds, _, box_preds = self.predict_raw(inputs)
         scores, labels = K.det_postprocess(cat_preds.contiguous())
         return {"scores": scores, "labels": labels, "boxes": box_preds}
+
+    def attribute_detections(self, inputs: dict) -> Dict[str, torch.Tensor]:
+        """detections(inputs) plus every query's predicted attribute set, in HBM: attributes int64 [B,N,Wa], the attribute
+        probabilities cut at >= 0.5 (the decode rule of InverseTokenization) and packed 64 to a word (bit a mod 64 of word a div 64;
+        <PAD> and <OOV>, indices 0 and 1, are never set; include/bdetr.h, K29), and attribute_count int32 [B,N], their set bits."""
+        cat_preds, attribute_preds, box_preds = self.predict_raw(inputs)
+        scores, labels = K.det_postprocess(cat_preds.contiguous())
+        bits, count = K.attr_pack(attribute_preds.contiguous())
+        return {"scores": scores, "labels": labels, "boxes": box_preds, "attributes": bits, "attribute_count": count}
 
     IOU_TYPES = ("bbox", "segm")
 
@@ -315,3 +324,53 @@ class Inference:
         keys = ("PQ", "SQ", "RQ")
         res = self._evaluation_loop("evaluate_panoptic", x, steps, per_batch, ev.result, keys, verbose)
         return res if return_dict else [res[k] for k in keys]
+
+    def evaluate_attributes(self, x: Iterable[dict], steps: Optional[int] = None, iou_types=("bbox",), evaluator=None, mask_evaluator=None,
+                            iou_thresholds=None, f1_thresholds=None, empty_f1: float = 1.0, return_dict: bool = True, verbose: int = 0):
+        """Attribute-aware AP over the batches of `x` (the dicts evaluate(coco=True) takes; 'attribute' is in every batch): the full COCO
+        protocol with one more test for a true positive - the F1 of the detection's predicted attribute set (probability >= 0.5)
+        against the matched ground truth's must reach an F1 threshold - averaged over a grid of IoU and F1 thresholds
+        (evaluation.AttributeEvaluator; csrc/attrmetric.hip, K29-K31).  The rule is modelled on Fashionpedia's AP_IoU+F1 and stated in
+        this project's own words; it is not claimed to equal fashionpedia-api bit for bit.  Per batch: an inference-mode forward
+        pass, bdetr_det_postprocess, two bdetr_attr_pack and the gated matcher, nothing read back; one device-to-host copy at the end.
+        Changes nothing, as evaluate(): weights, moving statistics, optimizer slots and counters, the step seed and what
+        panoptic_masks() answers for stay as they were.
+        iou_types: "bbox" (every model), "segm" (masks on the panoptic head's 23 x 23 grid; needs the head and inputs["masks"]) or both;
+        image-resolution masks with the gate are not built.  evaluator / mask_evaluator: an AttributeEvaluator / AttributeMaskEvaluator
+        (reset first; its own thresholds hold); otherwise one is built from iou_thresholds / f1_thresholds (both default to
+        0.5:0.05:0.95) and empty_f1, the F1 of two empty sets (1.0: they agree).  Returns the result() dict - AP (over all T x F),
+        AP_IoU50, AP_IoU75, AP_F1_50, AP_F1_75, AP_small ... AR_large, stats (those fourteen), AP_table [T][F], per_class_AP and the
+        counts; with "segm" the mask_ counterparts beside them - or with return_dict=False stats, followed by mask_stats."""
+        from .model import _prepare_masks, _prepare_targets
+        types = self._check_iou_types(iou_types)
+        if "segm" in types:
+            self._require_panoptic_head()
+        args = (self.num_attributes, iou_thresholds, f1_thresholds, empty_f1)
+        box_ev = mask_ev = None
+        if "bbox" in types:
+            box_ev = self._fresh_evaluator(evaluator, evaluation.AttributeEvaluator, "evaluate_attributes needs an AttributeEvaluator as evaluator", *args)
+            if isinstance(box_ev, evaluation.AttributeMaskEvaluator):
+                raise ValueError("evaluate_attributes needs an AttributeEvaluator as evaluator, not its mask form")
+        if "segm" in types:
+            mask_ev = self._fresh_evaluator(mask_evaluator, evaluation.AttributeMaskEvaluator,
+                                            "evaluate_attributes needs an AttributeMaskEvaluator as mask_evaluator", *args)
+
+        def per_batch(batch: dict) -> None:
+            cat_ids, attribute_hot, bbox, num_objects = _prepare_targets(self, batch)
+            masks = _prepare_masks(batch, bbox.shape[0], bbox.shape[1]) if mask_ev is not None else None
+            coco_fields = self._coco_fields(batch, bbox.shape[0], bbox.shape[1])      # (iscrowd, area, image_hw)
+            cat_preds, attribute_preds, box_preds = self.predict_raw(batch)
+            if box_ev is not None:
+                box_ev.update(cat_preds, attribute_preds, box_preds, cat_ids, attribute_hot, bbox, num_objects, *coco_fields)
+            if mask_ev is not None:
+                mask_ev.update(cat_preds, attribute_preds, self.panoptic_masks(), cat_ids, attribute_hot, masks, num_objects, *coco_fields)
+
+        def result() -> dict:
+            parts = evaluation.results([ev for ev in (box_ev, mask_ev) if ev is not None])      # one copy for both
+            counts = ("num_detections", "num_ground_truths", "num_images", "gt_count", "gt_count_per_range")
+            return parts[0] if mask_ev is None else self._with_mask_result(parts[0] if box_ev is not None else None, parts[-1], counts)
+
+        prefixes = [p for p, ev in (("", box_ev), ("mask_", mask_ev)) if ev is not None]
+        keys = [p + k for p in prefixes for k in ("AP", "AP_IoU50", "AP_F1_50", "AR")]
+        res = self._evaluation_loop("evaluate_attributes", x, steps, per_batch, result, keys, verbose)
+        return res if return_dict else [v for p in prefixes for v in res[p + "stats"]]

@@ -1247,6 +1247,148 @@ def mask_match_coco(score, label, det_bits, det_pop, gt_label, gt_bits, gt_pop, 
 
 
 # --------------------------------------------------------------------------------------
+# attribute-aware AP - csrc/attrmetric.hip (K29-K31)
+# --------------------------------------------------------------------------------------
+ATTR_MAX, ATTR_MAX_F1_THRESHOLDS, MATCH_LDS_LIMIT = 4096, 16, 64 * 1024
+
+
+def attr_words(num_attributes: int) -> int:
+    """Wa, the 64-bit words of an attribute set; a ValueError outside K29's limits (3 <= A <= 4096)."""
+    A = int(num_attributes)
+    if not 3 <= A <= ATTR_MAX:
+        raise ValueError(f"attr_pack: num_attributes counts <PAD> and <OOV> and must be in [3, {ATTR_MAX}], got {A}")
+    return (A + 63) // 64
+
+
+def attr_match_lds_bytes(N: int, M: int, Wa: int, mask_words: Optional[int] = None) -> int:
+    """The dynamic LDS a workgroup of K30 (mask_words None) or K31 (mask_words = W) needs: include/bdetr.h's formulas."""
+    Np, Mp = (int(N) + 3) & ~3, (int(M) + 3) & ~3
+    own = 36 * Np + 20 * Mp if mask_words is None else 24 * Np + 8 * Mp + 8 * int(mask_words) * (Np + Mp)
+    return own + ((Np + Mp + 7) & ~7) + (8 * int(Wa) + 4) * (Np + Mp)
+
+
+def check_attr_gate(what: str, N: int, M: int, Wa: int, f1_thresholds, empty_f1, mask_words: Optional[int] = None):
+    """Every refusal of the gate that needs no device, as ValueError: F in [1, 16], empty_f1 0 or 1, Wa in [1, 64] and the staging
+    within 64 KiB.  Returns (f1 thresholds as contiguous fp64, F, empty_f1 as float)."""
+    f1 = np.ascontiguousarray(f1_thresholds, np.float64).reshape(-1)
+    if not 1 <= f1.size <= ATTR_MAX_F1_THRESHOLDS:
+        raise ValueError(f"{what}: 1 to {ATTR_MAX_F1_THRESHOLDS} F1 thresholds, got {f1.size}")
+    if float(empty_f1) not in (0.0, 1.0):
+        raise ValueError(f"{what}: empty_f1 is the F1 of two empty attribute sets, 0.0 or 1.0, got {empty_f1}")
+    if not 1 <= int(Wa) <= ATTR_MAX // 64:
+        raise ValueError(f"{what}: attribute sets have 1 to {ATTR_MAX // 64} words, got {Wa}")
+    need = attr_match_lds_bytes(N, M, Wa, mask_words)
+    if need > MATCH_LDS_LIMIT:
+        raise ValueError(f"{what}: N={N} M={M} Wa={Wa}" + ("" if mask_words is None else f" W={mask_words}") + f" need {need} bytes of LDS per "
+                         f"image, {(8 * int(Wa) + 4) * (((N + 3) & ~3) + ((M + 3) & ~3))} of them the attribute sets; the limit is {MATCH_LDS_LIMIT}")
+    return f1, int(f1.size), float(empty_f1)
+
+
+def attr_pack(x):
+    """x [..., A] fp32 (attribute probabilities, or the tokenizer's multi-hot targets) -> (bits int64 [..., ceil(A/64)], count int32
+    [...]) (include/bdetr.h, K29): bit a mod 64 of word a div 64 is a >= 2 and x[a] >= 0.5 (the reference's decode rule; NaN: false;
+    <PAD> and <OOV> are never an attribute), the tail word's unused bits are zero, count = the row's set bits.  int64 holds the
+    uint64 bit pattern."""
+    _dtypes("attr_pack", x=(x, torch.float32))
+    if x.dim() < 1 or x.numel() == 0:
+        raise _lib.BdetrError(f"attr_pack: x must be [..., A] with at least one element, got {tuple(x.shape)}")
+    A = x.shape[-1]
+    Wa = attr_words(A)
+    _chk(x)
+    lead = tuple(x.shape[:-1])
+    bits = empty(*lead, Wa, like=x, dtype=torch.int64)
+    count = empty(*lead, like=x, dtype=torch.int32)
+    check(_lib.lib().bdetr_attr_pack(_p(x), x.numel() // A, A, _p(bits), _p(count), _stream()), "attr_pack")
+    return bits, count
+
+
+def _attr_operands(what: str, B: int, N: int, M: int, det_attr, det_count, gt_attr, gt_attr_count) -> int:
+    """The gate's operands, checked; returns Wa."""
+    _dtypes(what, det_attr=(det_attr, torch.int64), det_count=(det_count, torch.int32), gt_attr=(gt_attr, torch.int64),
+            gt_attr_count=(gt_attr_count, torch.int32))
+    if det_attr.dim() != 3:
+        raise _lib.BdetrError(f"{what}: det_attr must be [B,N,Wa]")
+    Wa = int(det_attr.shape[2])
+    if tuple(det_attr.shape) != (B, N, Wa) or tuple(det_count.shape) != (B, N) or tuple(gt_attr.shape) != (B, M, Wa) \
+            or tuple(gt_attr_count.shape) != (B, M):
+        raise _lib.BdetrError(f"{what}: operand shapes disagree (det_attr [B,N,Wa], det_count [B,N], gt_attr [B,M,Wa], gt_attr_count [B,M])")
+    return Wa
+
+
+def _match_outputs_attr(score, thresholds, A: int, F: int):
+    """_match_outputs with the leading F of the gated kernels: tp_bits / ig_bits [F,A,B,N], matched_gt [F,A,B,T,N]."""
+    B, N = score.shape
+    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
+    T = int(thr.size)
+    order = empty(B, N, like=score, dtype=torch.int32)
+    class_rank = empty(B, N, like=score, dtype=torch.int32)
+    tp_bits = empty(F, max(A, 1), B, N, like=score, dtype=torch.int16)
+    ig_bits = empty(F, max(A, 1), B, N, like=score, dtype=torch.int16)
+    matched = empty(F, max(A, 1), B, max(T, 1), N, like=score, dtype=torch.int32)
+    return thr, T, order, class_rank, tp_bits, ig_bits, matched
+
+
+def det_match_attr(score, label, box_pred, det_attr, det_count, gt_label, gt_box, gt_attr, gt_attr_count, gt_crowd, gt_area, num_objects,
+                   image_hw, area_ranges, thresholds, f1_thresholds, empty_f1, num_classes: int, max_dets: int, gt_count):
+    """det_match_coco with the attribute F1 gate (include/bdetr.h, K30): det_attr int64 [B,N,Wa] / det_count int32 [B,N] and gt_attr
+    int64 [B,M,Wa] / gt_attr_count int32 [B,M] as attr_pack returns them; f1_thresholds: host fp64 values (F of them); empty_f1: the
+    F1 of two empty sets, 0.0 or 1.0.  Everything else as det_match_coco.  Returns (order int32 [B,N], class_rank int32 [B,N], tp_bits
+    int16 [F,A,B,N], ig_bits int16 [F,A,B,N] - uint16 bit patterns - and matched_gt int32 [F,A,B,T,N]).  A gate outside the limits
+    (F, empty_f1, Wa, the LDS staging) is a ValueError before anything is launched."""
+    if score.dim() != 2 or gt_label.dim() != 2 or det_attr.dim() != 3:
+        raise _lib.BdetrError("det_match_attr: operand shapes disagree (score [B,N], gt_label [B,M], det_attr [B,N,Wa])")
+    B, N = score.shape
+    M = gt_label.shape[1]
+    f1, F, empty_f1 = check_attr_gate("det_match_attr", N, M, det_attr.shape[2], f1_thresholds, empty_f1)
+    Wa = _attr_operands("det_match_attr", B, N, M, det_attr, det_count, gt_attr, gt_attr_count)
+    _chk(score, box_pred, gt_box)
+    _chk(label, gt_label, num_objects, det_count, gt_attr_count, dtype=torch.int32)
+    _chk(det_attr, gt_attr, dtype=torch.int64)
+    if tuple(label.shape) != (B, N) or tuple(box_pred.shape) != (B, N, 4) or tuple(gt_label.shape) != (B, M) or tuple(gt_box.shape) != (B, M, 4) \
+            or num_objects.numel() != B:
+        raise _lib.BdetrError("det_match_attr: operand shapes disagree")
+    A = _coco_operands("det_match_attr", B, M, gt_crowd, gt_area, image_hw, area_ranges, gt_count, int(num_classes))
+    thr, T, order, class_rank, tp_bits, ig_bits, matched = _match_outputs_attr(score, thresholds, A, F)
+    check(_lib.lib().bdetr_det_match_attr(_p(score), _p(label), _p(box_pred), _p(det_attr), _p(det_count), _p(gt_label), _p(gt_box), _p(gt_attr),
+                                          _p(gt_attr_count), _p(gt_crowd), _p(gt_area), _p(num_objects), _p(image_hw), _p(area_ranges),
+                                          thr.ctypes.data, f1.ctypes.data, empty_f1, B, N, M, int(num_classes), Wa, T, F, A, int(max_dets),
+                                          _p(order), _p(class_rank), _p(tp_bits), _p(ig_bits), _p(matched), _p(gt_count), _stream()),
+          "det_match_attr")
+    return order, class_rank, tp_bits, ig_bits, matched
+
+
+def mask_match_attr(score, label, det_bits, det_pop, det_attr, det_count, gt_label, gt_bits, gt_pop, gt_attr, gt_attr_count, gt_crowd, gt_area,
+                    num_objects, image_hw, area_ranges, thresholds, f1_thresholds, empty_f1, num_pixels: int, num_classes: int, max_dets: int,
+                    gt_count):
+    """mask_match_coco with the attribute F1 gate (include/bdetr.h, K31): the gate's operands and what is returned as det_match_attr,
+    everything else as mask_match_coco."""
+    _dtypes("mask_match_attr", score=(score, torch.float32), label=(label, torch.int32), det_bits=(det_bits, torch.int64),
+            det_pop=(det_pop, torch.int32), gt_label=(gt_label, torch.int32), gt_bits=(gt_bits, torch.int64), gt_pop=(gt_pop, torch.int32),
+            num_objects=(num_objects, torch.int32))
+    if score.dim() != 2 or gt_label.dim() != 2 or det_bits.dim() != 3 or getattr(det_attr, "dim", lambda: 0)() != 3:
+        raise _lib.BdetrError("mask_match_attr: operand shapes disagree (score [B,N], gt_label [B,M], det_bits [B,N,W], det_attr [B,N,Wa])")
+    B, N = score.shape
+    M, W = gt_label.shape[1], det_bits.shape[2]
+    P = int(num_pixels)
+    f1, F, empty_f1 = check_attr_gate("mask_match_attr", N, M, det_attr.shape[2], f1_thresholds, empty_f1, mask_words=W)
+    Wa = _attr_operands("mask_match_attr", B, N, M, det_attr, det_count, gt_attr, gt_attr_count)
+    if tuple(label.shape) != (B, N) or tuple(det_bits.shape) != (B, N, W) or tuple(det_pop.shape) != (B, N) or tuple(gt_label.shape) != (B, M) \
+            or tuple(gt_bits.shape) != (B, M, W) or tuple(gt_pop.shape) != (B, M) or num_objects.numel() != B or W != (P + 63) // 64:
+        raise _lib.BdetrError("mask_match_attr: operand shapes disagree")
+    A = _coco_operands("mask_match_attr", B, M, gt_crowd, gt_area, image_hw, area_ranges, gt_count, int(num_classes))
+    _chk(score)
+    _chk(label, det_pop, gt_label, gt_pop, num_objects, det_count, gt_attr_count, dtype=torch.int32)
+    _chk(det_bits, gt_bits, det_attr, gt_attr, dtype=torch.int64)
+    thr, T, order, class_rank, tp_bits, ig_bits, matched = _match_outputs_attr(score, thresholds, A, F)
+    check(_lib.lib().bdetr_mask_match_attr(_p(score), _p(label), _p(det_bits), _p(det_pop), _p(det_attr), _p(det_count), _p(gt_label), _p(gt_bits),
+                                           _p(gt_pop), _p(gt_attr), _p(gt_attr_count), _p(gt_crowd), _p(gt_area), _p(num_objects), _p(image_hw),
+                                           _p(area_ranges), thr.ctypes.data, f1.ctypes.data, empty_f1, B, N, M, P, int(num_classes), Wa, T, F, A,
+                                           int(max_dets), _p(order), _p(class_rank), _p(tp_bits), _p(ig_bits), _p(matched), _p(gt_count),
+                                           _stream()), "mask_match_attr")
+    return order, class_rank, tp_bits, ig_bits, matched
+
+
+# --------------------------------------------------------------------------------------
 # mask targets from COCO segmentations - csrc/maskraster.hip (K18)
 # --------------------------------------------------------------------------------------
 MASK_KIND_NONE, MASK_KIND_POLY, MASK_KIND_RLE = 0, 1, 2

@@ -10,6 +10,7 @@ load_weights(latest_checkpoint)); semantics SURVEY S14/S15.
 from __future__ import annotations
 
 import contextlib
+import gc
 import glob
 import math
 import os
@@ -700,6 +701,27 @@ class PanopticQuality(_HeldOutMetric):
         return {f"val_{k}": float(res[k]) for k in ("PQ", "SQ", "RQ")}
 
 
+class AttributeAP(_HeldOutMetric):
+    """Attribute-aware AP on a held-out set at the end of an epoch: Model.evaluate_attributes over `validation_data` (at most `steps`
+    batches), every `every` epochs; adds every scalar of the result under val_attr_ to that epoch's logs - val_attr_AP,
+    val_attr_AP_IoU50, val_attr_AP_IoU75, val_attr_AP_F1_50, val_attr_AP_F1_75, val_attr_AP_small ... val_attr_AR_large,
+    val_attr_AR and, with "segm", the val_attr_mask_ counterparts.  Like DetectionAP it leaves the model as it found it; put it before
+    the callbacks that write the logs.  evaluator / mask_evaluator / iou_types / iou_thresholds / f1_thresholds / empty_f1: as
+    Model.evaluate_attributes'."""
+
+    def __init__(self, validation_data, every: int = 1, steps: Optional[int] = None, evaluator=None, iou_types=("bbox",), mask_evaluator=None,
+                 iou_thresholds=None, f1_thresholds=None, empty_f1: float = 1.0):
+        super().__init__(validation_data, every, steps, evaluator)
+        self.iou_types, self.mask_evaluator = Model._check_iou_types(iou_types), mask_evaluator
+        self.iou_thresholds, self.f1_thresholds, self.empty_f1 = iou_thresholds, f1_thresholds, float(empty_f1)
+
+    def measure(self) -> Dict[str, float]:
+        res = self.model.evaluate_attributes(self.validation_data, steps=self.steps, iou_types=self.iou_types, evaluator=self.evaluator,
+                                             mask_evaluator=self.mask_evaluator, iou_thresholds=self.iou_thresholds,
+                                             f1_thresholds=self.f1_thresholds, empty_f1=self.empty_f1)
+        return {f"val_attr_{k}": float(v) for k, v in res.items() if isinstance(v, float) and k.startswith(("AP", "AR", "mask_AP", "mask_AR"))}
+
+
 def latest_checkpoint(checkpoint_dir: str) -> Optional[str]:
     files = sorted(glob.glob(os.path.join(checkpoint_dir, "*.safetensors")), key=os.path.getmtime)
     return files[-1] if files else None
@@ -1167,6 +1189,15 @@ class Model(Layer, Inference):
             if self._dp is not None:
                 self._dp.drain()                             # no eager collective in flight when the first segment's capture opens
             cap = engine.SegmentedCapture()
+            # No cyclic garbage collection while a capture is open.  A retired model is a reference cycle (Model <-> RangeGuard) that
+            # owns its captured graphs and their private pools, and only the cyclic collector frees it - whenever its allocation
+            # counters say so.  A pass that lands inside this capture destroys those graphs on the capturing thread, their pools are
+            # released with hipFree, HIP refuses that during a capture, and the error surfaces in a destructor: the process aborts.
+            # torch.cuda.graph no longer collects on entry, so collect here, while it is legal, and keep the collector off until
+            # the last segment is closed.
+            gc_was_on = gc.isenabled()
+            gc.collect()
+            gc.disable()
             engine.set_capture(cap)
             prev_launch = K.set_launch_stream(None)
             try:
@@ -1181,7 +1212,9 @@ class Model(Layer, Inference):
             finally:
                 engine.set_capture(None)
                 K.set_launch_stream(prev_launch)
-            cap.done = []                                    # the deferred closures kept the crossing tensors alive during the capture
+                if gc_was_on:
+                    gc.enable()
+            cap.done = []                                  # the deferred closures kept the crossing tensors alive during the capture
             if cap.CENSUS:
                 self._graph_census = cap.census()            # raises if a memset / memcpy node entered the captured step
             self.steps_done, self.optimizer.iterations = keep         # capturing is not a step

@@ -686,7 +686,8 @@ int bdetr_adamw_clipnorm(const uint64_t* ptrs, const int64_t* sizes, int ntensor
 /* ------------------------------------------------------------------------
  * K14  detection metric: COCO-style box AP without a host hop per batch (csrc/detmetric.hip; evaluation.py accumulates).
  *   The matching of K14-K17 and K22 is ONE kernel, csrc/coco_match.h: the five entries differ in where an IoU comes from and in
- *   whether the ignore class (K16) is compiled in, nothing else.
+ *   whether the ignore class (K16) is compiled in, nothing else.  (K30 and K31 are the same kernel again, with the attribute F1
+ *   gate as one more compile-time parameter.)
  *   The reference has no evaluation at all; the rule restated here is pycocotools' COCOeval.evaluateImg for the no-crowd,
  *   all-areas case with one max_dets.
  *   bdetr_det_postprocess : cat_pred [B,N,C] probabilities -> label[B,N] = first-max argmax over classes 2 .. C-1 (0 = <PAD>, "no
@@ -984,6 +985,63 @@ int bdetr_mask_rle_count(const uint64_t* bits, const int32_t* image_hw, const ui
                          int32_t* n_counts, void* stream);
 int bdetr_mask_rle_encode(const uint64_t* bits, const int32_t* image_hw, const uint8_t* keep, const int64_t* offset, int B, int N, int Hm,
                           int Wm, int64_t total, int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------
+ * K29-K31  attribute-aware detection AP: AP with a joint constraint (csrc/attrmetric.hip; evaluation.AttributeEvaluator and
+ *   AttributeMaskEvaluator accumulate).  Additions to ABI 8: nothing that existed changed.  A detection is a true positive only
+ *   when its IoU with a ground truth reaches the IoU threshold AND the F1 of its predicted attribute set against that ground
+ *   truth's reaches an F1 threshold; the result is averaged over a grid of both.  The rule is modelled on Fashionpedia's evaluation
+ *   (COCOeval with an F1 gate, its AP_IoU+F1) and is stated here in this project's own words, as K18 and K19 are: it is NOT claimed
+ *   to equal fashionpedia-api bit for bit.
+ *
+ * K29  bdetr_attr_pack: x float [rows,A] -> bits uint64 [rows,Wa], Wa = ceil(A / 64), and count int32 [rows].  The rows are
+ *   attribute probabilities [B N, A] or the multi-hot targets [B M, A] the tokenizer leaves.  Bit (a mod 64) of word (a div 64) is
+ *   set when a >= 2 and x[a] >= 0.5f - the reference's decode rule (InverseTokenization), not bdetr_mask_binarize's `>` -; NaN: not
+ *   set; indices 0 (<PAD>) and 1 (<OOV>) are never an attribute; the bits at and past A are zero; count = the row's set bits.  One
+ *   wave per row: the wave's 64-bit ballot of the predicate IS the word.  Limits: rows >= 1, 3 <= A <= 4096.
+ *
+ *   F1 of detection d against ground truth m, on K29's words and counts:
+ *       tp = sum over w of popcount(d[w] & g[w]);  F1 = (double)(2 tp) / (double)(count_d + count_g): ONE IEEE fp64 division of
+ *       exact integers, so equal rationals are equal doubles - 2 * 1 / (2 + 2) meets 0.5 and 2 * 3 / (4 + 4) meets 0.75;
+ *       count_d + count_g == 0 (both sets empty): F1 = empty_f1, 0.0 or 1.0 (1.0: two empty sets agree);
+ *       the gate at F1 threshold f: F1 >= min(f1_thresholds[f], 1 - 1e-10), the form the IoU test has.
+ *
+ * K30  bdetr_det_match_attr: K16's bdetr_det_match_coco with the gate (the same kernel, csrc/coco_match.h, with one more
+ *   compile-time parameter).  A ground truth is a candidate for a detection at (t, f) only if it passes K16's tests AND the gate -
+ *   whether it is ignored, crowd or neither.  Among the candidates nothing changes: non-ignored before ignored, the largest IoU,
+ *   the larger row on equal IoU, a crowd is reusable, an unmatched detection with its own area outside the range is ignored.
+ *   Every (t, f) pair is matched on its own.  Grid (B, A, F): one workgroup per image, area range and F1 threshold, one wave per
+ *   IoU threshold; the attribute words and counts of the image's N detections and M ground truths are staged in LDS beside the
+ *   boxes.
+ *   Inputs beyond K16: det_attr uint64 [B,N,Wa] / det_count int32 [B,N] and gt_attr uint64 [B,M,Wa] / gt_attr_count int32 [B,M] as
+ *   K29 leaves them; f1_thresholds: F doubles in HOST memory, read during the call; empty_f1.
+ *       tp_bits, ig_bits : uint16 [F,A,B,N], K16's words per F1 threshold (bit 15 of tp_bits = keep, the same for every f)
+ *       matched_gt       : int32 [F,A,B,T,N]
+ *       order, class_rank: int32 [B,N] as K16 (they do not depend on f: the workgroups a = 0, f = 0 write them)
+ *       gt_count         : int32 [A,C] as K16 (it does not depend on f: only the f = 0 workgroups add to it)
+ *   Limits: those of K16, 1 <= F <= 16, 1 <= Wa <= 64, empty_f1 0 or 1, and the image's staging within the default 64 KiB of
+ *   dynamic LDS: 36 Np + 20 Mp + roundup8(Np + Mp) + (8 Wa + 4) (Np + Mp) bytes with Np, Mp = N, M rounded up to 4 (14.3 KiB at
+ *   N = M = 100, Wa = 5).  Anything else returns -1 (bdetr_last_error names the limit) without a launch.
+ *
+ * K31  bdetr_mask_match_attr: K17's bdetr_mask_match_coco with the same gate; operands as K17 plus K30's.  Limits: those of K17
+ *   and of the gate, and 24 Np + 8 Mp + roundup8(Np + Mp) + 8 W (Np + Mp) + (8 Wa + 4) (Np + Mp) bytes of LDS within 64 KiB.
+ *   (Image-resolution masks with the gate are not built: K22's source would take the same gate.)
+ * ---------------------------------------------------------------------- */
+int bdetr_attr_pack(const float* x, int64_t rows, int A, uint64_t* bits, int32_t* count, void* stream);
+int bdetr_det_match_attr(const float* score, const int32_t* label, const float* box_pred, const uint64_t* det_attr,
+                         const int32_t* det_count, const int32_t* gt_label, const float* gt_box, const uint64_t* gt_attr,
+                         const int32_t* gt_attr_count, const uint8_t* gt_crowd, const float* gt_area, const int32_t* num_objects,
+                         const int32_t* image_hw, const double* area_ranges, const double* thresholds, const double* f1_thresholds,
+                         double empty_f1, int B, int N, int M, int C, int Wa, int T, int F, int A, int max_dets, int32_t* order,
+                         int32_t* class_rank, uint16_t* tp_bits, uint16_t* ig_bits, int32_t* matched_gt, int32_t* gt_count,
+                         void* stream);
+int bdetr_mask_match_attr(const float* score, const int32_t* label, const uint64_t* det_bits, const int32_t* det_pop,
+                          const uint64_t* det_attr, const int32_t* det_count, const int32_t* gt_label, const uint64_t* gt_bits,
+                          const int32_t* gt_pop, const uint64_t* gt_attr, const int32_t* gt_attr_count, const uint8_t* gt_crowd,
+                          const float* gt_area, const int32_t* num_objects, const int32_t* image_hw, const double* area_ranges,
+                          const double* thresholds, const double* f1_thresholds, double empty_f1, int B, int N, int M, int P, int C,
+                          int Wa, int T, int F, int A, int max_dets, int32_t* order, int32_t* class_rank, uint16_t* tp_bits,
+                          uint16_t* ig_bits, int32_t* matched_gt, int32_t* gt_count, void* stream);
 
 #ifdef __cplusplus
 }
