@@ -221,7 +221,8 @@ __global__ __launch_bounds__(256) void flag_nonfinite_kernel(const float* __rest
 
 extern "C" int bdetr_tokens_prepare(const int* cat_ids, const int* att_ids, int64_t rows, int slots, int C, int A,
                                     int* cat_out, float* att_hot, void* stream) {
-    BDETR_CHECK_ARG(cat_ids && att_ids && cat_out && att_hot && rows > 0 && slots >= 0 && C > 1 && A > 1, "bdetr_tokens_prepare: bad arguments");
+    // (no slots: the attribute operand is empty and never read - an empty tensor's pointer is null)
+    BDETR_CHECK_ARG(cat_ids && (att_ids || slots == 0) && cat_out && att_hot && rows > 0 && slots >= 0 && C > 1 && A > 1, "bdetr_tokens_prepare: bad arguments");
     hipLaunchKernelGGL(tokens_prepare_kernel, dim3(ew_grid(rows, 256, 1)), dim3(256), 0, (hipStream_t)stream, cat_ids, att_ids, rows, slots, C, A, cat_out, att_hot);
     return bdetr_launch_status("tokens_prepare");
 }

@@ -103,7 +103,8 @@ int bdetr_image_prep(const float* in, int B, int h, int w, float* out, int H, in
  * (strings never reach the device): category ids [rows] are range-checked against C, the attribute id
  * slots [rows][slots] become the multi-hot matrix [rows][A] (tf.one_hot + reduce_max over the slot axis,
  * tokenizers.py:72-82; <PAD> slots set bit 0).  An id outside its vocabulary maps to 1 (<OOV>), as
- * StringLookup maps an unknown string.  rows = B*M. */
+ * StringLookup maps an unknown string.  rows = B*M.  slots = 0: att_ids is not read and may be null; att_hot
+ * is all zero. */
 int bdetr_tokens_prepare(const int* cat_ids, const int* att_ids, int64_t rows, int slots, int C, int A,
                          int* cat_out, float* att_hot, void* stream);
 

@@ -9,6 +9,10 @@ bar it was held to and the index of the worst element ((n, h, w, channel) for th
 tests/test_precision_gpu.py::_prof_tuples reads).  A failed comparison is recorded and the next case runs; any other error
 ends the child with a traceback.
 
+Every case runs inside a guard arena (tests/_guard.py): its operands, results and workspaces sit between 0xFF margins, and the
+report's "guard" is null or what the arena found - a changed margin, a changed read-only operand, an unguarded result or a NaN
+left in a result.  (One run per case: the two-fill comparison of integer results belongs to tests/test_memory_bounds_gpu.py.)
+
 The module is also imported by the parent (no GPU work at import time) for the case lists and what each case must launch."""
 import json
 import os
@@ -278,6 +282,7 @@ def attn_case(close, B, h, nq, nk):
 def main(name):
     import tempfile
     import torch
+    import _guard
     from boosted_detr_amd import _lib
     from boosted_detr_amd import kernels as k
     from test_p16_gpu import p16_conv_case
@@ -298,17 +303,24 @@ def main(name):
     with tempfile.TemporaryDirectory() as tmp:
         for kind, args, what in case_list(name):
             del RECORDS[:]
-            failed = None
+            failed = guard = None
+            arena = _guard.Arena("cuda")
             L.bdetr_prof_enable(1)
             try:
-                bodies[kind](*args)
+                with arena.armed():
+                    bodies[kind](*args)
             except AssertionError as e:
                 failed = str(e)[:600] or "assertion failed"
             finally:
                 tuples = sorted(_prof_tuples(os.path.join(tmp, "prof.csv")))
                 L.bdetr_prof_enable(0)
+            try:
+                arena.verify()
+            except _guard.GuardError as e:
+                guard = str(e)[:1500]
+            del arena
             names = P16_PRODUCTS if kind == "p16" and len(RECORDS) == len(P16_PRODUCTS) else ["p%d" % i for i in range(len(RECORDS))]
-            results.append({"case": [kind] + list(args), "what": what, "failed": failed, "tuples": [list(t) for t in tuples],
+            results.append({"case": [kind] + list(args), "what": what, "failed": failed, "guard": guard, "tuples": [list(t) for t in tuples],
                             "errors": {n: r for n, r in zip(names, RECORDS)}})
     print(MARK + json.dumps({"list": name, "cases": results}), flush=True)
 

@@ -121,8 +121,8 @@ def p16_conv_case(N, H, W, C, K, R, stride, pad, accumulate=True):
     try:
         d1 = k.p16_conv2d_bwd_weight(xf, dyb, g, x_f16=True)
         d2 = k.p16_conv2d_bwd_weight(xf, dyb, g, x_f16=True)
-        base = dev(rnd(K, R, R, C, seed=12))
-        d3 = k.p16_conv2d_bwd_weight(xb, dyb, g, dw=base.clone(), prezeroed=True)       # "+=" onto a running sum, like the atomics
+        base = rnd(K, R, R, C, seed=12)
+        d3 = k.p16_conv2d_bwd_weight(xb, dyb, g, dw=dev(base), prezeroed=True)          # "+=" onto a running sum, like the atomics
     finally:
         k.set_deterministic(prev)
     close(d1, wtt.grad.permute(0, 2, 3, 1), rtol=6e-5)
@@ -130,7 +130,7 @@ def p16_conv_case(N, H, W, C, K, R, stride, pad, accumulate=True):
     import ctypes
     from boosted_detr_amd import _lib
     split = _lib.lib().bdetr_p16_conv2d_bwd_weight_splitk(ctypes.byref(g.desc())) > 1       # an unsplit launch stores, a split one adds (include/bdetr.h)
-    close(d3, (base.double().cpu() if split else 0) + wtt.grad.permute(0, 2, 3, 1), rtol=6e-5)
+    close(d3, (base.double() if split else 0) + wtt.grad.permute(0, 2, 3, 1), rtol=6e-5)
 
 
 @pytest.mark.parametrize("N,H,W,C,K,R,stride,pad", P16_CONVS + P16_BIG_CONVS)

@@ -7,6 +7,7 @@ child process, tests/_variant_child.py) on the geometries where tiled kernels go
 
   * the project's own bars against fp64 references (2e-5 x max|ref| forward, 6e-5 gradients, 1e-4 statistic sums, 1e-5
     fused-vs-two-pass) - asserted in the child by the imported case bodies and once more here from the reported figures;
+  * that the guard arena of every case (tests/_guard.py: 0xFF margins around every operand, result and workspace) found nothing;
   * that the forced variant is among the launched (kind, bm, bn) tuples - a forced tile the chooser silently declines fails -
     and, where the admission rule must refuse it, that it is not.
 
@@ -53,6 +54,8 @@ def run_cases(variant, env, list_name, timeout):
     assert [tuple(c["case"]) for c in report["cases"]] == [(kind,) + tuple(args) for kind, args, _ in wanted], "the child ran another case list"
     bad = ["%s (%s): %s" % (c["case"], c["what"], c["failed"]) for c in report["cases"] if c["failed"]]
     assert not bad, "%s:\n%s" % (variant, "\n".join(bad))
+    unguarded = ["%s (%s): %s" % (c["case"], c["what"], c["guard"]) for c in report["cases"] if c["guard"] is not None]
+    assert not unguarded, "%s:\n%s" % (variant, "\n".join(unguarded))
     for c in report["cases"]:
         assert c["errors"], (variant, c["case"], "compared nothing")
         for name, e in c["errors"].items():
@@ -66,7 +69,10 @@ def kinds(tuples, code):
 
 # Per-child time limits: wall times measured once on an MI355X (process start, HIP initialisation and the fp64 references included) -
 # hconv 3.7 s, stile 3.3 s, pp 3.6 s, wgrad 3.0 s, hwgrad 4.4 s, tile 3.2 s, attention 3.0 s, the batch-norm pytest child 6.8 s -
-# times three, rounded up to the next 10 s (a cold process start is not proportional to the work); run_child caps them at 600 s
+# times three, rounded up to the next 10 s (a cold process start is not proportional to the work); run_child caps them at 600 s.
+# Re-measured with every case inside the guard arena (margin fills, operand snapshots, the margin scan): hconv 3.4 s, stile 3.7 s,
+# pp 3.3 s, wgrad 3.1 s, hwgrad 4.2 s, tile 3.2 s, attention 3.1 s, the batch-norm pytest child (no arena) 6.9 s - the same limits by
+# the same rule
 @pytest.mark.parametrize("tile", sorted(vc.HCONV_TILES))
 def test_hconv_forced_tile_geometry_and_fused_sums(cuda, tile):
     """BDETR_HCONV_TILE: W at the halo capacity and one past it, 1-pixel-wide / -high / 1x1 images, many images inside one tile,
