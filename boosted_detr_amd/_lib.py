@@ -75,6 +75,7 @@ SIGNATURES = {
     "bdetr_abi_version": (I, []),
     "bdetr_last_error": (C.c_char_p, []),
     "bdetr_device_cus": (I, []),
+    "bdetr_stream_policy": (I, []),
     "bdetr_low_priority_stream_create": (I, [P]),
     "bdetr_side_stream_candidates": (I, [P, I, I, I, P, P, P]),
     "bdetr_stream_destroy": (I, [P]),

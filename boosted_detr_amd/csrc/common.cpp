@@ -1,5 +1,7 @@
 // Error reporting shared by every translation unit of libbdetr.
 #include "common.h"
+#include "stream.h"
+#include <stdlib.h>
 #include <string.h>
 
 static thread_local char g_err[512] = "";
@@ -13,6 +15,26 @@ void bdetr_set_error(const char* fmt, ...) {
 
 extern "C" const char* bdetr_last_error(void) { return g_err; }
 extern "C" int bdetr_abi_version(void) { return BDETR_ABI_VERSION; }
+
+// BDETR_STREAM_POLICY: a sum of the operand-class bits of stream.h, read once.  Unset = STREAM_DEFAULT, the classes that won in the
+// training step (profiles/stream_policy_2026-10-20.txt); 0 = every access default.  A value that is not a whole decimal number in
+// 0..STREAM_ALL is not masked into some policy: it is reported once on stderr (and as the library's last error) and the default stays.
+int bdetr_stream_policy_bits() {
+    static const int bits = [] {
+        const char* e = getenv("BDETR_STREAM_POLICY");
+        if (e == nullptr || *e == '\0') return (int)STREAM_DEFAULT;
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (end == e || *end != '\0' || v < 0 || v > STREAM_ALL) {
+            bdetr_set_error("BDETR_STREAM_POLICY=%s is not a sum of operand-class bits in 0..%d: the default (%d) is in force", e, (int)STREAM_ALL, (int)STREAM_DEFAULT);
+            fprintf(stderr, "libbdetr: %s\n", bdetr_last_error());
+            return (int)STREAM_DEFAULT;
+        }
+        return (int)v;
+    }();
+    return bits;
+}
+extern "C" int bdetr_stream_policy(void) { return bdetr_stream_policy_bits(); }
 
 // A non-blocking HIP stream of the LOWEST priority the device offers: the host runs the weight-gradient
 // GEMMs on it so that the workgroup dispatcher serves the critical path (the caller's stream) first and

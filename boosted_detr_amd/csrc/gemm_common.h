@@ -5,6 +5,7 @@
 // f32x16 accumulators and share the problem description, the epilogue and the live-profiling hooks.
 #pragma once
 #include "common.h"
+#include "stream.h"
 #include <type_traits>
 
 namespace bdgemm {
@@ -143,10 +144,12 @@ __device__ __forceinline__ void gemm_bias_act_stats(f32x16 (&acc)[BM / WM / 32][
 }
 
 // bn_apply_p16's ReLU bit mask (norm.hip relu_mask_bits4): component e of float4 index i lives in 64-bit word (i >> 6) * 4 + e, bit i & 63
+template <bool STREAM = false>       // STREAM: non-temporal loads (stream.h)
 __device__ __forceinline__ unsigned mask_bits4(const unsigned long long* mask, int64_t i) {
     const unsigned long long* w = mask + (i >> 6) * 4;
     const int b = (int)(i & 63);
-    return (unsigned)((w[0] >> b) & 1ull) | ((unsigned)((w[1] >> b) & 1ull) << 1) | ((unsigned)((w[2] >> b) & 1ull) << 2) | ((unsigned)((w[3] >> b) & 1ull) << 3);
+    const unsigned long long w0 = ld_stream<STREAM>(w), w1 = ld_stream<STREAM>(w + 1), w2 = ld_stream<STREAM>(w + 2), w3 = ld_stream<STREAM>(w + 3);
+    return (unsigned)((w0 >> b) & 1ull) | ((unsigned)((w1 >> b) & 1ull) << 1) | ((unsigned)((w2 >> b) & 1ull) << 2) | ((unsigned)((w3 >> b) & 1ull) << 3);
 }
 
 // Epilogue of a BM x BN workgroup tile held as TM x TN 32x32 accumulators per wave (C/D layout of the
@@ -154,7 +157,10 @@ __device__ __forceinline__ unsigned mask_bits4(const unsigned long long* mask, i
 // statistics (above), then either LDS-transposed 16-byte row stores (store / accumulate) or per-element stores /
 // atomics (split-K).  `lds` must hold LDS_FLOATS >= BM * BN floats and be free to overwrite once every wave has
 // passed the barrier this function starts with.
-template <int BM, int BN, int WM, int WN, int NT, int LDS_FLOATS, bool MASKED_VARIANTS = false, bool BNB2_ONLY = false, bool COMPACT_ONLY = false>
+// STREAM (the masked accumulates of the fused 1x1 backward-data): the old gradient and its ReLU mask are loaded with the non-temporal hint -
+// this epilogue is their last reader (stream.h; the fused sums' y and mask are read again by the BatchNorm backward pass that follows
+// and keep the default policy).
+template <int BM, int BN, int WM, int WN, int NT, int LDS_FLOATS, bool MASKED_VARIANTS = false, bool BNB2_ONLY = false, bool COMPACT_ONLY = false, bool STREAM = false>
 __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[BM / WM / 32][BN / WN / 32], const GemmParams& g, float* lds,
                                               int tile_i, int i0, int j0, float* cbase, const float* bias_pre = nullptr) {
     constexpr int WTM = BM / WM, WTN = BN / WN, TM = WTM / 32, TN = WTN / 32;
@@ -242,9 +248,9 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[BM / WM / 32][BN / W
                         old[k] = f32x4{0, 0, 0, 0};
                         const unsigned iu = (unsigned)i, w = iu % (unsigned)g.acc_W, t = iu / (unsigned)g.acc_W, h = t % (unsigned)g.acc_H, n = t / (unsigned)g.acc_H;
                         if (ok[k] && ((h | w) & 1u) == 0u)
-                            old[k] = *reinterpret_cast<const f32x4*>(g.acc_src + ((int64_t)(n * (unsigned)(g.acc_H >> 1) + (h >> 1)) * (g.acc_W >> 1) + (w >> 1)) * g.ldc + jc);
-                    } else if constexpr (ACCUM) { old[k] = f32x4{0, 0, 0, 0}; if (ok[k]) old[k] = *reinterpret_cast<const f32x4*>(dst[k]); }
-                    if constexpr (ACCUM && MASKED) { abits[k] = 0u; if (ok[k]) abits[k] = mask_bits4(g.acc_mask, (row * g.ldc + jc) >> 2); }
+                            old[k] = ld_stream<STREAM && MASKED>(reinterpret_cast<const f32x4*>(g.acc_src + ((int64_t)(n * (unsigned)(g.acc_H >> 1) + (h >> 1)) * (g.acc_W >> 1) + (w >> 1)) * g.ldc + jc));
+                    } else if constexpr (ACCUM) { old[k] = f32x4{0, 0, 0, 0}; if (ok[k]) old[k] = ld_stream<STREAM && MASKED>(reinterpret_cast<const f32x4*>(dst[k])); }
+                    if constexpr (ACCUM && MASKED) { abits[k] = 0u; if (ok[k]) abits[k] = mask_bits4<STREAM>(g.acc_mask, (row * g.ldc + jc) >> 2); }
                     if constexpr (BNB) { yv[k] = f32x4{0, 0, 0, 0}; if (ok[k]) yv[k] = *reinterpret_cast<const f32x4*>(g.bnb_y + (int64_t)i * g.ldc + jc); }
                     if constexpr (BNB && MASKED) { bbits[k] = 0u; if (ok[k]) bbits[k] = mask_bits4(g.bnb_mask, ((int64_t)i * g.ldc + jc) >> 2); }
                     if constexpr (BNB2) { y2v[k] = f32x4{0, 0, 0, 0}; if (ok[k]) y2v[k] = *reinterpret_cast<const f32x4*>(g.bnb2_y + (int64_t)i * g.ldc + jc); }

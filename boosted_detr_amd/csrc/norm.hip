@@ -7,6 +7,7 @@
 // (transformers.py:135-137,178-180), softmax (transformers.py:89, prediction_heads.py:111).
 #include "common.h"
 #include "p16.h"
+#include "stream.h"
 
 namespace {
 
@@ -243,10 +244,11 @@ void sum_partials2(const float* pa, const float* pb, int nparts, int C, float* o
         hipLaunchKernelGGL(sum_partials2_kernel, dim3((C + 7) / 8), dim3(256), 0, st, pa, pb, nparts, C, oa, ob);
 }
 
+template <bool NT>      // NT (here and below): the stream-once loads carry the non-temporal hint (stream.h)
 struct StatFn {
     const float* x; int C;
     __device__ __forceinline__ void operator()(int64_t r, int c, f32x4& a, f32x4& b) const {
-        f32x4 v = *reinterpret_cast<const f32x4*>(x + r * C + c);
+        f32x4 v = ld_stream<NT>(reinterpret_cast<const f32x4*>(x + r * C + c));
         a = v; b = v * v;
     }
 };
@@ -265,12 +267,15 @@ __device__ __forceinline__ float bn_bwd_dx(float g, float xv, float m, float rs,
 
 // ReLU bit mask written by bn_apply_p16 (1 bit per element instead of re-reading a 4-byte-per-element tensor in both
 // backward passes): element e of float4 index i lives in word (i >> 6) * 4 + e, bit i & 63
+template <bool NT = false>
 __device__ __forceinline__ unsigned relu_mask_bits4(const void* mask, int64_t i) {
     const unsigned long long* w = reinterpret_cast<const unsigned long long*>(mask) + (i >> 6) * 4;
     const int b = (int)(i & 63);
-    return (unsigned)((w[0] >> b) & 1ull) | ((unsigned)((w[1] >> b) & 1ull) << 1) | ((unsigned)((w[2] >> b) & 1ull) << 2) | ((unsigned)((w[3] >> b) & 1ull) << 3);
+    const unsigned long long w0 = ld_stream<NT>(w), w1 = ld_stream<NT>(w + 1), w2 = ld_stream<NT>(w + 2), w3 = ld_stream<NT>(w + 3);
+    return (unsigned)((w0 >> b) & 1ull) | ((unsigned)((w1 >> b) & 1ull) << 1) | ((unsigned)((w2 >> b) & 1ull) << 2) | ((unsigned)((w3 >> b) & 1ull) << 3);
 }
 
+template <bool NT>
 struct BnBwdFn {   // a = g (masked dout), b = g * xhat
     const float* dout; const float* out; const float* x; const float* mean; const float* rstd; const float* gamma; const float* beta;
     int C; int relu;
@@ -288,17 +293,17 @@ struct BnBwdFn {   // a = g (masked dout), b = g * xhat
             const unsigned q = (unsigned)r, j2 = q % w2, t = q / w2, i2 = t % h2, n = t / h2;
             r = ((int64_t)n * even_h + 2 * i2) * even_w + 2 * j2;
         }
-        f32x4 g = *reinterpret_cast<const f32x4*>(dout + (dout_compact ? rg : r) * C + c);
-        f32x4 xv = *reinterpret_cast<const f32x4*>(x + r * C + c);
+        f32x4 g = ld_stream<NT>(reinterpret_cast<const f32x4*>(dout + (dout_compact ? rg : r) * C + c));
+        f32x4 xv = ld_stream<NT>(reinterpret_cast<const f32x4*>(x + r * C + c));
         f32x4 m = *reinterpret_cast<const f32x4*>(mean + c);
         f32x4 rs = *reinterpret_cast<const f32x4*>(rstd + c);
         if (relu) {
             if (out != nullptr && out_p16) {
-                const unsigned pm = out_p16 == 2 ? relu_mask_bits4(out, (r * C + c) >> 2) : p16_positive4_bf16(out, (r * C + c) >> 2);
+                const unsigned pm = out_p16 == 2 ? relu_mask_bits4<NT>(out, (r * C + c) >> 2) : p16_positive4_bf16<NT>(out, (r * C + c) >> 2);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) if (!((pm >> e) & 1u)) g[e] = 0.f;
             } else if (out != nullptr) {
-                f32x4 o = *reinterpret_cast<const f32x4*>(out + r * C + c);
+                f32x4 o = ld_stream<NT>(reinterpret_cast<const f32x4*>(out + r * C + c));
 #pragma unroll
                 for (int e = 0; e < 4; ++e) if (!(o[e] > 0.f)) g[e] = 0.f;
             } else {     // no residual: the mask is a function of x alone - recompute it, do not re-read `out`
@@ -311,19 +316,20 @@ struct BnBwdFn {   // a = g (masked dout), b = g * xhat
     }
 };
 
+template <bool NT>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        const float* __restrict__ residual, int relu, float* __restrict__ out,
                                                        int64_t n4, int c4n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % c4n) * 4;
-        f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
+        f32x4 v = ld_stream4<NT>(x, i);
         f32x4 m = *reinterpret_cast<const f32x4*>(mean + c), rs = *reinterpret_cast<const f32x4*>(rstd + c);
         f32x4 g = *reinterpret_cast<const f32x4*>(gamma + c), b = *reinterpret_cast<const f32x4*>(beta + c);
         f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = bn_affine(v[e], m[e], rs[e], g[e], b[e]);
-        if (residual != nullptr) o += reinterpret_cast<const f32x4*>(residual)[i];
+        if (residual != nullptr) o += ld_stream4<NT>(residual, i);
         if (relu) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.f);
@@ -332,6 +338,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     }
 }
 
+template <bool NT>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dout, const float* __restrict__ out, const float* __restrict__ x,
                                                            const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta,
@@ -339,15 +346,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            float* __restrict__ dx, float* __restrict__ dres, int64_t n4, int c4n, float inv_rows) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % c4n) * 4;
-        f32x4 g = reinterpret_cast<const f32x4*>(dout)[i];
+        f32x4 g = ld_stream4<NT>(dout, i);
         f32x4 rs = *reinterpret_cast<const f32x4*>(rstd + c), gm = *reinterpret_cast<const f32x4*>(gamma + c);
         f32x4 m = *reinterpret_cast<const f32x4*>(mean + c);
         f32x4 xv = {0.f, 0.f, 0.f, 0.f};
         const bool recompute = relu && out == nullptr;
-        if (!frozen || recompute) xv = reinterpret_cast<const f32x4*>(x)[i];
+        if (!frozen || recompute) xv = ld_stream4<NT>(x, i);
         if (relu) {
             if (!recompute) {
-                f32x4 o = reinterpret_cast<const f32x4*>(out)[i];
+                f32x4 o = ld_stream4<NT>(out, i);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) if (!(o[e] > 0.f)) g[e] = 0.f;
             } else {
@@ -380,6 +387,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
 // no gradient either way (the ReLU mask).
 struct StemGeom { int N, H, W, C, PH, PW; };
 
+template <bool NT>
 __global__ __launch_bounds__(256) void stem_pool_fwd_kernel(const float* __restrict__ y, const float* __restrict__ mean, const float* __restrict__ rstd,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta, StemGeom s,
                                                             float* __restrict__ out32, void* __restrict__ out_f16, unsigned* __restrict__ tap,
@@ -399,7 +407,7 @@ __global__ __launch_bounds__(256) void stem_pool_fwd_kernel(const float* __restr
             const int ih = ph * 2 - 1 + k / 3, iw = pw * 2 - 1 + k % 3;
             in[k] = (unsigned)ih < (unsigned)s.H && (unsigned)iw < (unsigned)s.W;
             v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (in[k]) v[k] = reinterpret_cast<const f32x4*>(y)[(((int64_t)n * s.H + ih) * s.W + iw) * c4n + c4];
+            if (in[k]) v[k] = ld_stream4<NT>(y, (((int64_t)n * s.H + ih) * s.W + iw) * c4n + c4);
         }
         // (the padding ring holds zeros and every window has a real tap, whose value is >= 0 after the ReLU: skipping the ring's
         // taps gives the same maximum as comparing against their zeros)
@@ -428,6 +436,7 @@ __global__ __launch_bounds__(256) void stem_pool_fwd_kernel(const float* __restr
 
 // gradient of the NORMALISED, rectified tensor at input pixel `px` (flat n*H*W + ih*W + iw), channels c..c+3: the pooled gradient of
 // every window whose recorded tap is this pixel, masked by the ReLU (recomputed from y with the forward's bn_affine).  Also returns xhat.
+template <bool NT>
 __device__ __forceinline__ f32x4 stem_pixel_grad(const float* __restrict__ dpool, const unsigned* __restrict__ tap, const StemGeom& s, unsigned px, int c,
                                                  const f32x4 yv, const f32x4 m, const f32x4 rs, const f32x4 gm, const f32x4 bt, f32x4& xhat) {
     const int c4n = s.C / 4, c4 = c / 4;
@@ -448,8 +457,8 @@ __device__ __forceinline__ f32x4 stem_pixel_grad(const float* __restrict__ dpool
         const int ph = ph0 + (a & (int)two_h), pw = pw0 + (b & (int)two_w);
         const int64_t o = (((int64_t)n * s.PH + ph) * s.PW + pw) * c4n + c4;
         mine[k] = real ? (unsigned)((ih - (ph * 2 - 1)) * 3 + (iw - (pw * 2 - 1))) : 0xFFu;
-        word[k] = tap[o];
-        dv[k] = reinterpret_cast<const f32x4*>(dpool)[o];
+        word[k] = ld_stream<NT>(tap + o);
+        dv[k] = ld_stream4<NT>(dpool, o);
     }
     f32x4 g = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -462,18 +471,20 @@ __device__ __forceinline__ f32x4 stem_pixel_grad(const float* __restrict__ dpool
     return g;
 }
 
+template <bool NT>
 struct StemBwdFn {   // a = g, b = g * xhat  (colreduce2_kernel functor; `r` is the flat input pixel)
     const float* dpool; const unsigned* tap; const float* y; const float* mean; const float* rstd; const float* gamma; const float* beta; StemGeom s;
     __device__ __forceinline__ void operator()(int64_t r, int c, f32x4& a, f32x4& b) const {
-        const f32x4 yv = *reinterpret_cast<const f32x4*>(y + r * s.C + c);
+        const f32x4 yv = ld_stream<NT>(reinterpret_cast<const f32x4*>(y + r * s.C + c));
         const f32x4 m = *reinterpret_cast<const f32x4*>(mean + c), rs = *reinterpret_cast<const f32x4*>(rstd + c);
         const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c), bt = *reinterpret_cast<const f32x4*>(beta + c);
         f32x4 xh;
-        a = stem_pixel_grad(dpool, tap, s, (unsigned)r, c, yv, m, rs, gm, bt, xh);
+        a = stem_pixel_grad<NT>(dpool, tap, s, (unsigned)r, c, yv, m, rs, gm, bt, xh);
         b = a * xh;
     }
 };
 
+template <bool NT>
 __global__ __launch_bounds__(256) void stem_bwd_apply_kernel(const float* __restrict__ dpool, const unsigned* __restrict__ tap, const float* __restrict__ y,
                                                              const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, const float* __restrict__ dgamma, const float* __restrict__ dbeta,
@@ -483,9 +494,9 @@ __global__ __launch_bounds__(256) void stem_bwd_apply_kernel(const float* __rest
     const int c4n = s.C / 4;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     auto one = [&](int64_t i, int c, const f32x4 m, const f32x4 rs, const f32x4 gm, const f32x4 bt, const f32x4 dg, const f32x4 db) {
-        const f32x4 yv = reinterpret_cast<const f32x4*>(y)[i];
+        const f32x4 yv = ld_stream4<NT>(y, i);
         f32x4 xh;
-        const f32x4 g = stem_pixel_grad(dpool, tap, s, (unsigned)(i / c4n), c, yv, m, rs, gm, bt, xh);
+        const f32x4 g = stem_pixel_grad<NT>(dpool, tap, s, (unsigned)(i / c4n), c, yv, m, rs, gm, bt, xh);
         f32x4 r;
 #pragma unroll
         for (int e = 0; e < 4; ++e) r[e] = bn_bwd_dx(g[e], yv[e], m[e], rs[e], gm[e], dg[e], db[e], inv_rows);      // bn_bwd_apply_kernel's expression
@@ -512,6 +523,7 @@ __global__ __launch_bounds__(256) void stem_bwd_apply_kernel(const float* __rest
 // writing the f16 pair (forward operand of the consumer conv), the bf16 pair (its weight-gradient operand) and / or
 // the fp32 tensor.  The fp32 arithmetic is identical to the kernels above (bn_affine), so a ReLU mask recomputed in
 // the backward pass agrees with what the forward wrote.
+template <bool NT>
 __global__ __launch_bounds__(256) void bn_apply_p16_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            const void* __restrict__ residual, int residual_p16, bdetr_bn_affine rbn, int relu, float* __restrict__ out32,
@@ -538,8 +550,8 @@ __global__ __launch_bounds__(256) void bn_apply_p16_kernel(const float* __restri
     auto load_res = [&](int64_t i) {
         f32x4 r = {0.f, 0.f, 0.f, 0.f};
         if (residual != nullptr) {
-            if (residual_p16 == 1) { float r4[4]; p16_load4_f16(residual, i, r4); r = f32x4{r4[0], r4[1], r4[2], r4[3]}; }
-            else r = reinterpret_cast<const f32x4*>(residual)[i];
+            if (residual_p16 == 1) { float r4[4]; p16_load4_f16<NT>(residual, i, r4); r = f32x4{r4[0], r4[1], r4[2], r4[3]}; }
+            else r = ld_stream4<NT>(reinterpret_cast<const float*>(residual), i);
         }
         return r;
     };
@@ -593,12 +605,12 @@ __global__ __launch_bounds__(256) void bn_apply_p16_kernel(const float* __restri
         const Affine p2 = rb ? affine_of(rbn.mean, rbn.rstd, rbn.gamma, rbn.beta, c) : p;
         for (; (i | 63) + stride < n4; i += 2 * stride) {
             const int64_t i0 = at(i), i1 = at(i + stride);
-            const f32x4 v0 = reinterpret_cast<const f32x4*>(x)[i0], v1 = reinterpret_cast<const f32x4*>(x)[i1];
+            const f32x4 v0 = ld_stream4<NT>(x, i0), v1 = ld_stream4<NT>(x, i1);
             const f32x4 r0 = load_res(i0), r1 = load_res(i1);
             body(i0, v0, r0, p, p2);
             body(i1, v1, r1, p, p2);
         }
-        for (; i < n4; i += stride) { const int64_t i0 = at(i); const f32x4 v0 = reinterpret_cast<const f32x4*>(x)[i0]; const f32x4 r0 = load_res(i0); body(i0, v0, r0, p, p2); }
+        for (; i < n4; i += stride) { const int64_t i0 = at(i); const f32x4 v0 = ld_stream4<NT>(x, i0); const f32x4 r0 = load_res(i0); body(i0, v0, r0, p, p2); }
         return;
     }
     for (; i < n4; i += stride) {
@@ -606,12 +618,13 @@ __global__ __launch_bounds__(256) void bn_apply_p16_kernel(const float* __restri
         const Affine p = affine_of(mean, rstd, gamma, beta, c);
         const Affine p2 = rb ? affine_of(rbn.mean, rbn.rstd, rbn.gamma, rbn.beta, c) : p;
         const int64_t i0 = at(i);
-        const f32x4 v0 = reinterpret_cast<const f32x4*>(x)[i0];
+        const f32x4 v0 = ld_stream4<NT>(x, i0);
         const f32x4 r0 = load_res(i0);
         body(i0, v0, r0, p, p2);
     }
 }
 
+template <bool NT>
 __global__ __launch_bounds__(256) void bn_bwd_apply_p16_kernel(const float* __restrict__ dout, const void* __restrict__ out, int out_p16, const float* __restrict__ x,
                                                                const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta,
@@ -641,18 +654,18 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_p16_kernel(const float* __re
             const unsigned iu = (unsigned)i, row = iu / (unsigned)c4n, cc = iu - row * (unsigned)c4n;      // (host: n4 < 2^32 in this mode)
             const unsigned w = row % (unsigned)cW, t = row / (unsigned)cW, h = t % (unsigned)cH, n = t / (unsigned)cH;
             q.g = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (((h | w) & 1u) == 0u) q.g = reinterpret_cast<const f32x4*>(dout)[((int64_t)(n * (unsigned)(cH >> 1) + (h >> 1)) * (cW >> 1) + (w >> 1)) * c4n + cc];
+            if (((h | w) & 1u) == 0u) q.g = ld_stream4<NT>(dout, ((int64_t)(n * (unsigned)(cH >> 1) + (h >> 1)) * (cW >> 1) + (w >> 1)) * c4n + cc);
             // an odd pixel's g is zero whatever its mask says, and the forward may never have written that mask (bn_apply_p16_kernel eH > 0):
             // it is not read - q.pm / q.o stay zero, which clears the zero
             else masked = false;
         } else {
-            q.g = reinterpret_cast<const f32x4*>(dout)[i];
+            q.g = ld_stream4<NT>(dout, i);
         }
-        q.xv = need_x ? reinterpret_cast<const f32x4*>(x)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+        q.xv = need_x ? ld_stream4<NT>(x, i) : f32x4{0.f, 0.f, 0.f, 0.f};
         q.o = f32x4{0.f, 0.f, 0.f, 0.f}; q.pm = 0u;
         if (masked) {
-            if (out_p16) q.pm = out_p16 == 2 ? relu_mask_bits4(out, i) : p16_positive4_bf16(out, i);
-            else q.o = reinterpret_cast<const f32x4*>(out)[i];
+            if (out_p16) q.pm = out_p16 == 2 ? relu_mask_bits4<NT>(out, i) : p16_positive4_bf16<NT>(out, i);
+            else q.o = ld_stream4<NT>(reinterpret_cast<const float*>(out), i);
         }
         return q;
     };
@@ -927,8 +940,8 @@ extern "C" int bdetr_colstats(const float* x, int64_t rows, int C, float* part_s
     ColGeom g = col_geom(C);
     int64_t rpc = chunk_rows_for(rows, 512, 64);     // must match bdetr_bn_bwd_chunks(rows): the caller sizes part_* with it
     int nch = (int)cdiv64(rows, rpc);
-    StatFn f{x, C};
-    hipLaunchKernelGGL((colreduce2_kernel<StatFn>), dim3(g.gx, nch), dim3(256), 0, (hipStream_t)stream, f, rows, C, g.tx, rpc, part_sum, part_sq);
+    STREAM_DISPATCH(stream_on(STREAM_REDUCE), NT, StatFn<NT> f{x, C};
+                    hipLaunchKernelGGL((colreduce2_kernel<StatFn<NT>>), dim3(g.gx, nch), dim3(256), 0, (hipStream_t)stream, f, rows, C, g.tx, rpc, part_sum, part_sq));
     return bdetr_launch_status("colstats");
 }
 
@@ -944,7 +957,8 @@ extern "C" int bdetr_bn_apply(const float* x, const float* mean, const float* rs
                               int64_t rows, int C, void* stream) {
     BDETR_CHECK_ARG(x && mean && rstd && gamma && beta && out && rows > 0 && C > 0 && C % 4 == 0, "bdetr_bn_apply: bad arguments (C %% 4 == 0 required)");
     int64_t n4 = rows * C / 4;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(ew_grid(n4, 256, 2)), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma, beta, residual, relu, out, n4, C / 4);
+    STREAM_DISPATCH(stream_on(STREAM_APPLY_OTHER), NT,
+                    hipLaunchKernelGGL(bn_apply_kernel<NT>, dim3(ew_grid(n4, 256, 2)), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma, beta, residual, relu, out, n4, C / 4));
     return bdetr_launch_status("bn_apply");
 }
 
@@ -960,12 +974,13 @@ extern "C" int bdetr_bn_bwd(const float* dout, const float* out, const float* x,
     int64_t rpc = chunk_rows_for(rows, chunks_for_width(g.gx), 64);   // <= bdetr_bn_bwd_chunks(rows), which sizes ws
     int nch = (int)cdiv64(rows, rpc);
     float* pa = ws; float* pb = ws + (int64_t)nch * C;
-    BnBwdFn f{dout, out, x, mean, rstd, gamma, beta, C, relu};
-    hipLaunchKernelGGL((colreduce2_kernel<BnBwdFn>), dim3(g.gx, nch), dim3(256), 0, st, f, rows, C, g.tx, rpc, pa, pb);
+    STREAM_DISPATCH(stream_on(STREAM_REDUCE), NT, BnBwdFn<NT> f{dout, out, x, mean, rstd, gamma, beta, C, relu};
+                    hipLaunchKernelGGL((colreduce2_kernel<BnBwdFn<NT>>), dim3(g.gx, nch), dim3(256), 0, st, f, rows, C, g.tx, rpc, pa, pb));
     sum_partials2(pa, pb, nch, C, dbeta, dgamma, st);
     int64_t n4 = rows * C / 4;
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(n4, 256, 2)), dim3(256), 0, st, dout, out, x, mean, rstd, gamma, beta, dgamma, dbeta,
-                       relu, frozen, dx, dresidual, n4, C / 4, 1.0f / (float)rows);
+    STREAM_DISPATCH(stream_on(STREAM_APPLY_OTHER), NT,
+                    hipLaunchKernelGGL(bn_bwd_apply_kernel<NT>, dim3(ew_grid(n4, 256, 2)), dim3(256), 0, st, dout, out, x, mean, rstd, gamma, beta, dgamma, dbeta,
+                                       relu, frozen, dx, dresidual, n4, C / 4, 1.0f / (float)rows));
     return bdetr_launch_status("bn_bwd");
 }
 
@@ -976,8 +991,9 @@ extern "C" int bdetr_stem_pool_fwd(const float* y, const float* mean, const floa
     BDETR_CHECK_ARG((int64_t)N * H * W < (int64_t)1 << 31, "bdetr_stem_pool_fwd: more than 2^31 pixels");
     const StemGeom s{N, H, W, C, (H + 2 - 3) / 2 + 1, (W + 2 - 3) / 2 + 1};
     const int64_t n4 = (int64_t)N * s.PH * s.PW * (C / 4);
-    hipLaunchKernelGGL(stem_pool_fwd_kernel, dim3(ew_grid(n4, 256, 1)), dim3(256), 0, (hipStream_t)stream, y, mean, rstd, gamma, beta, s, out32, out_f16,
-                       reinterpret_cast<unsigned*>(tap), overflow_flag);
+    STREAM_DISPATCH(stream_on(STREAM_APPLY_OTHER), NT,
+                    hipLaunchKernelGGL(stem_pool_fwd_kernel<NT>, dim3(ew_grid(n4, 256, 1)), dim3(256), 0, (hipStream_t)stream, y, mean, rstd, gamma, beta, s, out32, out_f16,
+                                       reinterpret_cast<unsigned*>(tap), overflow_flag));
     return bdetr_launch_status("stem_pool_fwd");
 }
 
@@ -997,12 +1013,13 @@ extern "C" int bdetr_stem_pool_bwd(const float* dpool, const uint8_t* tap, const
     int64_t rpc = chunk_rows_for(rows, STEM_BWD_CHUNKS, 64);
     int nch = (int)cdiv64(rows, rpc);
     float* pa = ws; float* pb = ws + (int64_t)nch * C;
-    StemBwdFn f{dpool, reinterpret_cast<const unsigned*>(tap), y, mean, rstd, gamma, beta, s};
-    hipLaunchKernelGGL((colreduce2_kernel<StemBwdFn>), dim3(g.gx, nch), dim3(256), 0, st, f, rows, C, g.tx, rpc, pa, pb);
+    STREAM_DISPATCH(stream_on(STREAM_REDUCE), NT, StemBwdFn<NT> f{dpool, reinterpret_cast<const unsigned*>(tap), y, mean, rstd, gamma, beta, s};
+                    hipLaunchKernelGGL((colreduce2_kernel<StemBwdFn<NT>>), dim3(g.gx, nch), dim3(256), 0, st, f, rows, C, g.tx, rpc, pa, pb));
     sum_partials2(pa, pb, nch, C, dbeta, dgamma, st);
     const int64_t n4 = rows * C / 4;
-    hipLaunchKernelGGL(stem_bwd_apply_kernel, dim3(ew_grid(n4, 256, 2)), dim3(256), 0, st, dpool, reinterpret_cast<const unsigned*>(tap), y, mean, rstd, gamma, beta,
-                       dgamma, dbeta, s, dy, dy_p16, n4, 1.0f / (float)rows);
+    STREAM_DISPATCH(stream_on(STREAM_APPLY_OTHER), NT,
+                    hipLaunchKernelGGL(stem_bwd_apply_kernel<NT>, dim3(ew_grid(n4, 256, 2)), dim3(256), 0, st, dpool, reinterpret_cast<const unsigned*>(tap), y, mean, rstd, gamma, beta,
+                                       dgamma, dbeta, s, dy, dy_p16, n4, 1.0f / (float)rows));
     return bdetr_launch_status("stem_pool_bwd");
 }
 
@@ -1036,8 +1053,9 @@ static int bn_apply_p16_impl(const float* x, const float* mean, const float* rst
         n4 /= 4;                                                   // the compact index space [N, H/2, W/2, C/4]
     }
     const int grid = channel_aligned_grid(n4, C);
-    hipLaunchKernelGGL(bn_apply_p16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma, beta, residual, residual_p16, rbn, relu,
-                       out32, out_f16, out_bf16, reinterpret_cast<unsigned long long*>(relu_mask), overflow_flag, n4, C / 4, even_h, even_w);
+    STREAM_DISPATCH(stream_on(STREAM_APPLY), NT,
+                    hipLaunchKernelGGL(bn_apply_p16_kernel<NT>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma, beta, residual, residual_p16, rbn, relu,
+                                       out32, out_f16, out_bf16, reinterpret_cast<unsigned long long*>(relu_mask), overflow_flag, n4, C / 4, even_h, even_w));
     return bdetr_launch_status("bn_apply_p16");
 }
 
@@ -1060,10 +1078,11 @@ extern "C" int bdetr_bn_apply_p16_even_pixels(const float* x, const float* mean,
 
 namespace {
 // x <- x * mask, mask = bn_apply_p16's 1-bit ReLU mask (the fallback for a lazily masked skip gradient, see ops.py)
+template <bool NT>
 __global__ __launch_bounds__(256) void relu_mask_apply_kernel(float* __restrict__ x, const unsigned long long* __restrict__ mask, int64_t n4) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        const unsigned pm = relu_mask_bits4(mask, i);
-        f32x4 v = reinterpret_cast<f32x4*>(x)[i];
+        const unsigned pm = relu_mask_bits4<NT>(mask, i);
+        f32x4 v = ld_stream4<NT>(x, i);
 #pragma unroll
         for (int e = 0; e < 4; ++e) if (!((pm >> e) & 1u)) v[e] = 0.f;
         reinterpret_cast<f32x4*>(x)[i] = v;
@@ -1073,8 +1092,9 @@ __global__ __launch_bounds__(256) void relu_mask_apply_kernel(float* __restrict_
 
 extern "C" int bdetr_relu_mask_apply(float* x, const uint64_t* relu_mask, int64_t n, void* stream) {
     BDETR_CHECK_ARG(x && relu_mask && n > 0 && n % 4 == 0, "bdetr_relu_mask_apply: bad arguments (n %% 4 == 0 required)");
-    hipLaunchKernelGGL(relu_mask_apply_kernel, dim3(ew_grid(n / 4, 256, 2)), dim3(256), 0, (hipStream_t)stream, x,
-                       reinterpret_cast<const unsigned long long*>(relu_mask), n / 4);
+    STREAM_DISPATCH(stream_on(STREAM_APPLY_OTHER), NT,
+                    hipLaunchKernelGGL(relu_mask_apply_kernel<NT>, dim3(ew_grid(n / 4, 256, 2)), dim3(256), 0, (hipStream_t)stream, x,
+                                       reinterpret_cast<const unsigned long long*>(relu_mask), n / 4));
     return bdetr_launch_status("relu_mask_apply");
 }
 
@@ -1098,7 +1118,6 @@ static int bn_bwd_p16_impl(const float* dout, const void* out, int out_p16, cons
     if (pre_g != nullptr) {
         sum_partials2(pre_g, pre_gx, pre_n, C, dbeta, dgamma, st);
     } else {
-        BnBwdFn f{dout, reinterpret_cast<const float*>(out), x, mean, rstd, gamma, beta, C, relu, out_p16, even_h, even_w, dout_compact};
         int64_t red_rows = rows;
         if (even_h > 0) {
             red_rows = rows / ((int64_t)even_h * even_w) * ((even_h + 1) / 2) * ((even_w + 1) / 2);
@@ -1106,12 +1125,15 @@ static int bn_bwd_p16_impl(const float* dout, const void* out, int out_p16, cons
             nch = (int)cdiv64(red_rows, rpc);
             pb = ws + (int64_t)nch * C;
         }
-        hipLaunchKernelGGL((colreduce2_kernel<BnBwdFn>), dim3(g.gx, nch), dim3(256), 0, st, f, red_rows, C, g.tx, rpc, pa, pb);
+        STREAM_DISPATCH(stream_on(STREAM_REDUCE), NT,
+                        BnBwdFn<NT> f{dout, reinterpret_cast<const float*>(out), x, mean, rstd, gamma, beta, C, relu, out_p16, even_h, even_w, dout_compact};
+                        hipLaunchKernelGGL((colreduce2_kernel<BnBwdFn<NT>>), dim3(g.gx, nch), dim3(256), 0, st, f, red_rows, C, g.tx, rpc, pa, pb));
         sum_partials2(pa, pb, nch, C, dbeta, dgamma, st);
     }
     const int64_t n4 = rows * C / 4;
-    hipLaunchKernelGGL(bn_bwd_apply_p16_kernel, dim3(channel_aligned_grid(n4, C)), dim3(256), 0, st, dout, out, out_p16, x, mean, rstd, gamma, beta, dgamma, dbeta,
-                       relu, frozen, dx32, dx_bf16, dresidual, n4, C / 4, 1.0f / (float)rows, dout_compact ? even_h : 0, dout_compact ? even_w : 0);
+    STREAM_DISPATCH(stream_on(STREAM_APPLY), NT,
+                    hipLaunchKernelGGL(bn_bwd_apply_p16_kernel<NT>, dim3(channel_aligned_grid(n4, C)), dim3(256), 0, st, dout, out, out_p16, x, mean, rstd, gamma, beta, dgamma, dbeta,
+                                       relu, frozen, dx32, dx_bf16, dresidual, n4, C / 4, 1.0f / (float)rows, dout_compact ? even_h : 0, dout_compact ? even_w : 0));
     return bdetr_launch_status("bn_bwd_p16");
 }
 

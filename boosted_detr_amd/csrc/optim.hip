@@ -6,6 +6,7 @@
 //   v  <- m*v - lr*g ;  w <- w + m*v - lr*g
 // and the AdamW line next to it in the same cell (tfa.optimizers.AdamW = Keras Adam + decoupled weight decay), see adamw_apply_kernel.
 #include "common.h"
+#include "stream.h"
 
 namespace {
 
@@ -14,6 +15,8 @@ struct TensorTriple { float* w; float* g; float* v; };
 // one workgroup per (tensor, slab): deterministic per-slab partial sums of g^2
 constexpr int SLAB = 16384;
 
+// NT: the gradient loads carry the non-temporal hint (stream.h)
+template <bool NT>
 __global__ __launch_bounds__(256) void sqnorm_kernel(const uint64_t* __restrict__ ptrs, const int64_t* __restrict__ sizes,
                                                      const int64_t* __restrict__ slab_tensor, const int64_t* __restrict__ slab_first,
                                                      float* __restrict__ partial, int stride) {
@@ -27,8 +30,8 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const uint64_t* __restrict_
     // multiple of 16,384 elements), the last 1-3 elements one by one: the 4-byte form ran at 2.1 TB/s (round 5)
     const int64_t end = min(n, off + SLAB), nq = (reinterpret_cast<uintptr_t>(g) & 15) == 0 ? (end - off) >> 2 : 0;
     const f32x4* g4 = reinterpret_cast<const f32x4*>(g + off);
-    for (int64_t q = threadIdx.x; q < nq; q += 256) { const f32x4 x = g4[q]; s += x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3]; }
-    for (int64_t i = off + 4 * nq + threadIdx.x; i < end; i += 256) { float x = g[i]; s += x * x; }
+    for (int64_t q = threadIdx.x; q < nq; q += 256) { const f32x4 x = ld_stream<NT>(g4 + q); s += x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3]; }
+    for (int64_t i = off + 4 * nq + threadIdx.x; i < end; i += 256) { float x = ld_stream<NT>(g + i); s += x * x; }
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
     __syncthreads();
@@ -48,6 +51,9 @@ __global__ __launch_bounds__(256) void norm_final_kernel(const float* __restrict
     if (guard != nullptr && !(fabsf(nrm) <= 3.0e38f)) *guard = 1;
 }
 
+// NT: gradient and momentum loads non-temporal (their last use this step); NTS: the momentum store too (its next reader is a step away).
+// The weight's load and store keep the default policy: the weight pack reads the weights next.
+template <bool NT, bool NTS>
 __global__ __launch_bounds__(256) void sgd_apply_kernel(const uint64_t* __restrict__ ptrs, const int64_t* __restrict__ sizes,
                                                         const int64_t* __restrict__ slab_tensor, const int64_t* __restrict__ slab_first,
                                                         const float* __restrict__ norms, const float* __restrict__ lr_p,
@@ -71,7 +77,7 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(const uint64_t* __restri
     f32x4* v4 = reinterpret_cast<f32x4*>(v + off);
     f32x4* w4 = reinterpret_cast<f32x4*>(w + off);
     for (int64_t q = threadIdx.x; q < nq; q += 256) {             // (the same arithmetic per element as the scalar tail below)
-        const f32x4 gq = g4[q], vq = v4[q], wq = w4[q];
+        const f32x4 gq = ld_stream<NT>(g4 + q), vq = ld_stream<NT>(v4 + q), wq = w4[q];
         f32x4 vn, wn;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -79,12 +85,12 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(const uint64_t* __restri
             vn[e] = momentum * vq[e] - lr * gi;
             wn[e] = wq[e] + momentum * vn[e] - lr * gi;
         }
-        v4[q] = vn; w4[q] = wn;
+        st_stream<NTS>(v4 + q, vn); w4[q] = wn;
     }
     for (int64_t i = off + 4 * nq + threadIdx.x; i < end; i += 256) {
-        const float gi = g[i] * scale;
-        const float vn = momentum * v[i] - lr * gi;
-        v[i] = vn;
+        const float gi = ld_stream<NT>(g + i) * scale;
+        const float vn = momentum * ld_stream<NT>(v + i) - lr * gi;
+        st_stream<NTS>(v + i, vn);
         w[i] = w[i] + momentum * vn - lr * gi;
     }
 }
@@ -166,9 +172,12 @@ extern "C" int bdetr_sgd_nesterov_clipnorm(const uint64_t* ptrs, const int64_t* 
     BDETR_CHECK_ARG(ptrs && sizes && slab_tensor && slab_first && partial && norms && lr && ntensors > 0 && nslabs > 0,
                     "bdetr_sgd_nesterov_clipnorm: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sqnorm_kernel, dim3(nslabs), dim3(256), 0, st, ptrs, sizes, slab_tensor, slab_first, partial, 3);
+    // (the norm pass reads the gradients the apply pass reads again: it takes the hint of the reductions, not the optimizer's)
+    STREAM_DISPATCH(stream_on(STREAM_REDUCE), NT,
+                    hipLaunchKernelGGL(sqnorm_kernel<NT>, dim3(nslabs), dim3(256), 0, st, ptrs, sizes, slab_tensor, slab_first, partial, 3));
     hipLaunchKernelGGL(norm_final_kernel, dim3((ntensors + 255) / 256), dim3(256), 0, st, partial, slab_first, ntensors, norms, skip_flag);
-    hipLaunchKernelGGL(sgd_apply_kernel, dim3(nslabs), dim3(256), 0, st, ptrs, sizes, slab_tensor, slab_first, norms, lr, momentum, clipnorm, grad_scale, skip_flag);
+    STREAM_DISPATCH(stream_on(STREAM_OPTIM), NT, STREAM_DISPATCH(stream_on(STREAM_MOM_STORE), NTS,
+                    hipLaunchKernelGGL((sgd_apply_kernel<NT, NTS>), dim3(nslabs), dim3(256), 0, st, ptrs, sizes, slab_tensor, slab_first, norms, lr, momentum, clipnorm, grad_scale, skip_flag)));
     return bdetr_launch_status("sgd_nesterov_clipnorm");
 }
 
@@ -181,7 +190,8 @@ extern "C" int bdetr_adamw_clipnorm(const uint64_t* ptrs, const int64_t* sizes, 
     BDETR_CHECK_ARG(ptrs && sizes && slab_tensor && slab_first && partial && norms && step_scalars && ntensors > 0 && nslabs > 0,
                     "bdetr_adamw_clipnorm: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sqnorm_kernel, dim3(nslabs), dim3(256), 0, st, ptrs, sizes, slab_tensor, slab_first, partial, 4);
+    STREAM_DISPATCH(stream_on(STREAM_REDUCE), NT,
+                    hipLaunchKernelGGL(sqnorm_kernel<NT>, dim3(nslabs), dim3(256), 0, st, ptrs, sizes, slab_tensor, slab_first, partial, 4));
     hipLaunchKernelGGL(norm_final_kernel, dim3((ntensors + 255) / 256), dim3(256), 0, st, partial, slab_first, ntensors, norms, skip_flag);
     hipLaunchKernelGGL(adamw_apply_kernel, dim3(nslabs), dim3(256), 0, st, ptrs, sizes, slab_tensor, slab_first, norms, step_scalars, decays,
                        beta1, beta2, one_minus_beta1, one_minus_beta2, epsilon, clipnorm, grad_scale, skip_flag);

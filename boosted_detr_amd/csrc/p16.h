@@ -2,8 +2,10 @@
 // consecutive fp32 values into the 32-byte group [8 x hi][8 x lo] and back.
 #pragma once
 #include "common.h"
+#include "stream.h"
 
 typedef unsigned int p16_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int p16_u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 p16_bf16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 p16_f16x2 __attribute__((ext_vector_type(2)));
 typedef float p16_f32x2 __attribute__((ext_vector_type(2)));
@@ -97,10 +99,13 @@ __device__ __forceinline__ void p16_store4(void* base, int64_t f4_index, float v
     reinterpret_cast<p16_u32x4*>(base)[f4_index] = w;
 }
 // the lane's four values back from an f16 pair tensor
+// (NT, here and in p16_positive4_bf16: the 8-byte loads carry the non-temporal hint, stream.h.  8-byte loads: a pair tensor's base is
+// 16-byte aligned and a lane's halves sit at multiples of 8 inside its 32-byte group.)
+template <bool NT = false>
 __device__ __forceinline__ void p16_load4_f16(const void* base, int64_t f4_index, float (&v)[4]) {
     const char* g = reinterpret_cast<const char*>(base) + (f4_index >> 1) * 32 + (f4_index & 1) * 8;
-    const unsigned h0 = reinterpret_cast<const unsigned*>(g)[0], h1 = reinterpret_cast<const unsigned*>(g)[1];
-    const unsigned l0 = reinterpret_cast<const unsigned*>(g + 16)[0], l1 = reinterpret_cast<const unsigned*>(g + 16)[1];
+    const p16_u32x2 h = ld_stream<NT>(reinterpret_cast<const p16_u32x2*>(g)), l = ld_stream<NT>(reinterpret_cast<const p16_u32x2*>(g + 16));
+    const unsigned h0 = h[0], h1 = h[1], l0 = l[0], l1 = l[1];
     const p16_f32x2 a = __builtin_convertvector(__builtin_bit_cast(p16_f16x2, h0), p16_f32x2), b = __builtin_convertvector(__builtin_bit_cast(p16_f16x2, h1), p16_f32x2);
     const p16_f32x2 c = __builtin_convertvector(__builtin_bit_cast(p16_f16x2, l0), p16_f32x2), d = __builtin_convertvector(__builtin_bit_cast(p16_f16x2, l1), p16_f32x2);
     v[0] = a[0] + c[0]; v[1] = a[1] + c[1];
@@ -108,9 +113,11 @@ __device__ __forceinline__ void p16_load4_f16(const void* base, int64_t f4_index
 }
 // bit e set when element e of the lane's four is > 0 in a bf16 pair tensor (the hi half decides: bf16 keeps fp32's
 // exponent range, so hi > 0 <=> x > 0 for every normal x)
+template <bool NT = false>
 __device__ __forceinline__ unsigned p16_positive4_bf16(const void* base, int64_t f4_index) {
     const char* g = reinterpret_cast<const char*>(base) + (f4_index >> 1) * 32 + (f4_index & 1) * 8;
-    const unsigned h0 = reinterpret_cast<const unsigned*>(g)[0], h1 = reinterpret_cast<const unsigned*>(g)[1];
+    const p16_u32x2 h = ld_stream<NT>(reinterpret_cast<const p16_u32x2*>(g));
+    const unsigned h0 = h[0], h1 = h[1];
     auto pos = [](unsigned h16) { return (h16 & 0x8000u) == 0u && (h16 & 0x7FFFu) != 0u; };
     return (pos(h0 & 0xFFFFu) ? 1u : 0u) | (pos(h0 >> 16) ? 2u : 0u) | (pos(h1 & 0xFFFFu) ? 4u : 0u) | (pos(h1 >> 16) ? 8u : 0u);
 }

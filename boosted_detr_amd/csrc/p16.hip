@@ -48,6 +48,8 @@ __global__ __launch_bounds__(256) void p16_pack_wt_kernel(const float* __restric
 
 // every registered conv weight in ONE launch: row t of the table = {w, w_f16, wt_bf16, K, R, S, C} (int64 each);
 // blockIdx.y = tensor, the blocks of a row grid-stride over its 8-element groups (both copies)
+// NT: the weight loads carry the non-temporal hint (stream.h) - the pack is the weights' last reader of the step
+template <bool NT>
 __global__ __launch_bounds__(256) void p16_pack_weights_multi_kernel(const int64_t* __restrict__ table, int* __restrict__ overflow_flag) {
     const int64_t* row = table + (int64_t)blockIdx.y * 7;
     const float* w = reinterpret_cast<const float*>(row[0]);
@@ -57,7 +59,7 @@ __global__ __launch_bounds__(256) void p16_pack_weights_multi_kernel(const int64
     const int64_t n8 = (int64_t)K * R * S * C / 8;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
         if (wf != nullptr) {
-            const f32x4 a = reinterpret_cast<const f32x4*>(w)[2 * i], b = reinterpret_cast<const f32x4*>(w)[2 * i + 1];
+            const f32x4 a = ld_stream4<NT>(w, 2 * i), b = ld_stream4<NT>(w, 2 * i + 1);
             const float v[8] = {a[0] * P16_W_SCALE, a[1] * P16_W_SCALE, a[2] * P16_W_SCALE, a[3] * P16_W_SCALE,
                                 b[0] * P16_W_SCALE, b[1] * P16_W_SCALE, b[2] * P16_W_SCALE, b[3] * P16_W_SCALE};      // the forward copy holds 2^8 w (p16.h)
             p16_store8<true>(wf + i * 32, v);
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(256) void p16_pack_weights_multi_kernel(const int64
             const int src_tap = (R - 1 - r) * S + (S - 1 - s2);
             float v[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = w[((int64_t)(kg * 8 + e) * R * S + src_tap) * C + c];
+            for (int e = 0; e < 8; ++e) v[e] = ld_stream<NT>(w + ((int64_t)(kg * 8 + e) * R * S + src_tap) * C + c);
             p16_store8<false>(wt + (((int64_t)c * R * S + tap) * K + kg * 8) * 4, v);
         }
     }
@@ -80,7 +82,8 @@ __global__ __launch_bounds__(256) void p16_pack_weights_multi_kernel(const int64
 
 extern "C" int bdetr_p16_pack_conv_weights_multi(const int64_t* table, int ntensors, int* overflow_flag, void* stream) {
     BDETR_CHECK_ARG(table && ntensors > 0, "bdetr_p16_pack_conv_weights_multi: bad arguments");
-    hipLaunchKernelGGL(p16_pack_weights_multi_kernel, dim3(48, ntensors), dim3(256), 0, (hipStream_t)stream, table, overflow_flag);
+    STREAM_DISPATCH(stream_on(STREAM_OPTIM), NT,
+                    hipLaunchKernelGGL(p16_pack_weights_multi_kernel<NT>, dim3(48, ntensors), dim3(256), 0, (hipStream_t)stream, table, overflow_flag));
     return bdetr_launch_status("p16_pack_conv_weights_multi");
 }
 

@@ -200,7 +200,7 @@ constexpr int lds_bytes_for(int bm, int bn, int ns) { return ns * (bm + bn) * 12
 // runs.  The buffer descriptor covers exactly the tile's valid rows (rows past I are dropped by the buffer unit's range
 // check), a lane's column is valid or not for the whole tile (an invalid one starts 2 GB out of range), and the row
 // offset is one running VGPR: a store costs one add, and the second 32-column block rides the instruction's immediate.
-enum { EPI_PLAIN = 0, EPI_ROWMAP = 1, EPI_VEC = 8, EPI_BNB2 = 16, EPI_COMPACT = 32 };      // EPI_COMPACT (with EPI_VEC): only the masked accumulate whose OLD gradient is a compact even-pixel tensor (GemmParams::acc_src)      // EPI_BNB2 (with EPI_VEC): only the masked accumulate + masked sums + second-BatchNorm sum form
+enum { EPI_PLAIN = 0, EPI_ROWMAP = 1, EPI_VEC = 8, EPI_BNB2 = 16, EPI_COMPACT = 32, EPI_STREAM = 64 };      // EPI_STREAM (with EPI_VEC, masked accumulates): gemm_epilogue's STREAM      // EPI_COMPACT (with EPI_VEC): only the masked accumulate whose OLD gradient is a compact even-pixel tensor (GemmParams::acc_src)      // EPI_BNB2 (with EPI_VEC): only the masked accumulate + masked sums + second-BatchNorm sum form
 template <int BM, int BN, int WM, int WN, bool STATS = true, int EPI = EPI_ROWMAP>
 __device__ __forceinline__ void direct_epilogue(f32x16 (&acc)[BM / WM / 32][BN / WN / 32], const GemmParams& g, int tile_i, int i0, int j0, const float* bias_pre) {
     constexpr int WTM = BM / WM, WTN = BN / WN, TM = WTM / 32, TN = WTN / 32;
@@ -757,7 +757,7 @@ void sgemm_kernel(typename LA::Op opa, typename LB::Op opb, GemmParams g)
             atomic_epilogue<BM, BN, WM, WN>(acc, g, i0, j0);
             return;
         }
-        gemm_epilogue<BM, BN, WM, WN, NT, LDS_BYTES / 4, (EPI & EPI_VEC) != 0, (EPI & EPI_BNB2) != 0, (EPI & EPI_COMPACT) != 0>(acc, g, reinterpret_cast<float*>(lds), tile_i, i0, j0, g.c + (g.splitk > 1 ? (int64_t)zz * g.sc0 : 0), bias_pre);
+        gemm_epilogue<BM, BN, WM, WN, NT, LDS_BYTES / 4, (EPI & EPI_VEC) != 0, (EPI & EPI_BNB2) != 0, (EPI & EPI_COMPACT) != 0, (EPI & EPI_STREAM) != 0>(acc, g, reinterpret_cast<float*>(lds), tile_i, i0, j0, g.c + (g.splitk > 1 ? (int64_t)zz * g.sc0 : 0), bias_pre);
     }
 }
 
@@ -843,10 +843,13 @@ int launch_cfg(const typename LA::Op& a, const typename LB::Op& b, GemmParams g,
             if (g.acc_src != nullptr) {
                 BDETR_CHECK_ARG(g.acc_mask != nullptr && g.bnb2_y == nullptr && g.acc_H > 0 && g.acc_W > 0 && g.acc_H % 2 == 0 && g.acc_W % 2 == 0 && g.I % (g.acc_H * g.acc_W) == 0,
                                 "sgemm: a compact old gradient needs the masked accumulate, an even map that divides the rows, and no second BatchNorm");
+                if (stream_on(STREAM_GEMM_EPI)) return go(std::integral_constant<int, EPI_VEC | EPI_COMPACT | EPI_STREAM>{});
                 return go(std::integral_constant<int, EPI_VEC | EPI_COMPACT>{});
             }
-            if (g.bnb2_y != nullptr) return go(std::integral_constant<int, EPI_VEC | EPI_BNB2>{});
-            return go(std::integral_constant<int, EPI_VEC>{});
+            // (the policy is a template parameter of the masked accumulates only: the other forms have no stream-once operand)
+            const bool nt = g.acc_mask != nullptr && stream_on(STREAM_GEMM_EPI);
+            if (g.bnb2_y != nullptr) return nt ? go(std::integral_constant<int, EPI_VEC | EPI_BNB2 | EPI_STREAM>{}) : go(std::integral_constant<int, EPI_VEC | EPI_BNB2>{});
+            return nt ? go(std::integral_constant<int, EPI_VEC | EPI_STREAM>{}) : go(std::integral_constant<int, EPI_VEC>{});
         }
         BDETR_CHECK_ARG(g.acc_mask == nullptr && g.bnb_y == nullptr, "sgemm: masks / fused sums are not available with a row map");
         // persistent: as many workgroups as stay resident (a multiple of 8: one XCD per workgroup for all its tiles)

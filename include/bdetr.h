@@ -31,6 +31,10 @@ int         bdetr_abi_version(void);
 const char* bdetr_last_error(void);
 /* number of CUs of the current device (used by the host to size split-K) */
 int         bdetr_device_cus(void);
+/* (additive) The cache policy of stream-once operands in force for this process: BDETR_STREAM_POLICY, read once - a sum of operand-class
+ * bits (csrc/stream.h), 0 = every access uses the default policy; a value outside 0..63 is reported on stderr and the built-in default stays.  A policy
+ * changes no result. */
+int         bdetr_stream_policy(void);
 
 /* A non-blocking stream of the lowest priority class of the device (never destroyed: process lifetime), for
  * work that must not delay the caller's critical path (the host's weight-gradient side stream), and the
