@@ -315,6 +315,8 @@ def test_maxpool(cuda):
 
 
 def test_activations(cuda):
+    """Unit-scale inputs only (|x / 100| < 2 for the box sigmoid, |x| < 16 for the sigmoid): saturation, +-inf, NaN, -0.0 and the
+    exp overflow points are tests/test_value_domain_gpu.py::test_pointwise_saturation_and_specials."""
     from boosted_detr_amd import kernels as k
     x, dy = rnd(1000, seed=1) * 50, rnd(1000, seed=2)
     xd = x.double().requires_grad_(True)
