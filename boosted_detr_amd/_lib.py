@@ -153,6 +153,9 @@ SIGNATURES = {
     "bdetr_attention_head_dim": (I, []),
     "bdetr_attention_fwd": (I, [P, P, P, P, P, I, I, I, I, F, P]),
     "bdetr_attention_bwd": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, P]),
+    "bdetr_attention_masked_fwd": (I, [P, P, P, P, P, I, I, I, I, F, P, L, L, L, I, P]),
+    "bdetr_attention_masked_bwd": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, P, L, L, L, I, P]),
+    "bdetr_attention_mask_apply": (I, [P, P, I, I, I, I, P, L, L, L, I, I, P]),
     "bdetr_softmax_rows_fwd": (I, [P, P, L, I, F, P]),
     "bdetr_softmax_rows_bwd": (I, [P, P, P, L, I, F, P]),
     "bdetr_add_dropout_layernorm_fwd": (I, [P, P, P, P, P, P, P, L, I, F, F, U64, P, P]),

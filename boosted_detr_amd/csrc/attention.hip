@@ -230,12 +230,63 @@ __device__ __forceinline__ void col_operand(ColOperand<AR>& c, const float* __re
     if constexpr (AR != AR_FP32) c.f = col_frag<AR>(c.r);
 }
 
-template <int AR>
+// ---------------- attention masks (include/bdetr.h K32 / K33) ----------------
+// One compile-time parameter MK on the three tiled kernels (the way csrc/coco_match.h takes its F1 gate): MK_NONE compiles every
+// line below away.  (KO beside it says whether the mask is key-only, sq == 0 - the common case, a padding mask: it then costs one
+// register or 256 bytes of LDS, and must not pay the registers of the per-element loads of a full mask.)
+// MK_F32 (multiply): the softmax runs over ALL keys, only the tile handed to the V^T P^T product (and, in the backward, to dV) is
+// p * m, and dP is multiplied by m before dS.  MK_U8 (exclusion): a key whose byte is 0 has score -inf.
+// The mask is [B or 1, h or 1, q or 1, nk] with element strides sb / sh / sq (0 on a broadcast axis) and unit stride along keys.
+// Every element of a full mask is read by a one-element load of its own, predicated on key < nk and on the lane owning a row: mask
+// rows are not 16-byte aligned in general (nk = 49) and nothing may read past a row's or the tensor's end.
+enum { MK_NONE = 0, MK_F32 = 1, MK_U8 = 2 };
+struct MaskArg { const void* p; int64_t sb, sh, sq; };
+template <int MK> struct MaskElem { typedef float type; };
+template <> struct MaskElem<MK_U8> { typedef unsigned char type; };
+template <int MK>
+__device__ __forceinline__ float mask_value(typename MaskElem<MK>::type x) {
+    if constexpr (MK == MK_U8) return x != 0 ? 1.f : 0.f; else return x;
+}
+// Query on the lane (forward, dQ): mv[e] = mask[this lane's query][k0 + crow(e, lh)], 0 at keys >= nk and on lanes without a query.
+// (base: the (image, head) plane, uniform; row0: this lane's row offset in it.  Offsets inside a plane are 32-bit - check_mask
+// bounds the plane -, so an address is the scalar base plus ONE register.)
+template <int MK>
+__device__ __forceinline__ void mask_keys_of_query(float (&mv)[16], const typename MaskElem<MK>::type* __restrict__ base, unsigned row0, bool ok, int k0, int nk, int lh) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int kk = k0 + crow(e, lh);
+        float x = 0.f;
+        if (ok && kk < nk) x = mask_value<MK>(base[row0 + (unsigned)kk]);
+        mv[e] = x;
+    }
+}
+// A key-only mask (sq == 0: [B,1,1,k], [1,h,1,k]) is the same 64 values for every query of the workgroup: threads 0..63 stage the
+// chunk's values in LDS beside the streamed chunk, and a lane reads its 16 as four broadcast 16-byte reads.
+template <int MK>
+__device__ __forceinline__ void mask_stage_keys(float* __restrict__ sM, const typename MaskElem<MK>::type* __restrict__ row, int c0, int nk) {
+    if (threadIdx.x < CH) {
+        const int kk = c0 + (int)threadIdx.x;
+        sM[threadIdx.x] = kk < nk ? mask_value<MK>(row[kk]) : 0.f;
+    }
+}
+__device__ __forceinline__ void mask_keys_staged(float (&mv)[16], const float* __restrict__ sM, int t, int lh) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(sM + 32 * t + 8 * c + 4 * lh);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) mv[4 * c + e] = v[e];
+    }
+}
+
+template <int AR, int MK, bool KO>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                        float* __restrict__ o, float* __restrict__ lse,
-                                                       int h, int nq, int nk, float scale) {
+                                                       int h, int nq, int nk, float scale, MaskArg mk) {
     __shared__ __attribute__((aligned(16))) unsigned char sK[SMEM_BYTES];
     __shared__ __attribute__((aligned(16))) unsigned char sV[SMEM_BYTES];
+    typedef typename MaskElem<MK>::type MT;
+    float* sM = nullptr;
+    if constexpr (MK != MK_NONE && KO) { __shared__ __attribute__((aligned(16))) float sMask[CH]; sM = sMask; }
     const int b = blockIdx.z, head = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, lh = lane >> 5;
     const int64_t D = (int64_t)h * AD;
@@ -245,6 +296,15 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
     col_operand<AR>(qr, q + (int64_t)b * nq * D + head * AD, D, qi, qok, lh);
     const float* kbase = k + (int64_t)b * nk * D + head * AD;
     const float* vbase = v + (int64_t)b * nk * D + head * AD;
+    const MT* mbase = nullptr;                                  // this (image, head)'s mask plane; mrow: this lane's query row in it
+    unsigned mrow = 0;
+    if constexpr (MK != MK_NONE) {
+        mbase = static_cast<const MT*>(mk.p) + (int64_t)b * mk.sb + (int64_t)head * mk.sh;
+        mrow = qok ? (unsigned)qi * (unsigned)mk.sq : 0u;
+    }
+    auto mask_tile = [&](float (&mv)[16], int c0, int t) {
+        if constexpr (KO) mask_keys_staged(mv, sM, t, lh); else mask_keys_of_query<MK>(mv, mbase, mrow, qok, c0 + 32 * t, nk, lh);
+    };
 
     f32x16 oacc;
 #pragma unroll
@@ -264,6 +324,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
         __syncthreads();
         chunk_store<AR>(sK, ck[0]);
         chunk_store<AR>(sV, cv[0]);
+        if constexpr (MK != MK_NONE && KO) mask_stage_keys<MK>(sM, mbase, c0, nk);
         __syncthreads();
 #pragma unroll
         for (int p = 0; p + 1 < APF; ++p) { ck[p] = ck[p + 1]; cv[p] = cv[p + 1]; }
@@ -284,32 +345,56 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
 #pragma unroll
                 for (int e = 0; e < 16; ++e) if (!(c0 + 32 * t + crow(e, lh) < nk)) s[t][e] = -INFINITY;
         }
+        if constexpr (MK == MK_U8) {                               // exclusion: the key takes no part in the softmax
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                float mv[16];
+                mask_tile(mv, c0, t);
+#pragma unroll
+                for (int e = 0; e < 16; ++e) s[t][e] = mv[e] != 0.f ? s[t][e] : -INFINITY;
+            }
+        }
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int e = 0; e < 16; ++e) cmax = fmaxf(cmax, s[t][e]);
         cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
         const float mn = fmaxf(m, cmax);
-        const float alpha = exp2_fast(m - mn);
+        // exclusion: while no key has been kept yet the running maximum is still -inf, and (-inf) - (-inf) is NaN: subtract 0 then
+        // (alpha = 2^-inf = 0, every p = 2^-inf = 0).  With a finite maximum this is the unmasked arithmetic, bit for bit.
+        float mref = mn;
+        if constexpr (MK == MK_U8) mref = mn == -INFINITY ? 0.f : mn;
+        const float alpha = exp2_fast(m - mref);
         float psum = 0.f;
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) { const float p = exp2_fast(s[t][e] - mn); s[t][e] = p; psum += p; }
+            for (int e = 0; e < 16; ++e) { const float p = exp2_fast(s[t][e] - mref); s[t][e] = p; psum += p; }
         psum += __shfl_xor(psum, 32, 64);
         l = l * alpha + psum;
         m = mn;
 #pragma unroll
         for (int e = 0; e < 16; ++e) oacc[e] *= alpha;
 #pragma unroll
-        for (int t = 0; t < 2; ++t) rowsT_x_tile<AR>(oacc, sV, t, s[t], lane);       // O^T += V^T P^T
+        for (int t = 0; t < 2; ++t) {
+            if constexpr (MK == MK_F32) {                          // multiply: l above summed the unmasked p; only this tile is p * m
+                float mv[16];
+                mask_tile(mv, c0, t);
+#pragma unroll
+                for (int e = 0; e < 16; ++e) s[t][e] *= mv[e];
+            }
+            rowsT_x_tile<AR>(oacc, sV, t, s[t], lane);             // O^T += V^T P^T
+        }
     }
     if (qok) {
-        const float inv = 1.0f / l;
+        float inv = 1.0f / l;
+        if constexpr (MK == MK_U8) if (!(l > 0.f)) { inv = 0.f; m = -INFINITY; }          // a row with no kept key: O = 0, lse = -inf
         float* orow = o + (((int64_t)b * h + head) * nq + qi) * AD;
 #pragma unroll
         for (int e = 0; e < 16; ++e) orow[crow(e, lh)] = oacc[e] * inv;
-        if (lh == 0) lse[((int64_t)b * h + head) * nq + qi] = m * LN2 + logf(l);          // (m is a log2-domain maximum)
+        float lrow = m * LN2 + logf(l);                                                   // (m is a log2-domain maximum)
+        if constexpr (MK == MK_U8) if (!(l > 0.f)) lrow = -INFINITY;
+        if (lh == 0) lse[((int64_t)b * h + head) * nq + qi] = lrow;
     }
 }
 
@@ -328,14 +413,22 @@ __global__ __launch_bounds__(256) void attn_dvec_kernel(const float* __restrict_
 
 // KCOL == false: columns = queries, streamed rows = keys     -> out1 = dQ
 // KCOL == true : columns = keys,    streamed rows = queries  -> out1 = dK, out2 = dV
-template <bool KCOL, int AR>
+// With a mask (MK, above): dP = M * (dO V^T) and dV = (P * M)^T dO under the multiply rule - dS = P (dP - D) scale holds unchanged
+// because sum_k P_k M_k (dO . V_k) = dO . O, so attn_dvec_kernel is the unmasked one -; under exclusion P is 0 at an excluded key, and
+// a row with no kept key (lse = -inf) has P = 0 everywhere.  KCOL == false reads the mask as the forward does; KCOL == true owns one
+// key per lane and streams queries, so it reads mask[q = c0 + r][k = ci]: consecutive lanes, consecutive addresses (a key-only mask:
+// one value per lane, loaded once).
+template <bool KCOL, int AR, int MK, bool KO>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                        const float* __restrict__ d_o, const float* __restrict__ lse, const float* __restrict__ dvec,
                                                        float* __restrict__ out1, float* __restrict__ out2,
-                                                       int h, int nq, int nk, float scale) {
+                                                       int h, int nq, int nk, float scale, MaskArg mk) {
     __shared__ __attribute__((aligned(16))) unsigned char sR1[SMEM_BYTES];
     __shared__ __attribute__((aligned(16))) unsigned char sR2[SMEM_BYTES];
     __shared__ float sL[CH], sD[CH];
+    typedef typename MaskElem<MK>::type MT;
+    float* sM = nullptr;
+    if constexpr (MK != MK_NONE && KO && !KCOL) { __shared__ __attribute__((aligned(16))) float sMask[CH]; sM = sMask; }
     const int b = blockIdx.z, head = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, lh = lane >> 5;
     const int64_t D = (int64_t)h * AD;
@@ -359,6 +452,35 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
     float Lcol = 0.f, Dcol = 0.f;
     if (!KCOL && cok) { Lcol = lse[bh * nq + ci] * LOG2E; Dcol = dvec[bh * nq + ci]; }      // (log2 domain: see exp2_fast)
     const float scale2 = scale * LOG2E;
+    const MT* mbase = nullptr;                                  // this (image, head)'s mask plane; mrow: this lane's query row in it (dQ kernel)
+    unsigned mrow = 0;
+    float mcol = 0.f;                                           // key-only mask of this lane's key (dK/dV kernel)
+    if constexpr (MK != MK_NONE) {
+        mbase = static_cast<const MT*>(mk.p) + (int64_t)b * mk.sb + (int64_t)head * mk.sh;
+        if (!KCOL) mrow = cok ? (unsigned)ci * (unsigned)mk.sq : 0u;
+        if (KCOL && KO && cok) mcol = mask_value<MK>(mbase[ci]);
+    }
+    // dK/dV under a key-only float mask: m is a constant of the lane's key j, so M * (dO V^T) = dO (m_j V_j)^T and dV_j = m_j sum_r p dO_r:
+    // the V column is scaled once here, dV once at the end, and the loop below is the unmasked loop (m_j = 1: exact both times).
+    constexpr bool COLSCALE = KCOL && KO && MK == MK_F32;
+    if constexpr (COLSCALE) {
+#pragma unroll
+        for (int s = 0; s < 16; ++s) c2r.r[s] *= mcol;
+        if constexpr (AR != AR_FP32) c2r.f = col_frag<AR>(c2r.r);
+    }
+    auto mask_tile = [&](float (&mv)[16], int c0, int t) {
+        if constexpr (!KCOL) {
+            if constexpr (KO) mask_keys_staged(mv, sM, t, lh); else mask_keys_of_query<MK>(mv, mbase, mrow, cok, c0 + 32 * t, nk, lh);
+        } else if constexpr (!KO) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int qr = c0 + 32 * t + crow(e, lh);
+                float x = 0.f;
+                if (cok && qr < nq) x = mask_value<MK>(mbase[(unsigned)qr * (unsigned)mk.sq + (unsigned)ci]);
+                mv[e] = x;
+            }
+        }
+    };
 
     f32x16 acc1, acc2;
 #pragma unroll
@@ -380,6 +502,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
             sL[threadIdx.x] = qi < nq ? lse[bh * nq + qi] * LOG2E : 0.f;
             sD[threadIdx.x] = qi < nq ? dvec[bh * nq + qi] : 0.f;
         }
+        if constexpr (MK != MK_NONE && KO && !KCOL) mask_stage_keys<MK>(sM, mbase, c0, nk);
         __syncthreads();
 #pragma unroll
         for (int p = 0; p + 1 < APF; ++p) { c1[p] = c1[p + 1]; c2[p] = c2[p + 1]; }
@@ -390,14 +513,21 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
         for (int t = 0; t < 2; ++t) {
             f32x16 S = rows_x_col<AR>(sR1, t, c1r, li, lh);     // scores      (rows = streamed side)
             f32x16 G = rows_x_col<AR>(sR2, t, c2r, li, lh);     // dP          (same orientation)
+            float mv[16];
+            if constexpr (MK != MK_NONE && !(KCOL && KO)) mask_tile(mv, c0, t);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int r = 32 * t + crow(e, lh);
+                const float me = (MK == MK_NONE || COLSCALE) ? 1.f : (KCOL && KO) ? mcol : mv[e];
                 const float Lq = KCOL ? sL[r] : Lcol, Dq = KCOL ? sD[r] : Dcol;
                 // (a select, not a branch on the uniform `full`: the branched form measured 98 against 77 us on the encoder shape)
-                const float p = (full || c0 + r < nrow) ? exp2_fast(S[e] * scale2 - Lq) : 0.f;
-                S[e] = p * (G[e] - Dq) * scale;                  // dS (gradient w.r.t. the unscaled product)
+                float p = (full || c0 + r < nrow) ? exp2_fast(S[e] * scale2 - Lq) : 0.f;
+                if constexpr (MK == MK_U8) p = me != 0.f ? p : 0.f;        // (a select: 2^(s + inf) of a row with no kept key never multiplies)
+                float g = G[e];
+                if constexpr (MK == MK_F32 && !COLSCALE) g *= me;             // dP = M * (dO V^T)
+                S[e] = p * (g - Dq) * scale;                     // dS (gradient w.r.t. the unscaled product)
                 G[e] = p;
+                if constexpr (MK == MK_F32 && !COLSCALE) G[e] = p * me;       // dV takes P * M
             }
             rowsT_x_tile<AR>(acc1, sR1, t, S, lane);             // dQ^T += K^T dS^T   |  dK^T += Q^T dS
             if (KCOL) rowsT_x_tile<AR>(acc2, sR2, t, G, lane);   // dV^T += dO^T P
@@ -410,7 +540,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
         if (KCOL) {
             float* o2 = out2 + ((int64_t)b * ncol + ci) * D + head * AD;
 #pragma unroll
-            for (int e = 0; e < 16; ++e) o2[crow(e, lh)] = acc2[e];
+            for (int e = 0; e < 16; ++e) o2[crow(e, lh)] = COLSCALE ? acc2[e] * mcol : acc2[e];
         }
     }
 }
@@ -429,6 +559,71 @@ int check_attn(const void* a, const void* b, const void* c, int B, int h, int nq
     return 0;
 }
 
+// mask, its three element strides and the rule: checked before any launch.  The furthest element a kernel may address is
+// (B-1) sb + (h-1) sh + (nq-1) sq + nk - 1; that sum has to exist as an int64.
+int check_mask(const void* mask, int64_t sb, int64_t sh, int64_t sq, int mode, int B, int h, int nq, int nk, const char* who) {
+    BDETR_CHECK_ARG(mask != nullptr, "%s: null mask", who);
+    BDETR_CHECK_ARG(mode == BDETR_ATTN_MASK_MULTIPLY || mode == BDETR_ATTN_MASK_EXCLUDE, "%s: unknown mask mode %d", who, mode);
+    BDETR_CHECK_ARG(sb >= 0 && sh >= 0 && sq >= 0, "%s: negative mask stride (%lld, %lld, %lld)", who, (long long)sb, (long long)sh, (long long)sq);
+    int64_t a = 0, c = 0, d = 0, sum = 0;
+    const bool overflow = __builtin_mul_overflow((int64_t)(B - 1), sb, &a) || __builtin_mul_overflow((int64_t)(h - 1), sh, &c) ||
+                          __builtin_mul_overflow((int64_t)(nq - 1), sq, &d) || __builtin_add_overflow(a, c, &sum) ||
+                          __builtin_add_overflow(sum, d, &sum) || __builtin_add_overflow(sum, (int64_t)nk, &sum) ||
+                          sum > INT64_MAX / 4;                                       // (byte offsets of a float mask)
+    BDETR_CHECK_ARG(!overflow, "%s: mask size x stride overflows (strides %lld, %lld, %lld)", who, (long long)sb, (long long)sh, (long long)sq);
+    BDETR_CHECK_ARG(d + (int64_t)nk <= (int64_t)0x7fffffff, "%s: one (image, head) plane of the mask, (nq-1) sq + nk = %lld elements, exceeds 2^31 - 1",
+                    who, (long long)(d + nk));
+    BDETR_CHECK_ARG(mode != BDETR_ATTN_MASK_MULTIPLY || ((uintptr_t)mask & 3) == 0, "%s: a float mask must be 4-byte aligned", who);
+    return 0;
+}
+
+// forward products follow the policy's forward arithmetic: split-f16 under BDETR_GEMM_SPLIT (operands are LayerNorm-scale
+// projections and probabilities), split-bf16 under BDETR_GEMM_BF16X3, exact fp32 otherwise
+template <int MK, bool KO>
+void launch_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int h, int nq, int nk, float scale, MaskArg mk, hipStream_t st) {
+    dim3 grid((nq + COLS_PER_BLOCK - 1) / COLS_PER_BLOCK, h, B);
+    const int mode = attn_split_enabled() ? bdgemm::gemm_mode() : BDETR_GEMM_FP32;
+    if (mode == BDETR_GEMM_SPLIT) hipLaunchKernelGGL((attn_fwd_kernel<AR_F16, MK, KO>), grid, dim3(256), 0, st, q, k, v, o, lse, h, nq, nk, scale, mk);
+    else if (mode == BDETR_GEMM_BF16X3) hipLaunchKernelGGL((attn_fwd_kernel<AR_BF16, MK, KO>), grid, dim3(256), 0, st, q, k, v, o, lse, h, nq, nk, scale, mk);
+    else hipLaunchKernelGGL((attn_fwd_kernel<AR_FP32, MK, KO>), grid, dim3(256), 0, st, q, k, v, o, lse, h, nq, nk, scale, mk);
+}
+
+template <int MK, bool KO>
+void launch_bwd(const float* q, const float* k, const float* v, const float* o, const float* d_o, const float* lse, float* dq, float* dk, float* dv,
+                float* dvec_ws, int B, int h, int nq, int nk, float scale, MaskArg mk, hipStream_t st) {
+    const int64_t rows = (int64_t)B * h * nq;
+    hipLaunchKernelGGL(attn_dvec_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, st, o, d_o, dvec_ws, rows);
+    // gradient products: split-bf16 (fp32 range) under every policy but BDETR_GEMM_FP32, like the conv / GEMM family
+    const dim3 gq((nq + COLS_PER_BLOCK - 1) / COLS_PER_BLOCK, h, B), gk((nk + COLS_PER_BLOCK - 1) / COLS_PER_BLOCK, h, B);
+    if (!attn_split_enabled() || bdgemm::gemm_mode() == BDETR_GEMM_FP32 || bdgemm::gemm_mode() == BDETR_GEMM_BF16X6) {      // (bf16x6: the fp32-grade policy)
+        hipLaunchKernelGGL((attn_bwd_kernel<false, AR_FP32, MK, KO>), gq, dim3(256), 0, st, q, k, v, d_o, lse, dvec_ws, dq, (float*)nullptr, h, nq, nk, scale, mk);
+        hipLaunchKernelGGL((attn_bwd_kernel<true, AR_FP32, MK, KO>), gk, dim3(256), 0, st, q, k, v, d_o, lse, dvec_ws, dk, dv, h, nq, nk, scale, mk);
+    } else {
+        hipLaunchKernelGGL((attn_bwd_kernel<false, AR_BF16, MK, KO>), gq, dim3(256), 0, st, q, k, v, d_o, lse, dvec_ws, dq, (float*)nullptr, h, nq, nk, scale, mk);
+        hipLaunchKernelGGL((attn_bwd_kernel<true, AR_BF16, MK, KO>), gk, dim3(256), 0, st, q, k, v, d_o, lse, dvec_ws, dk, dv, h, nq, nk, scale, mk);
+    }
+}
+
+// x[b][hd][q][k] (contiguous [B,h,nq,nk]) against a mask with the fused kernels' broadcast strides, for the unfused attention path:
+// fill == 0: out = x * m (float mask) or (m ? x : 0) (byte mask);  fill != 0 (byte mask only): out = m ? x : BDETR_ATTN_MASK_FILL.
+template <int MK>
+__global__ __launch_bounds__(256) void attn_mask_apply_kernel(const float* __restrict__ x, float* __restrict__ out, MaskArg mk, int h, int nq, int nk,
+                                                              int64_t total, int fill) {
+    typedef typename MaskElem<MK>::type MT;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int kk = (int)(i % nk);
+    const int64_t r = i / nk;
+    const int qi = (int)(r % nq);
+    const int64_t bh = r / nq;
+    const int hd = (int)(bh % h);
+    const int64_t b = bh / h;
+    const float m = mask_value<MK>(static_cast<const MT*>(mk.p)[b * mk.sb + hd * mk.sh + qi * mk.sq + kk]);
+    const float xv = x[i];
+    if constexpr (MK == MK_U8) out[i] = m != 0.f ? xv : (fill ? BDETR_ATTN_MASK_FILL : 0.f);
+    else out[i] = xv * m;
+}
+
 }  // namespace
 
 extern "C" int bdetr_attention_head_dim(void) { return AD; }
@@ -437,13 +632,7 @@ extern "C" int bdetr_attention_fwd(const float* q, const float* k, const float* 
                                    int B, int h, int nq, int nk, float scale, void* stream) {
     if (int e = check_attn(q, k, v, B, h, nq, nk, "bdetr_attention_fwd")) return e;
     BDETR_CHECK_ARG(o && lse, "bdetr_attention_fwd: null output");
-    dim3 grid((nq + COLS_PER_BLOCK - 1) / COLS_PER_BLOCK, h, B);
-    // forward products follow the policy's forward arithmetic: split-f16 under BDETR_GEMM_SPLIT (operands are LayerNorm-scale
-    // projections and probabilities), split-bf16 under BDETR_GEMM_BF16X3, exact fp32 otherwise
-    const int mode = attn_split_enabled() ? bdgemm::gemm_mode() : BDETR_GEMM_FP32;
-    if (mode == BDETR_GEMM_SPLIT) hipLaunchKernelGGL((attn_fwd_kernel<AR_F16>), grid, dim3(256), 0, (hipStream_t)stream, q, k, v, o, lse, h, nq, nk, scale);
-    else if (mode == BDETR_GEMM_BF16X3) hipLaunchKernelGGL((attn_fwd_kernel<AR_BF16>), grid, dim3(256), 0, (hipStream_t)stream, q, k, v, o, lse, h, nq, nk, scale);
-    else hipLaunchKernelGGL((attn_fwd_kernel<AR_FP32>), grid, dim3(256), 0, (hipStream_t)stream, q, k, v, o, lse, h, nq, nk, scale);
+    launch_fwd<MK_NONE, false>(q, k, v, o, lse, B, h, nq, nk, scale, MaskArg{nullptr, 0, 0, 0}, (hipStream_t)stream);
     return bdetr_launch_status("attention_fwd");
 }
 
@@ -452,17 +641,59 @@ extern "C" int bdetr_attention_bwd(const float* q, const float* k, const float* 
                                    int B, int h, int nq, int nk, float scale, void* stream) {
     if (int e = check_attn(q, k, v, B, h, nq, nk, "bdetr_attention_bwd")) return e;
     BDETR_CHECK_ARG(o && d_o && lse && dq && dk && dv && dvec_ws, "bdetr_attention_bwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t rows = (int64_t)B * h * nq;
-    hipLaunchKernelGGL(attn_dvec_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, st, o, d_o, dvec_ws, rows);
-    // gradient products: split-bf16 (fp32 range) under every policy but BDETR_GEMM_FP32, like the conv / GEMM family
-    const dim3 gq((nq + COLS_PER_BLOCK - 1) / COLS_PER_BLOCK, h, B), gk((nk + COLS_PER_BLOCK - 1) / COLS_PER_BLOCK, h, B);
-    if (!attn_split_enabled() || bdgemm::gemm_mode() == BDETR_GEMM_FP32 || bdgemm::gemm_mode() == BDETR_GEMM_BF16X6) {      // (bf16x6: the fp32-grade policy)
-        hipLaunchKernelGGL((attn_bwd_kernel<false, AR_FP32>), gq, dim3(256), 0, st, q, k, v, d_o, lse, dvec_ws, dq, (float*)nullptr, h, nq, nk, scale);
-        hipLaunchKernelGGL((attn_bwd_kernel<true, AR_FP32>), gk, dim3(256), 0, st, q, k, v, d_o, lse, dvec_ws, dk, dv, h, nq, nk, scale);
-    } else {
-        hipLaunchKernelGGL((attn_bwd_kernel<false, AR_BF16>), gq, dim3(256), 0, st, q, k, v, d_o, lse, dvec_ws, dq, (float*)nullptr, h, nq, nk, scale);
-        hipLaunchKernelGGL((attn_bwd_kernel<true, AR_BF16>), gk, dim3(256), 0, st, q, k, v, d_o, lse, dvec_ws, dk, dv, h, nq, nk, scale);
-    }
+    launch_bwd<MK_NONE, false>(q, k, v, o, d_o, lse, dq, dk, dv, dvec_ws, B, h, nq, nk, scale, MaskArg{nullptr, 0, 0, 0}, (hipStream_t)stream);
     return bdetr_launch_status("attention_bwd");
 }
+
+extern "C" int bdetr_attention_masked_fwd(const float* q, const float* k, const float* v, float* o, float* lse,
+                                          int B, int h, int nq, int nk, float scale,
+                                          const void* mask, int64_t mask_sb, int64_t mask_sh, int64_t mask_sq, int mask_mode, void* stream) {
+    if (int e = check_attn(q, k, v, B, h, nq, nk, "bdetr_attention_masked_fwd")) return e;
+    BDETR_CHECK_ARG(o && lse, "bdetr_attention_masked_fwd: null output");
+    if (int e = check_mask(mask, mask_sb, mask_sh, mask_sq, mask_mode, B, h, nq, nk, "bdetr_attention_masked_fwd")) return e;
+    const MaskArg mk{mask, mask_sb, mask_sh, mask_sq};
+    hipStream_t st = (hipStream_t)stream;
+    const bool ko = mask_sq == 0;                                      // key-only: its own instantiations (see MK)
+    if (mask_mode == BDETR_ATTN_MASK_MULTIPLY) {
+        if (ko) launch_fwd<MK_F32, true>(q, k, v, o, lse, B, h, nq, nk, scale, mk, st); else launch_fwd<MK_F32, false>(q, k, v, o, lse, B, h, nq, nk, scale, mk, st);
+    } else {
+        if (ko) launch_fwd<MK_U8, true>(q, k, v, o, lse, B, h, nq, nk, scale, mk, st); else launch_fwd<MK_U8, false>(q, k, v, o, lse, B, h, nq, nk, scale, mk, st);
+    }
+    return bdetr_launch_status("attention_masked_fwd");
+}
+
+extern "C" int bdetr_attention_masked_bwd(const float* q, const float* k, const float* v, const float* o, const float* d_o,
+                                          const float* lse, float* dq, float* dk, float* dv, float* dvec_ws,
+                                          int B, int h, int nq, int nk, float scale,
+                                          const void* mask, int64_t mask_sb, int64_t mask_sh, int64_t mask_sq, int mask_mode, void* stream) {
+    if (int e = check_attn(q, k, v, B, h, nq, nk, "bdetr_attention_masked_bwd")) return e;
+    BDETR_CHECK_ARG(o && d_o && lse && dq && dk && dv && dvec_ws, "bdetr_attention_masked_bwd: null pointer");
+    if (int e = check_mask(mask, mask_sb, mask_sh, mask_sq, mask_mode, B, h, nq, nk, "bdetr_attention_masked_bwd")) return e;
+    const MaskArg mk{mask, mask_sb, mask_sh, mask_sq};
+    hipStream_t st = (hipStream_t)stream;
+    const bool ko = mask_sq == 0;
+    if (mask_mode == BDETR_ATTN_MASK_MULTIPLY) {
+        if (ko) launch_bwd<MK_F32, true>(q, k, v, o, d_o, lse, dq, dk, dv, dvec_ws, B, h, nq, nk, scale, mk, st);
+        else launch_bwd<MK_F32, false>(q, k, v, o, d_o, lse, dq, dk, dv, dvec_ws, B, h, nq, nk, scale, mk, st);
+    } else {
+        if (ko) launch_bwd<MK_U8, true>(q, k, v, o, d_o, lse, dq, dk, dv, dvec_ws, B, h, nq, nk, scale, mk, st);
+        else launch_bwd<MK_U8, false>(q, k, v, o, d_o, lse, dq, dk, dv, dvec_ws, B, h, nq, nk, scale, mk, st);
+    }
+    return bdetr_launch_status("attention_masked_bwd");
+}
+
+extern "C" int bdetr_attention_mask_apply(const float* x, float* out, int B, int h, int nq, int nk,
+                                          const void* mask, int64_t mask_sb, int64_t mask_sh, int64_t mask_sq, int mask_mode, int fill, void* stream) {
+    BDETR_CHECK_ARG(x && out, "bdetr_attention_mask_apply: null pointer");
+    BDETR_CHECK_ARG(B > 0 && h > 0 && nq > 0 && nk > 0, "bdetr_attention_mask_apply: bad sizes B=%d h=%d nq=%d nk=%d", B, h, nq, nk);
+    if (int e = check_mask(mask, mask_sb, mask_sh, mask_sq, mask_mode, B, h, nq, nk, "bdetr_attention_mask_apply")) return e;
+    BDETR_CHECK_ARG(!fill || mask_mode == BDETR_ATTN_MASK_EXCLUDE, "bdetr_attention_mask_apply: fill needs the exclusion rule");
+    const int64_t total = (int64_t)B * h * nq * nk;
+    BDETR_CHECK_ARG((total + 255) / 256 <= 0x7fffffff, "bdetr_attention_mask_apply: %lld elements are too many", (long long)total);
+    const MaskArg mk{mask, mask_sb, mask_sh, mask_sq};
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (mask_mode == BDETR_ATTN_MASK_MULTIPLY) hipLaunchKernelGGL((attn_mask_apply_kernel<MK_F32>), grid, dim3(256), 0, (hipStream_t)stream, x, out, mk, h, nq, nk, total, fill);
+    else hipLaunchKernelGGL((attn_mask_apply_kernel<MK_U8>), grid, dim3(256), 0, (hipStream_t)stream, x, out, mk, h, nq, nk, total, fill);
+    return bdetr_launch_status("attention_mask_apply");
+}
+

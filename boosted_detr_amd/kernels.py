@@ -827,26 +827,92 @@ def stem_bwd_weight_s2d(x4, dy_bf16, dw):
     return dw
 
 
-def attention_fwd(q, k, v, heads, scale):
-    """q [B,nq,h*32], k/v [B,nk,h*32] -> o [B,h,nq,32], lse [B,h,nq] (fused; scores never hit HBM)."""
+ATTN_MASK_MULTIPLY, ATTN_MASK_EXCLUDE = 1, 2       # BDETR_ATTN_MASK_* of include/bdetr.h
+
+
+def _attention_mask_args(mask, B, heads, nq, nk, like):
+    """An attention mask [B or 1, h or 1, nq or 1, nk] -> (tensor whose pointer goes down, batch / head / query element strides with 0
+    on a broadcast axis, rule).  float32: the multiply rule (K32); bool: exclusion (K33), handed down as uint8.  Anything else is
+    a ValueError, raised before a launch."""
+    if not isinstance(mask, torch.Tensor):
+        raise ValueError("attention mask must be a torch tensor")
+    if mask.dim() != 4:
+        raise ValueError(f"attention mask must be 4-D [B or 1, h or 1, q or 1, k], got shape {tuple(mask.shape)}")
+    if mask.dtype not in (torch.float32, torch.bool):
+        raise ValueError(f"attention mask must be float32 (multiply rule) or bool (exclusion rule), got {mask.dtype}")
+    if mask.device != like.device:
+        raise ValueError(f"attention mask lives on {mask.device}, the operands on {like.device}")
+    mb, mh, mq, mk = mask.shape
+    if mk != nk:
+        raise ValueError(f"attention mask's last axis must be the full key length {nk}, got {mk}")
+    for have, full, axis in ((mb, B, "batch"), (mh, heads, "head"), (mq, nq, "query")):
+        if have != 1 and have != full:
+            raise ValueError(f"attention mask's {axis} axis must be 1 or {full}, got {have}")
+    if not mask.is_contiguous():
+        raise ValueError("attention mask must be contiguous")
+    sb = mh * mq * mk if mb != 1 else 0
+    sh = mq * mk if mh != 1 else 0
+    sq = mk if mq != 1 else 0
+    if mask.dtype == torch.bool:
+        return mask.view(torch.uint8), sb, sh, sq, ATTN_MASK_EXCLUDE
+    return mask, sb, sh, sq, ATTN_MASK_MULTIPLY
+
+
+def attention_fwd(q, k, v, heads, scale, mask=None):
+    """q [B,nq,h*32], k/v [B,nk,h*32] -> o [B,h,nq,32], lse [B,h,nq] (fused; scores never hit HBM).
+
+    mask (optional, a constant - no gradient is ever computed for it): [B or 1, h or 1, nq or 1, nk], contiguous.
+      float32: the reference's rule, o = (softmax(scale q k^T) * mask) v with the softmax over all keys and lse that of the unmasked scores;
+      bool:    exclusion - True attends, a False key takes no part in the softmax; lse runs over the kept keys; a row with no kept
+               key gives o = 0 and lse = -inf.
+    mask=None launches exactly the unmasked kernels."""
     _chk(q, k, v)
     B, nq, D = q.shape
     nk = k.shape[1]
+    margs = None if mask is None else _attention_mask_args(mask, B, heads, nq, nk, q)
     o = empty(B, heads, nq, D // heads, like=q)
     lse = empty(B, heads, nq, like=q)
-    check(_lib.lib().bdetr_attention_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), B, heads, nq, nk, scale, _stream()), "attention_fwd")
+    if margs is None:
+        check(_lib.lib().bdetr_attention_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), B, heads, nq, nk, scale, _stream()), "attention_fwd")
+    else:
+        m, sb, sh, sq, rule = margs
+        check(_lib.lib().bdetr_attention_masked_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), B, heads, nq, nk, scale, _p(m), sb, sh, sq, rule,
+                                                    _stream()), "attention_masked_fwd")
     return o, lse
 
 
-def attention_bwd(q, k, v, o, d_o, lse, heads, scale):
+def attention_bwd(q, k, v, o, d_o, lse, heads, scale, mask=None):
+    """Gradients dq, dk, dv of attention_fwd; `mask` must be the forward's (it gets no gradient)."""
     _chk(q, k, v, o, d_o, lse)
     B, nq, D = q.shape
     nk = k.shape[1]
+    margs = None if mask is None else _attention_mask_args(mask, B, heads, nq, nk, q)
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
     ws = empty(B * heads * nq, like=q)
-    check(_lib.lib().bdetr_attention_bwd(_p(q), _p(k), _p(v), _p(o), _p(d_o), _p(lse), _p(dq), _p(dk), _p(dv), _p(ws), B, heads, nq, nk,
-                                         scale, _stream()), "attention_bwd")
+    if margs is None:
+        check(_lib.lib().bdetr_attention_bwd(_p(q), _p(k), _p(v), _p(o), _p(d_o), _p(lse), _p(dq), _p(dk), _p(dv), _p(ws), B, heads, nq, nk,
+                                             scale, _stream()), "attention_bwd")
+    else:
+        m, sb, sh, sq, rule = margs
+        check(_lib.lib().bdetr_attention_masked_bwd(_p(q), _p(k), _p(v), _p(o), _p(d_o), _p(lse), _p(dq), _p(dk), _p(dv), _p(ws), B, heads, nq, nk,
+                                                    scale, _p(m), sb, sh, sq, rule, _stream()), "attention_masked_bwd")
     return dq, dk, dv
+
+
+def attention_mask_apply(x, mask, fill=False, out=None):
+    """The mask of attention_fwd against a materialised contiguous [B,h,q,k] tensor (the unfused attention path, K34).
+    fill=False: out = x * mask (float32 mask) or out = where(mask, x, 0) (bool mask);  fill=True (bool mask only): out = where(mask, x,
+    a large finite negative), in front of softmax_rows_fwd.  out may be x."""
+    _chk(x, out)
+    B, heads, nq, nk = x.shape
+    m, sb, sh, sq, rule = _attention_mask_args(mask, B, heads, nq, nk, x)
+    if fill and rule != ATTN_MASK_EXCLUDE:
+        raise ValueError("fill applies to a bool mask only")
+    if out is None:
+        out = torch.empty_like(x)
+    check(_lib.lib().bdetr_attention_mask_apply(_p(x), _p(out), B, heads, nq, nk, _p(m), sb, sh, sq, rule, int(bool(fill)), _stream()),
+          "attention_mask_apply")
+    return out
 
 
 def softmax_rows_fwd(s2d, scale=1.0, out=None):

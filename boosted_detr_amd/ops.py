@@ -832,27 +832,42 @@ def reshape(x: torch.Tensor, shape) -> torch.Tensor:
 # ----------------------------------------------------------------------------------------
 # transformer pieces
 # ----------------------------------------------------------------------------------------
-def attention_core(Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, heads: int) -> torch.Tensor:
+def attention_core(Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, heads: int, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """softmax(Q K^T / sqrt(d)) V per head (transformers.py:86-97).  Q [B,q,h*d], K/V [B,k,h*d].
-    Returns [B,h,q,d] contiguous - the layout the reference reshapes WITHOUT permuting (line 100)."""
+    Returns [B,h,q,d] contiguous - the layout the reference reshapes WITHOUT permuting (line 100).
+
+    mask (optional): [B or 1, h or 1, q or 1, k], contiguous, on the operands' device.  float32: the reference's rule (line 94),
+    (softmax(S) * mask) V, nothing renormalised.  bool: exclusion, True attends, a False key takes no part in the softmax; a row
+    with no kept key gives zeros and zero gradients.  The mask is a constant: the backward returns gradients for Q, K and V only.
+    mask=None is the path, the kernels and the bits of a call without the keyword."""
     B, q, D = Q.shape
     kk = Kt.shape[1]
     d = D // heads
     scale = 1.0 / math.sqrt(float(d))
     if d == 32 and FUSED_ATTENTION[0]:
-        O, lse = K.attention_fwd(Q, Kt, V, heads, scale)
+        O, lse = K.attention_fwd(Q, Kt, V, heads, scale, mask=mask)
 
         def backward_fused(gO):
-            dQ, dK, dV = K.attention_bwd(Q, Kt, V, O, gO.contiguous(), lse, heads, scale)
+            dQ, dK, dV = K.attention_bwd(Q, Kt, V, O, gO.contiguous(), lse, heads, scale, mask=mask)      # (the mask: a constant, no gradient)
             return own(dQ), own(dK), own(dV)
 
         _rec([O], [Q, Kt, V], backward_fused)
         return O
+    if mask is not None:
+        K._attention_mask_args(mask, B, heads, q, kk, Q)      # a bad mask is a ValueError before the first launch
+    exclude = mask is not None and mask.dtype == torch.bool
     S = K.empty(B, heads, q, kk, like=Q)
     K.gemm_raw(q, kk, d, Q, D, True, Kt, D, True, S, kk, nb0=B, nb1=heads, sa=(q * D, d), sb=(kk * D, d), sc=(heads * q * kk, q * kk))
+    if exclude:                                   # excluded scores: a large finite negative (a row with no kept key stays finite) ...
+        K.attention_mask_apply(S, mask, fill=True, out=S)
     P = K.softmax_rows_fwd(S.view(-1, kk), scale, out=S.view(-1, kk)).view(B, heads, q, kk)   # in place; Rescaling is fused
+    PM = P                                        # what multiplies V: P, P with the excluded keys zeroed, or P * mask
+    if exclude:
+        K.attention_mask_apply(P, mask, out=P)    # ... and their probabilities are exact zeros afterwards (an empty row: all zeros)
+    elif mask is not None:
+        PM = K.attention_mask_apply(P, mask)      # the softmax backward needs the unmasked P: P * mask is a second tensor
     O = K.empty(B, heads, q, d, like=Q)
-    K.gemm_raw(q, d, kk, P, kk, True, V, D, False, O, d, nb0=B, nb1=heads, sa=(heads * q * kk, q * kk), sb=(kk * D, d), sc=(heads * q * d, q * d))
+    K.gemm_raw(q, d, kk, PM, kk, True, V, D, False, O, d, nb0=B, nb1=heads, sa=(heads * q * kk, q * kk), sb=(kk * D, d), sc=(heads * q * d, q * d))
 
     def backward(gO):
         gO = gO.contiguous()
@@ -860,9 +875,11 @@ def attention_core(Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, heads: in
         # dP[q][k] = sum_d dO[q][d] V[k][d]
         dP = K.empty(B, heads, q, kk, like=Q)
         K.gemm_raw(q, kk, d, gO, d, True, V, D, True, dP, kk, nb0=B, nb1=heads, sa=sO, sb=(kk * D, d), sc=sP, grad=True)
-        # dV[k][d] = sum_q P[q][k] dO[q][d]
+        if mask is not None:
+            K.attention_mask_apply(dP, mask, out=dP)          # multiply: dP = M * (dO V^T); exclusion: zero at the excluded keys
+        # dV[k][d] = sum_q P[q][k] dO[q][d]   (P * mask under the multiply rule)
         dV = K.empty(B, kk, D, like=Q)
-        K.gemm_raw(kk, d, q, P, kk, False, gO, d, False, dV, D, nb0=B, nb1=heads, sa=sP, sb=sO, sc=(kk * D, d), grad=True)
+        K.gemm_raw(kk, d, q, PM, kk, False, gO, d, False, dV, D, nb0=B, nb1=heads, sa=sP, sb=sO, sc=(kk * D, d), grad=True)
         dS = K.softmax_rows_bwd(P.view(-1, kk), dP.view(-1, kk), scale, out=dP.view(-1, kk)).view(B, heads, q, kk)
         # dQ[q][d] = sum_k dS[q][k] K[k][d] ;  dK[k][d] = sum_q dS[q][k] Q[q][d]
         dQ = K.empty(B, q, D, like=Q)

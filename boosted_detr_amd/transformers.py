@@ -60,18 +60,19 @@ class MultiheadAttention(Layer):
         self.OutputProjection = _Dense(self, "OutputProjection", proj_dim, query_dim, "glorot_normal")
 
     def call(self, inputs, attention_mask=None, training=False):
-        if attention_mask is not None:
-            raise NotImplementedError("the hot path always calls MultiheadAttention with attention_mask=None")
-        return self.OutputProjection(self.context(inputs))
+        """attention_mask (optional): [B or 1, h or 1, q or 1, k], contiguous.  float32: the reference's rule (transformers.py:91-94),
+        softmax(S) * attention_mask, nothing renormalised.  bool: exclusion - True attends, a False key takes no part in the softmax,
+        a query with no kept key attends to nothing (zeros before OutputProjection).  The mask is a constant and gets no gradient."""
+        return self.OutputProjection(self.context(inputs, attention_mask=attention_mask))
 
-    def context(self, inputs):
-        """Everything of the layer up to (not including) OutputProjection: the three projections, the attention core and the
-        reference's reshape without a head permute.  [B, q, h*d]."""
+    def context(self, inputs, attention_mask=None):
+        """Everything of the layer up to (not including) OutputProjection: the three projections, the attention core (with
+        ``attention_mask``, see call) and the reference's reshape without a head permute.  [B, q, h*d]."""
         query, key, value = inputs
         q, k, v = ops.dense_group([query, key, value],
                                   [self.QueryProjection.kernel, self.KeyProjection.kernel, self.ValueProjection.kernel],
                                   [self.QueryProjection.bias, self.KeyProjection.bias, self.ValueProjection.bias])
-        o = ops.attention_core(q, k, v, self.num_attention_heads)          # [B,h,q,d]
+        o = ops.attention_core(q, k, v, self.num_attention_heads, mask=attention_mask)          # [B,h,q,d]
         B, h, nq, d = o.shape
         return ops.reshape(o, (B, nq, h * d))                               # ReshapePreOutput: no permute (line 100)
 
@@ -119,10 +120,11 @@ class FeedForwardBlock(Layer):
         return ops.add_dropout_layernorm(features, y, self.ln_gamma, self.ln_beta, LN_EPS, self.dropout_rate, training)
 
 
-def attention_then(attn: AttentionBlock, ffn, inputs, training: bool):
+def attention_then(attn: AttentionBlock, ffn, inputs, training: bool, attention_mask=None):
     """AttentionBlock(inputs) followed by ``ffn`` (a FeedForwardBlock or None), exactly as the reference composes them
     (transformers.py:228-231, 348-351, 381-392) - on the fused row-chain kernels when they apply (csrc/rowchain.hip: a training step
-    under the 'split' policy at model width 256, equal dropout rates, layers already built), otherwise layer by layer."""
+    under the 'split' policy at model width 256, equal dropout rates, layers already built), otherwise layer by layer.
+    ``attention_mask`` (MultiheadAttention.call; a constant, no gradient) reaches the attention core on either route."""
     query, key, value = inputs
     fused = training and ops.rowchain_active(query.shape[-1]) and (ffn is None or ffn.dropout_rate == attn.dropout_rate)
     if fused:
@@ -137,10 +139,10 @@ def attention_then(attn: AttentionBlock, ffn, inputs, training: bool):
             attn.AttentionLayer.built = True
         fused = attn.AttentionLayer.num_attention_heads * attn.AttentionLayer.dim == query.shape[-1]
     if not fused:
-        x = attn([query, key, value], training=training)
+        x = attn([query, key, value], attention_mask=attention_mask, training=training)
         return ffn([x], training=training) if ffn is not None else x
     mha = attn.AttentionLayer
-    ctx = mha.context([query, key, value])
+    ctx = mha.context([query, key, value], attention_mask=attention_mask)
     ff = None if ffn is None else (ffn.DenseRelu.kernel, ffn.DenseRelu.bias, ffn.DenseLinear.kernel, ffn.DenseLinear.bias, ffn.ln_gamma, ffn.ln_beta)
     return ops.attention_out_chain(ctx, query, (mha.OutputProjection.kernel, mha.OutputProjection.bias), (attn.ln_gamma, attn.ln_beta), ff,
                                    LN_EPS, attn.dropout_rate, training)
@@ -162,10 +164,12 @@ class EncoderBlock(Layer):
     def build(self, input_shape):
         self.encoder_features_shape, self.encoder_positional_shape = input_shape[0], input_shape[1]
 
-    def call(self, inputs, training=False):
+    def call(self, inputs, training=False, attention_mask=None):
+        """attention_mask: the self-attention's mask [B or 1, h or 1, T or 1, T] (MultiheadAttention.call), e.g. a bool key mask
+        [B,1,1,T] that keeps a letterboxed image's padding tokens out of every softmax."""
         encoder_features, encoder_positional = inputs           # positional is [T,D] (batch-broadcast)
         qk = ops.add_bcast(encoder_features, encoder_positional)  # Add1 and Add2 compute the same tensor (224-225)
-        return attention_then(self.SelfAttentionBlock, self.FeedForwardBlock, [qk, qk, encoder_features], training)
+        return attention_then(self.SelfAttentionBlock, self.FeedForwardBlock, [qk, qk, encoder_features], training, attention_mask=attention_mask)
 
 
 def positional_init(r: int, c: int, D: int) -> np.ndarray:
@@ -199,13 +203,14 @@ class ImageEncoderAttention(Layer):
         _, r, c, D = self.encoder_features_shape
         self.positional_encoding = self.add_weight("positional_encoding", (r, c, D), value=positional_init(r, c, D))
 
-    def call(self, inputs, training=False):
+    def call(self, inputs, training=False, attention_mask=None):
+        """attention_mask: one mask [B or 1, h or 1, r*c or 1, r*c] for the self-attention of every EncoderBlock."""
         encoder_features = inputs[0]                       # [B,r,c,D]
         B, r, c, D = encoder_features.shape
         pos = self.positional_encoding            # Variable [r,c,D]; broadcast over the batch inside the add kernel
         x = ops.reshape(encoder_features, (B, r * c, D))
         for blk in self.EncoderBlocks:
-            x = blk([x, pos], training=training)
+            x = blk([x, pos], training=training, attention_mask=attention_mask)
         # the reference returns the batch-tiled positional tensor; the tile is kept implicit here
         return ops.reshape(x, (B, r, c, D)), self.positional_encoding
 
@@ -223,9 +228,11 @@ class DecoderBlock_NoSelfAttention(Layer):
         c.update({"num_attention_heads": self.num_attention_heads})
         return c
 
-    def call(self, inputs, training=False):
+    def call(self, inputs, training=False, joint_attention_mask=None):
+        """joint_attention_mask: the mask of the attention of the queries over the image tokens, [B or 1, h or 1, N or 1, T]."""
         encoder_value, decoder_features, encoder_key, decoder_positional = inputs
-        return attention_then(self.JointAttentionBlock, self.FeedForwardBlock, [decoder_features, encoder_key, encoder_value], training)
+        return attention_then(self.JointAttentionBlock, self.FeedForwardBlock, [decoder_features, encoder_key, encoder_value], training,
+                              attention_mask=joint_attention_mask)
 
 
 class DecoderBlock(Layer):
@@ -242,10 +249,14 @@ class DecoderBlock(Layer):
         c.update({"num_attention_heads": self.num_attention_heads})
         return c
 
-    def call(self, inputs, training=False):
+    def call(self, inputs, training=False, self_attention_mask=None, joint_attention_mask=None):
+        """self_attention_mask: [B or 1, h or 1, N or 1, N], among the queries; joint_attention_mask: [B or 1, h or 1, N or 1, T], queries
+        over image tokens (MultiheadAttention.call for the two rules)."""
         encoder_value, decoder_features, encoder_key, decoder_positional = inputs
-        x = attention_then(self.SelfAttentionBlock, None, [decoder_features, decoder_features, decoder_features], training)  # no positional (378-380)
-        return attention_then(self.JointAttentionBlock, self.FeedForwardBlock, [x, encoder_key, encoder_value], training)
+        x = attention_then(self.SelfAttentionBlock, None, [decoder_features, decoder_features, decoder_features], training,
+                           attention_mask=self_attention_mask)  # no positional (378-380)
+        return attention_then(self.JointAttentionBlock, self.FeedForwardBlock, [x, encoder_key, encoder_value], training,
+                              attention_mask=joint_attention_mask)
 
 
 class DecoderPrep(Layer):

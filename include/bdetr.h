@@ -1048,6 +1048,50 @@ int bdetr_mask_match_attr(const float* score, const int32_t* label, const uint64
                           int Wa, int T, int F, int A, int max_dets, int32_t* order, int32_t* class_rank, uint16_t* tp_bits,
                           uint16_t* ig_bits, int32_t* matched_gt, int32_t* gt_count, void* stream);
 
+/* ------------------------------------------------------------------------
+ * K32-K34  attention masks (csrc/attention.hip; kernels.attention_fwd / attention_bwd / ops.attention_core, mask=).  Additions to
+ *   ABI 8: nothing that existed changed; bdetr_attention_fwd / _bwd launch the kernels they launched before, bit for bit.
+ *
+ *   mask: [B or 1, h or 1, nq or 1, nk], the key axis always full and of unit stride; mask_sb / mask_sh / mask_sq are the ELEMENT
+ *   strides of the batch, head and query axes, 0 on a broadcast axis.  The mask is a constant: no gradient is computed for it.
+ *   mask_mode selects the rule and the element type:
+ *
+ * K32  BDETR_ATTN_MASK_MULTIPLY, float mask M - the reference's rule (transformers.py:91-94, softmax THEN mask):
+ *        P = softmax(scale Q K^T) over ALL keys;  O = (P * M) V;  lse = the log-sum-exp of the unmasked scaled scores.
+ *      M holds any floats (0, negative, above 1); nothing is renormalised.  Backward, with D = rowdot(dO, O):
+ *        dP = M * (dO V^T);  dS = P * (dP - D) * scale;  dV = (P * M)^T dO;  dQ = dS K;  dK = dS^T Q.
+ *      (dS keeps its unmasked form because sum_k P_k M_k (dO . V_k) = dO . O.)
+ *
+ * K33  BDETR_ATTN_MASK_EXCLUDE, uint8 mask - this project's own rule, not the reference's: a key whose byte is 0 is excluded, any
+ *      other value attends.  An excluded key takes no part in the softmax (its score is -inf); lse runs over the kept keys; the
+ *      backward is the ordinary one over the kept keys.  A row with no kept key gives O = 0, lse = -inf and contributes nothing to
+ *      dQ, dK, dV.  No NaN appears in any of these cases.
+ *
+ *   bdetr_attention_masked_fwd / _bwd: the operands of bdetr_attention_fwd / _bwd, then the mask.  Returns -1 before any launch
+ *   (bdetr_last_error says why) on a null mask, an unknown mode, a negative stride, a float mask that is not 4-byte aligned, or
+ *   when (B-1) sb + (h-1) sh + (nq-1) sq + nk does not fit the address arithmetic (the whole sum an int64 byte offset, one
+ *   (image, head) plane (nq-1) sq + nk at most 2^31 - 1 elements).  No atomics: two calls give the same bits.  An all-ones float
+ *   mask and an all-nonzero byte mask give the bits of the unmasked entry points.  A key-only mask (mask_sq == 0) runs its own
+ *   instantiations, which keep the unmasked kernels' occupancy.
+ *
+ * K34  bdetr_attention_mask_apply: the same mask against a materialised contiguous [B,h,nq,nk] tensor, for the unfused attention path
+ *      (head dimension other than 32).  fill == 0: out = x * M (float mask) or out = m ? x : 0 (byte mask).  fill != 0 (byte mask
+ *      only): out = m ? x : BDETR_ATTN_MASK_FILL, a large finite negative put in front of bdetr_softmax_rows_fwd - a row with no
+ *      kept key then has a finite (uniform) softmax, which the fill == 0 form zeroes afterwards.  out may be x.
+ * ---------------------------------------------------------------------- */
+#define BDETR_ATTN_MASK_MULTIPLY 1
+#define BDETR_ATTN_MASK_EXCLUDE 2
+#define BDETR_ATTN_MASK_FILL (-1.0e30f)
+int bdetr_attention_masked_fwd(const float* q, const float* k, const float* v, float* o, float* lse,
+                               int B, int h, int nq, int nk, float scale,
+                               const void* mask, int64_t mask_sb, int64_t mask_sh, int64_t mask_sq, int mask_mode, void* stream);
+int bdetr_attention_masked_bwd(const float* q, const float* k, const float* v, const float* o, const float* d_o,
+                               const float* lse, float* dq, float* dk, float* dv, float* dvec_ws,
+                               int B, int h, int nq, int nk, float scale,
+                               const void* mask, int64_t mask_sb, int64_t mask_sh, int64_t mask_sq, int mask_mode, void* stream);
+int bdetr_attention_mask_apply(const float* x, float* out, int B, int h, int nq, int nk,
+                               const void* mask, int64_t mask_sb, int64_t mask_sh, int64_t mask_sq, int mask_mode, int fill, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
