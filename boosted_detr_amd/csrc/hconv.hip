@@ -11,8 +11,13 @@
 // Zero padding cannot come from the loader any more (the halo holds the neighbouring image row / image where the convolution
 // wants zeros), so a fragment whose (row, tap) falls outside the image is zeroed in registers from a 9-bit mask per row.
 //
-// Schedule: the 8-wave ping-pong of sgemm.hip's PP loop (waves w and w + 4 share a SIMD; one half multiplies from registers
-// while the other reads its fragments and issues its share of the loads), K order = channel chunk outer, tap inner.
+// Schedule: an 8-wave ping-pong.  A workgroup's waves are dealt to the four SIMDs cyclically, so waves w and w + 4 share a
+// SIMD; waves 0-3 (group X) own the upper half of the tile's rows, waves 4-7 (group Y) the lower half, the weight tile is
+// shared.  One group multiplies a K-step from fragments already in registers while the other reads its fragments and issues
+// its share of the loads, then they swap: a wave's MFMA segment contains nothing but MFMAs and its load segment runs in the
+// shadow of its SIMD partner's MFMAs, instead of both partners stalling on the address unit at the same time.  K order =
+// channel chunk outer, tap inner.  The main loop's comment argues why no ring buffer is overwritten while it is still read
+// and why every stage has landed before its first reader.
 //
 // Replaces: Keras Conv2D (3x3, padding 'same') and its input gradient inside tf.keras.applications ResNet-50 / -101
 // (reference backbone.py:37-38, 57).
@@ -216,11 +221,15 @@ void hconv_kernel(HInput xa, HWeight wb, GemmParams g)
     // while Y multiplies, X is in L(t + 1).  A wave's MFMA segment holds nothing but MFMAs, and its load segment (LDS reads,
     // LDS-DMA issue, address arithmetic) runs in the shadow of its partner's MFMAs.  Slots (barrier-delimited): X runs L(t) in
     // slot 2t and M(t) in slot 2t + 1, Y runs L(t) in slot 2t + 1 and M(t) in slot 2t + 2.
-    // What L(t) issues (NLOAD = NIB + 1 loads per wave, a compile-time constant):
+    // What L(t) issues (NLOAD = NIB + 1 loads per wave, a compile-time constant; every wave issues every stage exactly once, in
+    // order, so the counted waits below mean the same thing in every wave):
     //   * its share of the WEIGHT stage of step t + 2 into ring buffer (t + 2) % 3 = (ts + 2) % 3, whose previous tenant (step
     //     t - 1) was last read in Y's L(t - 1), slot 2t - 1 - before the first issue (X, slot 2t);
     //   * piece phi (< 8) of the HALO of chunk + 1 into halo buffer (chunk + 1) & 1, whose previous tenant (chunk - 1) was last
     //     read in Y's L(9 chunk - 1); phi = 8 issues a load that only keeps the count uniform (source out of range, into a sink).
+    // Ring safety is these two "last read ... before the first issue" statements: a barrier separates every last read of a
+    // buffer from the first LDS-DMA issue into it.  The weight ring's third stage buys time in flight, not safety: with
+    // two, Y's share of step t + 1, issued in slot 2t + 1, would have to land within that slot - before X's L(t + 1) in 2t + 2.
     // Landing: both segments end with s_waitcnt vmcnt(NLOAD), which leaves only the wave's newest group in flight.  The weight
     // stage of step s (issued in L(s - 2)) is therefore complete in every wave by the end of slot 2s - 2 (X: end of L(s - 1);
     // Y: end of M(s - 2) ... L(s - 1)) - one barrier before its first reader, X's L(s) in slot 2s; likewise the last halo pieces

@@ -306,14 +306,10 @@ __device__ __forceinline__ void atomic_epilogue(f32x16 (&acc)[BM / WM / 32][BN /
         }
 }
 
-// NS = LDS stages: the loads of K-step t + NS - 1 are issued while K-step t computes and a counted s_waitcnt
-// vmcnt leaves the younger stages in flight across the (raw) barrier.
+// NS = LDS stages: the loads of K-step t + NS - 1 are issued while K-step t computes.  Every instantiation has two (the main
+// loops are written for that); the number stays a parameter because it is part of the profiling tuple (launch_cfg).
 constexpr int default_occ(int bm, int bn, int wm, int wn, int ns) { return (wm * wn == 4 && 2 * lds_bytes_for(bm, bn, ns) <= 160 * 1024) ? 2 : (wm * wn == 8 ? 2 : 1); }
 
-// PP ("ping-pong", 8 waves, three-stage ring): the two waves of a SIMD alternate roles in lock step - while waves 0-3 multiply
-// K-step t from fragments already in registers, waves 4-7 read their fragments and issue their share of the LDS-DMA loads, then
-// the halves swap (see the main loop).  A wave's MFMA segment contains nothing but MFMAs and its load segment runs in the shadow
-// of its SIMD partner's MFMAs, instead of both partners stalling on the address unit at the same time.
 // EPI (dense 1x1 kernels): EPI_PLAIN = persistent, register epilogue with bias / activation / statistics and plain stores only;
 // EPI_ROWMAP = persistent, plus the strided scatter (with or without accumulate) of the stride-2 backward-data launches;
 // EPI_VEC = NOT persistent, LDS-transposed float4 epilogue (gemm_epilogue) with its accumulate / masked accumulate / fused
@@ -321,7 +317,7 @@ constexpr int default_occ(int bm, int bn, int wm, int wn, int ns) { return (wm *
 // over the tile loop and spilled (50 VGPRs, a scratch round trip per tile: 0.19 ms against 0.12 on the 64 -> 256 channel layer at
 // 160x160), and the register epilogue's accumulate / sums - one dword per lane, up to 3 x 64 loads per lane and tile - ran at a
 // third of their HBM floor (tools/dgrad_epi_probe.py).
-template <int BM, int BN, int WM, int WN, int NS, class LA, class LB, bool XX, bool F16, bool PP = false, int OCC = default_occ(BM, BN, WM, WN, NS), int EPI = EPI_ROWMAP>
+template <int BM, int BN, int WM, int WN, int NS, class LA, class LB, bool XX, bool F16, int OCC = default_occ(BM, BN, WM, WN, NS), int EPI = EPI_ROWMAP>
 __global__ __launch_bounds__(WM * WN * 64, OCC)
 void sgemm_kernel(typename LA::Op opa, typename LB::Op opb, GemmParams g)
 {
@@ -353,8 +349,8 @@ void sgemm_kernel(typename LA::Op opa, typename LB::Op opb, GemmParams g)
     // MFMA-bound, measured equal or slower when persistent, and the f16 128x128 one does not fit its accumulators plus
     // the loop-carried state in 256 VGPRs) and the XX kernels (split-K weight gradients) run one virtual block per
     // workgroup.
-    constexpr bool PERSIST = !PP && !XX && std::is_same_v<LA, RRDense> && (EPI & EPI_VEC) == 0;
-    static_assert(PP ? (NS == 3 && NW == 8) : NS == 2, "the plain loops are written for a two-stage ring, the ping-pong loop for three stages and 8 waves");
+    constexpr bool PERSIST = !XX && std::is_same_v<LA, RRDense> && (EPI & EPI_VEC) == 0;
+    static_assert(NS == 2, "the loops are written for a two-stage ring");
     const int nwg = g.tiles_i * g.tiles_j;
     const int total = PERSIST ? nwg : nwg * (int)gridDim.z;
     int vb = PERSIST ? (int)blockIdx.x : (int)(blockIdx.z * nwg + blockIdx.x);
@@ -587,90 +583,7 @@ void sgemm_kernel(typename LA::Op opa, typename LB::Op opb, GemmParams g)
     };
 
     // ---------------- main loop ----------------
-    if constexpr (PP) {
-        // Ping-pong over a three-stage ring.  Group X = waves 0-3, group Y = waves 4-7: wave w and wave w + 4 share a SIMD (a
-        // workgroup's waves are dealt to the SIMDs cyclically), X owns the upper half of the tile's rows, Y the lower half, the B
-        // tile is shared.  K-step t is two half-steps, each closed by ONE workgroup barrier:
-        //   A(t): X multiplies step t (24 MFMAs, fragments already in registers) | Y reads its fragments of stage t and issues its
-        //         share of stage t + 2's loads
-        //   B(t): Y multiplies step t                                            | X reads its fragments of stage t + 1 and issues
-        //         its share of stage t + 2's loads
-        // Ring safety: stage t + 2 overwrites the buffer of stage t - 1, last read in A(t - 1) (by Y), one barrier before the first
-        // issue.  Landing: X's share of stage s is issued in B(s - 2) and waited for (vmcnt(0)) at the end of A(s - 1); Y's share is
-        // issued in A(s - 2) and waited for by the counted vmcnt(NLOAD) at the end of A(s - 1), which leaves Y's newest stage in
-        // flight; the barrier that closes A(s - 1) precedes the first read of stage s (X in B(s - 1)).  Every wave issues every
-        // stage exactly once, in order (the loaders' per-stage state advances once per issue_all).
-        constexpr int NLOAD_ = NIA + NIB;
-        const int nk = (r_end - r_begin + BK - 1) / BK;
-        float bias_pre[TN];
-        gemm_load_bias<BM, BN, WM, WN>(g, j0, bias_pre);              // (older than every stage load: retired by the first counted wait)
-        const bool grpY = wave >= NW / 2;                              // wave-uniform (readfirstlane above): scalar branches
-        u32x4 fah[2][TM], fal[2][TM], fbh[2][TN], fbl[2][TN];
-        auto read_all = [&](auto buf_c) {
-            constexpr int buf = decltype(buf_c)::value;
-            load_frags(buf, std::integral_constant<int, 0>{}, fah[0], fal[0], fbh[0], fbl[0]);
-            load_frags(buf, std::integral_constant<int, 1>{}, fah[1], fal[1], fbh[1], fbl[1]);
-            frag_wait(fah[0], fal[0], fbh[0], fbl[0]);
-            frag_wait(fah[1], fal[1], fbh[1], fbl[1]);
-            if constexpr (XX && !F16) {
-                if (g.b_f16) {                           // (weight gradients reading the forward's f16 pair of x: converted here, in the shadow of the partner group's MFMAs)
-#pragma unroll
-                    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                        for (int b = 0; b < TN; ++b) f16pair_to_bf16pair(fbh[ks][b], fbl[ks][b]);
-                }
-            }
-        };
-        auto mfma_step = [&]() {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) mfma_ks(fah[ks], fal[ks], fbh[ks], fbl[ks]);
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        if (nk > 0) issue_all(0, r_begin);
-        if (nk > 1) issue_all(1, r_begin + BK);
-        if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(NLOAD_) : "memory");
-        else        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        if (!grpY) read_all(std::integral_constant<int, 0>{});
-        auto step = [&](int t, auto b0_c, auto b1_c, auto b2_c) {
-            constexpr int b2 = decltype(b2_c)::value;
-            // ---- A(t)
-            if (!grpY) {
-                mfma_step();
-                asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-            } else {
-                read_all(b0_c);
-                if (t + 2 < nk) {
-                    issue_all(b2, r_begin + (t + 2) * BK);
-                    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(NLOAD_) : "memory");
-                } else {
-                    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-                }
-            }
-            // ---- B(t)
-            if (grpY) {
-                mfma_step();
-            } else {
-                if (t + 1 < nk) read_all(b1_c);
-                if (t + 2 < nk) issue_all(b2, r_begin + (t + 2) * BK);
-            }
-            asm volatile("s_barrier" ::: "memory");
-        };
-        using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-        for (int t = 0; t < nk; t += 3) {                 // unrolled by the ring depth: LDS addresses are lane bases + immediates
-            step(t, I0{}, I1{}, I2{});
-            if (t + 1 < nk) step(t + 1, I1{}, I2{}, I0{});
-            if (t + 2 < nk) step(t + 2, I2{}, I0{}, I1{});
-        }
-        if (XX && g.mode == ST_ATOMIC && g.bias == nullptr && g.act == BDETR_ACT_NONE && g.stat_sum == nullptr && !g.rowmap && g.ldc * 4 * BM < (1ll << 31)) {
-            atomic_epilogue<BM, BN, WM, WN>(acc, g, i0, j0);
-            return;
-        }
-        gemm_epilogue<BM, BN, WM, WN, NT, LDS_BYTES / 4>(acc, g, reinterpret_cast<float*>(lds), tile_i, i0, j0, g.c + (g.splitk > 1 ? (int64_t)zz * g.sc0 : 0), bias_pre);
-    } else if constexpr (PERSIST) {
+    if constexpr (PERSIST) {
         // Two-stage ring, persistent over tiles.  Per K-step: wait for everything this wave has in flight (stage kt, and
         // on a tile's first step the previous tile's C stores - on gfx9 stores count in vmcnt and return out of order with
         // loads, so a counted wait cannot tell them apart), barrier (every wave's share of stage kt has landed and every
@@ -775,21 +688,18 @@ void sgemm_kernel(typename LA::Op opa, typename LB::Op opb, GemmParams g)
 // (13.1 ms: equal on the 40x40 3x3 layers, slower on the others).  More bytes in flight or more resident
 // workgroups do not help: at 27 B/clk/CU the staging already runs near the L2 -> LDS fill rate the guide measured for
 // LDS-DMA gathers (66-73 GB/s per CU), which is what a bigger FLOP-per-staged-byte ratio would have to relieve.
-enum { T_128x128 = 0, T_128x64 = 1, T_64x64 = 2, T_PP256x128 = 3, T_PP256x64 = 4, T_COUNT = 5 };
-const int TILE_BM[T_COUNT] = {128, 128, 64, 256, 256};
-const int TILE_BN[T_COUNT] = {128, 64, 64, 128, 64};
-const int TILE_WM[T_COUNT] = {2, 2, 2, 4, 4};
-constexpr int DENSE128_WM = 2;                                   // wave rows of the 128x128 tile in the persistent dense (1x1) kernels
-int tile_wm(int tile, bool dense) { return (dense && tile == T_128x128) ? DENSE128_WM : TILE_WM[tile]; }
+enum { T_128x128 = 0, T_128x64 = 1, T_64x64 = 2, T_COUNT = 3 };
+const int TILE_BM[T_COUNT] = {128, 128, 64};
+const int TILE_BN[T_COUNT] = {128, 64, 64};
+const int TILE_WM[T_COUNT] = {2, 2, 2};
 
 int forced_tile() {
     static int forced = -2;
     if (forced == -2) {
         forced = -1;
         if (const char* e = getenv("BDETR_STILE")) {
-            const char* names[T_COUNT] = {"128x128", "128x64", "64x64", "pp256x128", "pp256x64"};
+            const char* names[T_COUNT] = {"128x128", "128x64", "64x64"};
             for (int t = 0; t < T_COUNT; ++t) if (!strcmp(e, names[t])) forced = t;
-            if (!strcmp(e, "pp")) forced = T_PP256x128;
         }
     }
     return forced;
@@ -797,15 +707,8 @@ int forced_tile() {
 
 // Bigger tiles stage fewer bytes per FLOP (128x128: 32 FLOP per staged byte, 64x64: 16) but need enough
 // workgroups to fill 256 CUs x 2 resident workgroups.
-// patch = the A operand is an im2col view (3x3 forward / backward-data): the ping-pong tiles exist for those kernels only
-// (pp_ok: bf16 launches only - the f16 flavour's two accumulator sets leave no room for a whole K-step of fragments)
-int choose_tile(int64_t I, int64_t J, int64_t z, bool pp_ok = false) {
-    int forced = forced_tile();
-    if (forced >= T_PP256x128) {
-        const bool patch = pp_ok;
-        if (!patch) forced = -1;                                       // dense / weight-gradient / f16 launches keep their own rule
-        else return J % 128 == 0 ? T_PP256x128 : (J % 64 == 0 ? T_PP256x64 : T_128x64);
-    }
+int choose_tile(int64_t I, int64_t J, int64_t z) {
+    const int forced = forced_tile();
     if (forced >= 0) return (J < 64 || (TILE_BN[forced] == 128 && J < 128)) ? T_64x64 : forced;
     const int64_t cus = num_cus();
     auto tiles = [&](int bm, int bn) { return cdiv64(I, bm) * cdiv64(J, bn) * z; };
@@ -814,7 +717,7 @@ int choose_tile(int64_t I, int64_t J, int64_t z, bool pp_ok = false) {
     return T_64x64;
 }
 
-template <int BM, int BN, int WM, int WN, int NS, class LA, class LB, bool XX, bool F16, bool PP = false, int OCC = default_occ(BM, BN, WM, WN, NS)>
+template <int BM, int BN, int WM, int WN, int NS, class LA, class LB, bool XX, bool F16, int OCC = default_occ(BM, BN, WM, WN, NS)>
 int launch_cfg(const typename LA::Op& a, const typename LB::Op& b, GemmParams g, int zdim, hipStream_t st, int kind) {
     g.tiles_i = (int)cdiv64(g.I, BM);
     g.tiles_j = (int)cdiv64(g.J, BN);
@@ -829,9 +732,9 @@ int launch_cfg(const typename LA::Op& a, const typename LB::Op& b, GemmParams g,
     const bool prof = g_prof_on;
     if (prof) prof_begin(st, 2.0 * (double)g.I * (double)g.J * (double)g.R, g.I, g.J, g.R, zdim, BM, BN * 10 + NS,
                          (F16 ? AR_P16_F16 : AR_P16_BF16) * 10000 + kind);
-    if constexpr (!PP && !XX && std::is_same_v<LA, RRDense>) {
+    if constexpr (!XX && std::is_same_v<LA, RRDense>) {
         auto go = [&](auto epi_c) {
-            hipLaunchKernelGGL((sgemm_kernel<BM, BN, WM, WN, NS, LA, LB, XX, F16, PP, OCC, decltype(epi_c)::value>), grid, dim3(WM * WN * 64), 0, st, a, b, g);
+            hipLaunchKernelGGL((sgemm_kernel<BM, BN, WM, WN, NS, LA, LB, XX, F16, OCC, decltype(epi_c)::value>), grid, dim3(WM * WN * 64), 0, st, a, b, g);
             if (prof) prof_end(st);
             return bdetr_launch_status("sgemm");
         };
@@ -856,7 +759,7 @@ int launch_cfg(const typename LA::Op& a, const typename LB::Op& b, GemmParams g,
         static int resident = 0;
         if (resident == 0) {
             int occ = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, sgemm_kernel<BM, BN, WM, WN, NS, LA, LB, XX, F16, PP, OCC, EPI_ROWMAP>, WM * WN * 64, 0) != hipSuccess || occ < 1) occ = 1;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, sgemm_kernel<BM, BN, WM, WN, NS, LA, LB, XX, F16, OCC, EPI_ROWMAP>, WM * WN * 64, 0) != hipSuccess || occ < 1) occ = 1;
             resident = occ * num_cus() / 8 * 8;
             if (resident < 8) resident = 8;
         }
@@ -864,7 +767,7 @@ int launch_cfg(const typename LA::Op& a, const typename LB::Op& b, GemmParams g,
         if (!g.rowmap) return go(std::integral_constant<int, EPI_PLAIN>{});
         return go(std::integral_constant<int, EPI_ROWMAP>{});
     }
-    hipLaunchKernelGGL((sgemm_kernel<BM, BN, WM, WN, NS, LA, LB, XX, F16, PP, OCC>), grid, dim3(WM * WN * 64), 0, st, a, b, g);
+    hipLaunchKernelGGL((sgemm_kernel<BM, BN, WM, WN, NS, LA, LB, XX, F16, OCC>), grid, dim3(WM * WN * 64), 0, st, a, b, g);
     if (prof) prof_end(st);
     return bdetr_launch_status("sgemm");
 }
@@ -872,21 +775,8 @@ int launch_cfg(const typename LA::Op& a, const typename LB::Op& b, GemmParams g,
 template <class LA, class LB, bool XX, bool F16>
 int launch_any(const typename LA::Op& a, const typename LB::Op& b, const GemmParams& g, int zdim, hipStream_t st, int kind, int tile) {
     switch (tile) {
-        case T_128x128:
-            // (DENSE128_WM = 4: the persistent dense kernels on EIGHT waves - wave tile 32x64, 4 waves per SIMD at two workgroups per
-            // CU, 127 VGPRs without spills in the plain-epilogue flavour.  Measured equal or slower than four waves on every 1x1
-            // layer and 1.3 % slower on the step, round 3; kept as a switch.)
-            if constexpr (!XX && std::is_same_v<LA, RRDense> && DENSE128_WM == 4) return launch_cfg<128, 128, 4, 2, 2, LA, LB, XX, F16, false, 4>(a, b, g, zdim, st, kind);
-            else return launch_cfg<128, 128, 2, 2, 2, LA, LB, XX, F16>(a, b, g, zdim, st, kind);
+        case T_128x128:    return launch_cfg<128, 128, 2, 2, 2, LA, LB, XX, F16>(a, b, g, zdim, st, kind);
         case T_128x64:     return launch_cfg<128, 64, 2, 2, 2, LA, LB, XX, F16>(a, b, g, zdim, st, kind);
-        case T_PP256x128:
-            // (the f16 flavour keeps two accumulator sets: with the fragments of a whole K-step resident it does not fit 256 VGPRs)
-            // (round 4 also ran the weight gradients on the ping-pong loop - BDETR_WGRAD_PP: slower on every layer, removed in round 5)
-            if constexpr (std::is_same_v<LA, RRPatch> && !F16) return launch_cfg<256, 128, 4, 2, 3, LA, LB, XX, F16, true>(a, b, g, zdim, st, kind);
-            else return launch_cfg<128, 128, 2, 2, 2, LA, LB, XX, F16>(a, b, g, zdim, st, kind);
-        case T_PP256x64:
-            if constexpr (std::is_same_v<LA, RRPatch> && !F16) return launch_cfg<256, 64, 4, 2, 3, LA, LB, XX, F16, true>(a, b, g, zdim, st, kind);
-            else return launch_cfg<128, 64, 2, 2, 2, LA, LB, XX, F16>(a, b, g, zdim, st, kind);
         default:           return launch_cfg<64, 64, 2, 2, 2, LA, LB, XX, F16>(a, b, g, zdim, st, kind);
     }
 }
@@ -947,7 +837,7 @@ extern "C" int bdetr_p16_supported(const bdetr_conv_desc* d) {
     return 1;
 }
 
-static int fwd_tile(const bdetr_conv_desc* d) { return choose_tile((int64_t)d->N * d->OH * d->OW, d->K, 1, false); }
+static int fwd_tile(const bdetr_conv_desc* d) { return choose_tile((int64_t)d->N * d->OH * d->OW, d->K, 1); }
 
 // 3x3 / stride 1 / pad 1: the halo-resident kernel of hconv.hip (its tile as BM * 1000 + BN), else 0
 static int fwd_hconv(const bdetr_conv_desc* d) {
@@ -959,7 +849,7 @@ extern "C" int bdetr_p16_conv2d_fwd_stat_chunks(const bdetr_conv_desc* d) {
     if (check_conv(d, "bdetr_p16_conv2d_fwd_stat_chunks")) return -1;
     if (const int ht = fwd_hconv(d)) return (int)cdiv64((int64_t)d->N * d->OH * d->OW, ht / 1000) * 4;      // tiles_i * WM (4 wave rows)
     const int t = fwd_tile(d);
-    return (int)cdiv64((int64_t)d->N * d->OH * d->OW, TILE_BM[t]) * tile_wm(t, is_1x1_dense(d));          // tiles_i * WM
+    return (int)cdiv64((int64_t)d->N * d->OH * d->OW, TILE_BM[t]) * TILE_WM[t];          // tiles_i * WM
 }
 
 extern "C" int bdetr_p16_conv2d_fwd(const void* x_f16, const void* w_f16, const float* bias, float* y,
@@ -987,7 +877,7 @@ extern "C" int bdetr_p16_conv2d_fwd(const void* x_f16, const void* w_f16, const 
 
 static int bwd_data_tile(const bdetr_conv_desc* d) {
     const bool dense = d->R == 1 && d->S == 1 && d->pad == 0;
-    return choose_tile(dense ? (int64_t)d->N * d->OH * d->OW : (int64_t)d->N * d->H * d->W, d->C, 1, !dense);
+    return choose_tile(dense ? (int64_t)d->N * d->OH * d->OW : (int64_t)d->N * d->H * d->W, d->C, 1);
 }
 
 // 1x1 stride-1 backward-data with accumulate / fused sums (EPI_VEC: one workgroup per tile, float4 epilogue with up to three tile-sized
@@ -1108,14 +998,8 @@ static int wgrad_tile(const bdetr_conv_desc* d) {
     return T_128x128;
 }
 
-static bool is_3x3_same(const bdetr_conv_desc* d) { return d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1; }
-
 extern "C" int bdetr_p16_conv2d_bwd_weight_splitk(const bdetr_conv_desc* d) {
     if (check_conv(d, "bdetr_p16_conv2d_bwd_weight_splitk")) return -1;
-    if (is_3x3_same(d)) {                                 // the halo-resident kernel (hwgrad.hip) slices the pixel range itself
-        const int hs = hwgrad_slices(d->N, d->H, d->W, d->C, d->K);
-        if (hs > 0) return hs > 1 ? hs : 2;               // (> 1: the slices add with atomics, the caller must hand over zeros / a running sum)
-    }
     const int M = d->N * d->OH * d->OW;
     const int64_t Kd = (int64_t)d->R * d->S * d->C;
     const int t = wgrad_tile(d);
@@ -1153,14 +1037,6 @@ static int p16_bwd_weight(const void* x_bf16, int x_is_f16, const void* dy_bf16,
     hipStream_t st = (hipStream_t)stream;
     const int M = d->N * d->OH * d->OW, Kd = d->R * d->S * d->C;
     if (splitk <= 0) splitk = bdetr_p16_conv2d_bwd_weight_splitk(d);
-    if (!x_is_f16 && is_3x3_same(d) && hwgrad_slices(d->N, d->H, d->W, d->C, d->K) > 0) {
-        // both operands as bf16 pairs, 3x3 'same': dy and x stream through LDS once for all nine taps (hwgrad.hip)
-        const int64_t n = (int64_t)d->K * Kd, slab = splitk_slab(n);
-        if (ws != nullptr) BDETR_CHECK_ARG(aligned16(ws) && ws_elems >= (int64_t)splitk * slab, "bdetr_p16_conv2d_bwd_weight_ws: workspace too small or misaligned");
-        int zdim = 1;
-        if (int e = hwgrad_launch(x_bf16, dy_bf16, dw, d->N, d->H, d->W, d->C, d->K, splitk, ws, slab, &zdim, st)) return e;
-        return ws != nullptr ? splitk_fold(ws, zdim, slab, dw, n, st) : 0;
-    }
     GemmParams g; init_params(g);
     g.b_f16 = x_is_f16;
     g.I = d->K; g.J = Kd; g.R = M;

@@ -78,28 +78,8 @@ def _p16_rows(pred):
     return [s for s in P16_CONVS if pred(s)]
 
 
-def pp_cases():
-    return [("p16", s, "") for s in _p16_rows(lambda s: s[5] == 3) + [(2, 13, 9, 64, 224, 3, 1, 1)]]
-
-
 def wgrad_cases():
     return [("p16", s, "") for s in _p16_rows(lambda s: s[5] == 1)]
-
-
-HWGRAD_SHAPES = [(4, 40, 40, 256, 256), (16, 20, 20, 512, 512), (8, 80, 80, 128, 128), (2, 14, 14, 256, 256),          # the four the older test reruns
-                 (3, 9, 11, 128, 64), (5, 3, 3, 64, 64), (2, 13, 37, 32, 64),                                          # K = 64 / C = 32: must stay on im2col
-                 (3, 9, 11, 64, 128), (5, 3, 3, 64, 128), (3, 5, 13, 64, 128),                                         # frame rows under 16 pixels: refused too
-                 (2, 13, 37, 64, 128), (3, 5, 14, 64, 128), (1, 17, 15, 128, 128)]                                     # odd maps the kernel admits (W + 2 = 16 the narrowest)
-
-
-def hwgrad_admits(N, H, W, C, K):
-    # csrc/hwgrad.hip: BKO x BCI blocks; MAX_XL; and a padded frame row of at least 16 pixels - the window advances 32 pixels a
-    # stage and wraps at most two frame rows (W = 11 and W = 3 came out wrong before hwgrad_slices() refused them)
-    return K % 128 == 0 and C % 64 == 0 and 14 <= W <= 93
-
-
-def hwgrad_cases():
-    return [("p16", s + (3, 1, 1), "") for s in HWGRAD_SHAPES]
 
 
 TILE_LINEARS = [(300, 256, 256), (130, 52, 48), (1600, 1024, 82)]                                  # the ragged rows of test_precision_gpu.LINEARS / CONVS
@@ -117,8 +97,7 @@ def case_list(name):
         return hconv_cases(arg)
     if head == "stile":
         return stile_cases(arg)
-    return {"pp": pp_cases, "wgrad": wgrad_cases, "hwgrad": hwgrad_cases, "tile": tile_cases,
-            "attn": lambda: [("attn", s, "") for s in ATTN_SHAPES]}[head]()
+    return {"wgrad": wgrad_cases, "tile": tile_cases, "attn": lambda: [("attn", s, "") for s in ATTN_SHAPES]}[head]()
 
 
 # ---------------------------------------------------------------------------------------------- the child itself

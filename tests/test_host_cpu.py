@@ -552,7 +552,7 @@ def test_every_kernel_switch_is_forced_by_some_test():
     for path in glob.glob(os.path.join(ROOT, "boosted_detr_amd", "csrc", "*.hip")):
         with open(path) as f:
             names |= set(re.findall(r'getenv\("(BDETR_[A-Z0-9_]+)"\)', f.read()))
-    assert len(names) >= 15, sorted(names)                       # the scan itself still finds the switches
+    assert len(names) >= 13, sorted(names)                      # the scan itself still finds the switches
     tests = ""
     for path in glob.glob(os.path.join(ROOT, "tests", "*.py")):
         if os.path.basename(path) != "test_host_cpu.py":

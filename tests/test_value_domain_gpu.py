@@ -6,8 +6,6 @@ channels / rows, saturated logits, attention scores up to 80 with the dominant k
 in u = 2^-24 stated next to each case; every test prints its worst measured `error / model` ratio (DESIGN.md "Value domain"
 records them).  Shapes are the smallest that reach every code path named."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -134,18 +132,15 @@ def test_bn_colstats_statistics_apply_and_backward(cuda, rows):
 
 
 # R of the hand-made partials: 31 additions inside a 32-row partial.  nparts = 300 > 4 x 64 takes fold_partials2_kernel, whose 8-phase
-# fp32 sum adds 7 more; bn_finalize_kernel then folds the 64 rows in fp64.  With BDETR_BN_WIDE_REDUCE=1 reduce_partials2_kernel<true>
-# folds all 300 in fp64: R = 31.
-def r_hand_made():
-    return 31 if os.environ.get("BDETR_BN_WIDE_REDUCE") == "1" else 31 + 7
+# fp32 sum adds 7 more; bn_finalize_kernel then folds the 64 rows in fp64.
+R_HAND_MADE = 31 + 7
 
 
 @pytest.mark.parametrize("start", [0, 5])
 def test_bn_stats_from_hand_made_partials(cuda, start):
-    """(b) 300 fp32 partials of 32 rows (rows 9600, C 8: the regimes at two rotations) through fold_partials2 + bn_finalize;
-    (c) runs this test again under BDETR_BN_WIDE_REDUCE=1.
-    measured on MI355X, 2026-10-21: max |dvar| / (u (m^2 + s^2)) 0.22 (rotation 0) / 0.75 (rotation 5), bound 40; the one-launch
-    reduction gives the same 0.22 / 0.75 (bound 33): the 32-row partials carry the error, not the fold."""
+    """(b) 300 fp32 partials of 32 rows (rows 9600, C 8: the regimes at two rotations) through fold_partials2 + bn_finalize.
+    measured on MI355X, 2026-10-21: max |dvar| / (u (m^2 + s^2)) 0.22 (rotation 0) / 0.75 (rotation 5), bound 40: the 32-row
+    partials carry the error, not the fold."""
     from boosted_detr_amd import _lib
     rows, C, nparts = 9600, 8, 300
     assert nparts > 4 * _lib.lib().bdetr_bn_stats_fold_rows()
@@ -153,22 +148,8 @@ def test_bn_stats_from_hand_made_partials(cuda, start):
     xt = torch.from_numpy(x)
     parts = (xt.view(nparts, 32, C).sum(1).cuda(), (xt * xt).view(nparts, 32, C).sum(1).cuda(), nparts)
     mean, rstd, var = finalize(rows, C, parts)
-    w = check_stats("hand-made partials start=%d R=%d" % (start, r_hand_made()), x, mean, rstd, var, r_hand_made(), names)
+    w = check_stats("hand-made partials start=%d R=%d" % (start, R_HAND_MADE), x, mean, rstd, var, R_HAND_MADE, names)
     print("VALUE_DOMAIN_RATIO %.3f" % w)
-
-
-def test_bn_stats_one_launch_reduction_in_a_child(cuda):
-    """(c) BDETR_BN_WIDE_REDUCE is read once per process: case (b) in a child process with the switch set (R = 31).  The "R=31" line
-    shows that the child saw the switch; that the switch routes bn_stats to reduce_partials2_kernel<true> is wide_reduce_min() in
-    csrc/norm.hip (300 partial rows >= 1), the path tests/test_variants_gpu.py::test_one_launch_batchnorm_reduction runs the
-    older BatchNorm tests on.  Time limit: that test's child (14 cases) takes 6.9 s and has 30 s by the rule stated there; this one
-    runs two cases behind the same start-up and gets twice that, since a timeout stops every later variant child."""
-    from test_variants_gpu import run_child
-    r = run_child("BDETR_BN_WIDE_REDUCE=1 (value domain)", {"BDETR_BN_WIDE_REDUCE": "1"},
-                  ["-m", "pytest", os.path.abspath(__file__), "-q", "-s", "-m", "gpu", "-k", "test_bn_stats_from_hand_made_partials"], 60)
-    assert r.returncode == 0 and "2 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]
-    assert "R=31" in r.stdout and "R=38" not in r.stdout
-    print("wide reduce:", re.findall(r"VALUE_DOMAIN_RATIO ([0-9.]+)", r.stdout))
 
 
 # R of bn_rows_stats (csrc/groupnorm_rows.hip group_colsum2): 64 row phases, a thread adds ceil(rows / 64) rows in fp32, the 64 phase
