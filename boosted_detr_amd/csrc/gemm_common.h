@@ -374,9 +374,72 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // fixed order z = 0 .. zdim - 1.  slab = splitk_slab(I * J); ws holds at least splitk * slab floats and is 16-byte aligned.
 inline int64_t splitk_slab(int64_t elems) { return (elems + 3) / 4 * 4; }
 int splitk_fold(const float* ws, int zdim, int64_t slab, float* dst, int64_t n, hipStream_t st);
+// Runs `launch` (the split-K launch of g over zdim slices) in that form: slabs of the caller's workspace, then the fold into g.c
+template <class F>
+int with_splitk_slabs(GemmParams& g, int zdim, float* ws, int64_t ws_elems, hipStream_t st, const char* who, F&& launch) {
+    float* c = g.c;
+    const int64_t n = (int64_t)g.I * g.J, slab = splitk_slab(n);
+    BDETR_CHECK_ARG(g.ldc == g.J, "%s: the split-K workspace form needs a dense C (ldc == J)", who);
+    BDETR_CHECK_ARG(aligned16(ws) && ws_elems >= (int64_t)zdim * slab, "%s: workspace too small or misaligned (%lld floats, need %lld)", who,
+                    (long long)ws_elems, (long long)((int64_t)zdim * slab));
+    g.c = ws; g.sc0 = slab; g.mode = ST_STORE;
+    if (int e = launch()) return e;
+    return splitk_fold(ws, zdim, slab, c, n, st);
+}
+
+// Cuts the reduction range [0, R) into about `want` slices of whole K-steps (bk) that add into C with float atomics (C zeroed by the
+// caller); returns gridDim.z.  (bdetr_gemm_grouped keeps a rule of its own: its slice count is exact, z = 1 runs unsplit.)
+inline int set_splitk(GemmParams& g, int R, int want, int bk) {
+    g.r_chunk = (int)(cdiv64(cdiv64(R, want), bk) * bk);
+    const int zdim = (int)cdiv64(R, g.r_chunk);
+    g.splitk = zdim > 1 ? zdim : 2;   // >1 keeps the split code path (r_begin/r_end)
+    g.mode = ST_ATOMIC;
+    return zdim;
+}
+
+// Backward-data of a strided convolution whose taps never overlap: C's rows scatter to the pixels (oh * stride, ow * stride) (+ rm_off)
+// of dx, and the pixels no window reads keep the zero fill made here (unless the launch accumulates)
+inline int set_rowmap(GemmParams& g, const bdetr_conv_desc* d, float* dx, bool accumulate, hipStream_t st) {
+    if (!accumulate) {
+        if (int e = bdetr_zero_bytes(dx, sizeof(float) * (size_t)d->N * d->H * d->W * d->C, st)) return e;
+    }
+    g.rowmap = 1; g.rm_OW = d->OW; g.rm_OHOW = d->OH * d->OW; g.rm_H = d->H; g.rm_W = d->W; g.rm_stride = d->stride;
+    return 0;
+}
+
+// what both GEMM files require of a convolution before their own operand limits
+inline int check_conv_geometry(const bdetr_conv_desc* d, const char* who) {
+    BDETR_CHECK_ARG(d != nullptr, "%s: null desc", who);
+    BDETR_CHECK_ARG(d->N > 0 && d->H > 0 && d->W > 0 && d->C > 0 && d->K > 0 && d->R > 0 && d->S > 0 && d->stride > 0 && d->pad >= 0,
+                    "%s: bad conv geometry", who);
+    BDETR_CHECK_ARG(d->OH == (d->H + 2 * d->pad - d->R) / d->stride + 1 && d->OW == (d->W + 2 * d->pad - d->S) / d->stride + 1,
+                    "%s: OH/OW inconsistent with geometry", who);
+    return 0;
+}
+inline bool is_1x1_dense(const bdetr_conv_desc* d) { return d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0; }
+
+// Launch plan of one pass of a convolution (of a plain GEMM: tile and arithmetic only), computed by one function per pass and file:
+// the size queries of the C ABI return its fields and the launchers launch what it names - neither restates the decision.
+enum { FAM_DENSE = 0, FAM_PATCH = 1, FAM_HALO = 2 };       // dense 1x1 operand, im2col patch gather, halo-resident 3x3 (hconv.hip)
+struct LaunchPlan {
+    int family;
+    int bm, bn, wm;      // the instantiation that launches; wm = its wave rows (partial-statistics rows per row of tiles)
+    int arith;           // igemm.hip: the AR_* that runs
+    int stat_rows;       // partial rows per statistic the epilogue writes: forward tiles_i * wm, fused BatchNorm-backward sums tiles_i
+    int splitk;          // weight gradients: split-K factor
+};
+// Before a launch that writes statistics (g.tiles_i set for the instantiation about to launch, wm its wave rows): the caller sized
+// the partial buffers from the plan, so a plan that disagrees with the kernel is refused instead of overrunning them
+inline int check_stat_rows(const GemmParams& g, int wm, int plan_rows, const char* who) {
+    BDETR_CHECK_ARG(g.stat_sum == nullptr || plan_rows == g.tiles_i * wm, "%s: the plan announced %d partial-statistics rows, this kernel writes %d", who, plan_rows, g.tiles_i * wm);
+    BDETR_CHECK_ARG(g.bnb_sum_g == nullptr || plan_rows == g.tiles_i, "%s: the plan announced %d partial-sum rows, this kernel writes %d", who, plan_rows, g.tiles_i);
+    return 0;
+}
 
 // ---- hconv.hip: 3x3 / stride 1 / pad 1 convolutions with the input halo resident in LDS ----
-int hconv_tile(int64_t rows, int W, int C, int J, bool f16);          // BM * 1000 + BN, or 0: stay on sgemm.hip's im2col kernel
-int hconv_launch(int tile, bool f16, const void* x, int N, int H, int W, int C, const void* w, int J, const GemmParams& g, hipStream_t st);
+// the halo kernel's plan for `rows` pixels of width W, C input and J output channels (fwd: stat_rows counts forward statistics, else
+// fused backward sums); false: stay on sgemm.hip's im2col kernel
+bool hconv_plan(int64_t rows, int W, int C, int J, bool fwd, LaunchPlan* p);
+int hconv_launch(const LaunchPlan& p, bool f16, const void* x, int N, int H, int W, int C, const void* w, int J, const GemmParams& g, hipStream_t st);
 
 }  // namespace bdgemm

@@ -269,11 +269,23 @@ void hconv_kernel(HInput xa, HWeight wb, GemmParams g)
     gemm_epilogue<BM, BN, WM, WN, NT, LDS_BYTES / 4>(acc, g, reinterpret_cast<float*>(lds), tile_i, i0, j0, g.c, bias_pre);
 }
 
+constexpr int HOST_WM = 4;                                  // hconv_kernel's WM: wave rows, one forward-statistics row each per row of tiles
+
+struct Switches {                                          // every environment switch of this file, read once
+    int enabled = 1, forced_tile = 0;
+    Switches() {
+        if (const char* e = getenv("BDETR_HCONV")) enabled = atoi(e);
+        if (const char* e = getenv("BDETR_HCONV_TILE")) forced_tile = atoi(e);
+    }
+};
+const Switches& switches() { static const Switches s; return s; }
+
 template <int BM, int BN, bool F16>
-int launch(const HInput& x, const HWeight& w, GemmParams g, hipStream_t st, int kind) {
+int launch(const HInput& x, const HWeight& w, GemmParams g, hipStream_t st, int kind, int stat_rows) {
     g.tiles_i = (int)cdiv64(g.I, BM);
     g.tiles_j = (int)cdiv64(g.J, BN);
     g.vec_store = (g.J % 4 == 0) && (g.ldc % 4 == 0) && aligned16(g.c);
+    if (int e = check_stat_rows(g, HOST_WM, stat_rows, "hconv")) return e;
     const bool prof = g_prof_on;
     if (prof) prof_begin(st, 2.0 * (double)g.I * (double)g.J * (double)g.R, g.I, g.J, g.R, 1, BM, BN * 10 + 3, (F16 ? AR_P16_F16 : AR_P16_BF16) * 10000 + kind);
     hipLaunchKernelGGL((hconv_kernel<BM, BN, F16>), dim3(g.tiles_i * g.tiles_j), dim3(512), 0, st, x, w, g);
@@ -285,42 +297,36 @@ int launch(const HInput& x, const HWeight& w, GemmParams g, hipStream_t st, int 
 
 namespace bdgemm {
 
-// Tile of the halo kernel for a 3x3 / stride 1 / pad 1 convolution with `rows` output pixels of width W, C input and J output
-// channels, or 0 when the launch must stay on sgemm.hip's im2col kernel.  Returned as BM * 1000 + BN.
-int hconv_tile(int64_t rows, int W, int C, int J, bool f16) {
-    static int enabled = -1;
-    if (enabled < 0) { const char* e = getenv("BDETR_HCONV"); enabled = e ? atoi(e) : 1; }
-    if (!enabled) return 0;
-    (void)f16;                                             // both flavours: one accumulator set since the f16 pair's lo half is unscaled (p16.h)
-    if (C % 32 || J % 64 || rows >= (1LL << 31)) return 0;
-    const int bn = J % 128 == 0 ? 128 : 64;
-    const int64_t cus = num_cus();
-    {   // A/B switch (tools/hconv_tile_ab.py, profiles/r04_hconv_tile_ab.json): BDETR_HCONV_TILE=256128 | 128128 | 256064 forces a tile where it fits
-        static int forced = -1;
-        if (forced < 0) { const char* e = getenv("BDETR_HCONV_TILE"); forced = e ? atoi(e) : 0; }
-        if (forced) {
-            const int fbm = forced / 1000, fbn = forced % 1000;
-            if ((fbn == 128 || fbn == 64) && (fbm == 128 || fbm == 256) && !(fbm == 128 && fbn == 64) && J % fbn == 0 && fbm + 2 * W + 2 <= halo_cap(fbn)) return forced;
-        }
-    }
+// The halo kernel's plan for a 3x3 / stride 1 / pad 1 convolution with `rows` output pixels of width W, C input and J output
+// channels; false when the launch must stay on sgemm.hip's im2col kernel.
+// (both operand flavours alike: one accumulator set since the f16 pair's lo half is unscaled, p16.h)
+bool hconv_plan(int64_t rows, int W, int C, int J, bool fwd, LaunchPlan* p) {
+    if (!switches().enabled) return false;
+    if (C % 32 || J % 64 || rows >= (1LL << 31)) return false;
+    int bn = J % 128 == 0 ? 128 : 64;
     // the bigger tile while it still gives most CUs a workgroup (one 8-wave workgroup per CU)
-    int bm = cdiv64(rows, 256) * cdiv64(J, bn) * 10 >= cus * 7 ? 256 : 128;
+    int bm = cdiv64(rows, 256) * cdiv64(J, bn) * 10 >= (int64_t)num_cus() * 7 ? 256 : 128;
     if (bm + 2 * W + 2 > halo_cap(bn)) bm = 128;
-    if (bm + 2 * W + 2 > halo_cap(bn)) return 0;
-    if (bm == 128 && bn == 64) return 0;                   // 6 MFMAs per half-step: not worth a barrier pair
-    return bm * 1000 + bn;
+    bool ok = bm + 2 * W + 2 <= halo_cap(bn) && !(bm == 128 && bn == 64);      // (128x64: 6 MFMAs per half-step, not worth a barrier pair)
+    // A/B switch (tools/hconv_tile_ab.py, profiles/r04_hconv_tile_ab.json): BDETR_HCONV_TILE=256128 | 128128 | 256064 forces a tile where it fits
+    const int fbm = switches().forced_tile / 1000, fbn = switches().forced_tile % 1000;
+    if ((fbn == 128 || fbn == 64) && (fbm == 128 || fbm == 256) && !(fbm == 128 && fbn == 64) && J % fbn == 0 && fbm + 2 * W + 2 <= halo_cap(fbn)) { bm = fbm; bn = fbn; ok = true; }
+    if (!ok) return false;
+    // forward: every wave row writes a partial row (gemm_bias_act_stats); fused backward sums: one row per row of tiles
+    *p = LaunchPlan{FAM_HALO, bm, bn, HOST_WM, 0, (int)cdiv64(rows, bm) * (fwd ? HOST_WM : 1), 0};
+    return true;
 }
 
 // x: P16 [N,H,W,C]; w: P16 [J][9 * C]; the epilogue is GemmParams' (g.I = N*H*W, g.J = J, g.R = 9 * C set by the caller)
-int hconv_launch(int tile, bool f16, const void* x, int N, int H, int W, int C, const void* w, int J, const GemmParams& g, hipStream_t st) {
+int hconv_launch(const LaunchPlan& p, bool f16, const void* x, int N, int H, int W, int C, const void* w, int J, const GemmParams& g, hipStream_t st) {
     HInput xi{x, N, H, W, C, N * H * W};
     HWeight wi{w, (unsigned)(9 * C), J};
     const int kind = 4000;                                  // profiling class: halo-resident 3x3
-    switch (tile) {
-        case 256128: return f16 ? launch<256, 128, true>(xi, wi, g, st, kind) : launch<256, 128, false>(xi, wi, g, st, kind);
-        case 128128: return f16 ? launch<128, 128, true>(xi, wi, g, st, kind) : launch<128, 128, false>(xi, wi, g, st, kind);
-        case 256064: return f16 ? launch<256, 64, true>(xi, wi, g, st, kind) : launch<256, 64, false>(xi, wi, g, st, kind);
-        default: bdetr_set_error("hconv_launch: no such tile %d", tile); return -1;
+    switch (p.bm * 1000 + p.bn) {
+        case 256128: return f16 ? launch<256, 128, true>(xi, wi, g, st, kind, p.stat_rows) : launch<256, 128, false>(xi, wi, g, st, kind, p.stat_rows);
+        case 128128: return f16 ? launch<128, 128, true>(xi, wi, g, st, kind, p.stat_rows) : launch<128, 128, false>(xi, wi, g, st, kind, p.stat_rows);
+        case 256064: return f16 ? launch<256, 64, true>(xi, wi, g, st, kind, p.stat_rows) : launch<256, 64, false>(xi, wi, g, st, kind, p.stat_rows);
+        default: bdetr_set_error("hconv_launch: no such tile %dx%d", p.bm, p.bn); return -1;
     }
 }
 

@@ -537,7 +537,16 @@ void igemm_kernel(typename LA::Op opa, typename LB::Op opb, GemmParams g)
 // ----------------------------------------------------------------------------------------
 // host-side dispatch
 // ----------------------------------------------------------------------------------------
-struct TileChoice { int bm, bn; };
+struct Switches {                                          // every environment switch of this file, read once
+    int forced_bm = 0, forced_bn = 0, initial_mode = BDETR_GEMM_MIXED;
+    Switches() {
+        if (const char* e = getenv("BDETR_TILE")) sscanf(e, "%dx%d", &forced_bm, &forced_bn);
+        if (const char* e = getenv("BDETR_GEMM_PRECISION"))
+            initial_mode = (!strcmp(e, "fp32") || !strcmp(e, "f32")) ? BDETR_GEMM_FP32 : !strcmp(e, "bf16x3") ? BDETR_GEMM_BF16X3
+                         : !strcmp(e, "split") ? BDETR_GEMM_SPLIT : !strcmp(e, "bf16x6") ? BDETR_GEMM_BF16X6 : BDETR_GEMM_MIXED;
+    }
+};
+const Switches& switches() { static const Switches s; return s; }
 
 }  // namespace
 
@@ -563,11 +572,7 @@ namespace {
 namespace bdgemm {
 thread_local int g_gemm_mode = -1;     // per host thread (include/bdetr.h): the one mode word the library keeps
 int gemm_mode() {
-    if (g_gemm_mode < 0) {
-        const char* e = getenv("BDETR_GEMM_PRECISION");
-        g_gemm_mode = !e ? BDETR_GEMM_MIXED : (!strcmp(e, "fp32") || !strcmp(e, "f32")) ? BDETR_GEMM_FP32
-                    : !strcmp(e, "bf16x3") ? BDETR_GEMM_BF16X3 : !strcmp(e, "split") ? BDETR_GEMM_SPLIT : !strcmp(e, "bf16x6") ? BDETR_GEMM_BF16X6 : BDETR_GEMM_MIXED;
-    }
+    if (g_gemm_mode < 0) g_gemm_mode = switches().initial_mode;
     return g_gemm_mode;
 }
 }  // namespace bdgemm
@@ -582,35 +587,40 @@ int use_split(bool grad) {      // -> AR_* of one product
     }
 }
 
-TileChoice choose_tile(int I, int J, int zdim, bool both_rc, bool split, bool patch = false) {
-    static int forced_bm = -1, forced_bn = -1;
-    if (forced_bm < 0) {
-        forced_bm = forced_bn = 0;
-        if (const char* e = getenv("BDETR_TILE")) sscanf(e, "%dx%d", &forced_bm, &forced_bn);
-    }
-    if (forced_bm > 0) {
-        if (J <= 32) return {128, 32};
-        return {forced_bm, forced_bn};
-    }
+// The tile and the arithmetic ONE product launches with: the heuristic's (or BDETR_TILE's) wish, then the instantiation that exists for it.
+// zdim: gridDim.z of the launch, 2 for any split-K launch; small_only: the flavour is instantiated at 64x64 only.
+LaunchPlan plan_tile(int family, int I, int J, int zdim, bool both_rc, int arith, bool small_only = false) {
+    const bool patch = family == FAM_PATCH;
+    if (arith == AR_FP16X3 && !both_rc) arith = AR_FP32;     // the fp16 split is built for the forward flavour only
+    const Switches& sw = switches();
     // Measured on MI355X (tools/gemm_bench.py): the 64x64 tile (4 workgroups per CU, 16 MFMAs per
     // wave between barriers) beats 128x128 / 128x64 on every shape of this model (M <= 409600,
     // N <= 2048): 97-108 vs 51-95 TF/s; 128x128 only wins once there are >= ~16 tiles per CU.
     auto tiles = [&](int bm, int bn) { return cdiv64(I, bm) * cdiv64(J, bn) * zdim; };
-    if (J <= 32) return {128, 32};
-    if (split) {
+    int bm = 64, bn = 64;
+    if (small_only) bm = bn = 64;
+    else if (J <= 32) { bm = 128; bn = 32; }
+    else if (sw.forced_bm > 0) { bm = sw.forced_bm; bn = sw.forced_bn; }
+    else if (arith != AR_FP32) {
         // bf16x3 (tools/gemm_bench.py on MI355X): the per-element hi/lo split is VALU work that a wider tile
         // amortises over more MFMAs, so 128x128 wins 10-25 % on the r-contiguous x r-contiguous flavour
         // (conv/dense forward) once it still yields ~a workgroup per CU; the transposing flavours and the
         // small problems stay on 64x64.
-        if (both_rc && J % 128 == 0 && tiles(128, 128) * 4 >= 3LL * num_cus()) return {128, 128};
+        if (both_rc && J % 128 == 0 && tiles(128, 128) * 4 >= 3LL * num_cus()) bm = bn = 128;
         // 3x3 convolution gradients (im2col operand, R >= 1152): 128x128 is 15-25 % faster on stages 3-5
         // (bench.py per-launch dump); the weight gradient gets its parallelism from split-K, so its rule must
-        // not depend on zdim (bdetr_conv2d_bwd_weight_splitk sizes z from this same choice)
-        if (patch && !both_rc && I % 128 == 0 && J % 128 == 0 && (zdim > 1 || tiles(128, 128) * 4 >= 3LL * num_cus())) return {128, 128};
-        return {64, 64};
-    }
-    if (tiles(128, 128) >= 16LL * num_cus() && J >= 1024) return {128, 128};
-    return {64, 64};
+        // not depend on zdim (bwd_weight_plan sizes z from this same choice)
+        else if (patch && !both_rc && I % 128 == 0 && J % 128 == 0 && (zdim > 1 || tiles(128, 128) * 4 >= 3LL * num_cus())) bm = bn = 128;
+    } else if (tiles(128, 128) >= 16LL * num_cus() && J >= 1024) bm = bn = 128;
+    // the instantiations: 128x128 (not bf16x6: two stages of three planes are 106 KB of LDS, one workgroup per CU), 128x64, 64x64, and
+    // for fp32 alone the narrow 128x32 (J <= 32: tiny heads); any other wish (BDETR_TILE) runs 64x64
+    LaunchPlan p{family, 64, 64, 2, arith, 0, 0};
+    if (arith != AR_FP32 && bn < 64) p.arith = AR_FP32;
+    if (bm == 128 && bn == 128) { p.bm = 128; p.bn = p.arith == AR_BF16X6 ? 64 : 128; }
+    else if (bm == 128 && bn == 64) p.bm = 128;
+    else if (bm == 128 && bn == 32 && p.arith == AR_FP32) { p.bm = 128; p.bn = 32; p.wm = 4; }
+    else if (bm == 128 && p.arith == AR_BF16X6) p.bm = 128;
+    return p;
 }
 
 // ---- optional live profiling of the MFMA kernel family (bench.py's roofline leg) -----------------
@@ -644,11 +654,12 @@ void prof_end(hipStream_t st) { (void)hipEventRecord(g_prof_recs.back().e1, st);
 namespace {
 
 template <int BM, int BN, int WM, int WN, class LA, bool A_RC, class LB, bool B_RC, int ARITH = AR_FP32>
-int launch_cfg(const typename LA::Op& a, const typename LB::Op& b, GemmParams g, int zdim, hipStream_t st) {
+int launch_cfg(const typename LA::Op& a, const typename LB::Op& b, GemmParams g, int zdim, hipStream_t st, int stat_rows) {
     g.tiles_i = (int)cdiv64(g.I, BM);
     g.tiles_j = (int)cdiv64(g.J, BN);
     dim3 grid(g.tiles_i * g.tiles_j, 1, zdim);
     g.vec_store = (g.J % 4 == 0) && (g.ldc % 4 == 0) && (g.sc0 % 4 == 0) && (g.sc1 % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.c) & 15) == 0);
+    if (int e = check_stat_rows(g, WM, stat_rows, "igemm")) return e;
     const bool prof = g_prof_on;
     if (prof) prof_begin(st, 2.0 * (double)g.I * (double)g.J * (double)g.R * (g.splitk > 1 ? (g.ngroups > 0 ? (double)g.ngroups : 1.0) : (double)zdim), g.I, g.J, g.R, zdim, BM, BN,
                          ARITH * 10000 + LoaderId<LA>::v * 1000 + (A_RC ? 100 : 0) + LoaderId<LB>::v * 10 + (B_RC ? 1 : 0));
@@ -657,35 +668,26 @@ int launch_cfg(const typename LA::Op& a, const typename LB::Op& b, GemmParams g,
     return bdetr_launch_status("igemm");
 }
 
+// launches the instantiation p (from plan_tile) names; a plan without one is an error, never another kernel
 template <class LA, bool A_RC, class LB, bool B_RC>
-int launch_any(const typename LA::Op& a, const typename LB::Op& b, GemmParams g, int zdim, hipStream_t st, int arith, bool small_only = false) {
-    if (arith == AR_FP16X3 && !(A_RC && B_RC)) arith = AR_FP32;     // the fp16 split is built for the forward flavour only
-    constexpr bool PATCH = LoaderId<LA>::v == 1 || LoaderId<LB>::v == 1;
-    TileChoice t = small_only ? TileChoice{64, 64} : choose_tile(g.I, g.J, g.splitk > 1 ? 2 : zdim, A_RC && B_RC, arith != AR_FP32, PATCH);
-    if constexpr (LoaderId<LA>::v != 3 && LoaderId<LB>::v != 3) {
-        // 16-byte loaders only; the narrow 128x32 tile (J <= 32: tiny heads) stays on the fp32 kernel
-        if (arith == AR_BF16X3 && t.bn >= 64) {
-            if (t.bm == 128 && t.bn == 128) return launch_cfg<128, 128, 2, 2, LA, A_RC, LB, B_RC, AR_BF16X3>(a, b, g, zdim, st);
-            if (t.bm == 128 && t.bn == 64)  return launch_cfg<128, 64, 2, 2, LA, A_RC, LB, B_RC, AR_BF16X3>(a, b, g, zdim, st);
-            return launch_cfg<64, 64, 2, 2, LA, A_RC, LB, B_RC, AR_BF16X3>(a, b, g, zdim, st);
-        }
-        if (arith == AR_BF16X6 && t.bn >= 64) {
-            // (no 128x128: two stages of three planes are 106 KB of LDS - one workgroup per CU)
-            if (t.bm == 128) return launch_cfg<128, 64, 2, 2, LA, A_RC, LB, B_RC, AR_BF16X6>(a, b, g, zdim, st);
-            return launch_cfg<64, 64, 2, 2, LA, A_RC, LB, B_RC, AR_BF16X6>(a, b, g, zdim, st);
-        }
-        if constexpr (A_RC && B_RC) {
-            if (arith == AR_FP16X3 && t.bn >= 64) {
-                if (t.bm == 128 && t.bn == 128) return launch_cfg<128, 128, 2, 2, LA, A_RC, LB, B_RC, AR_FP16X3>(a, b, g, zdim, st);
-                if (t.bm == 128 && t.bn == 64)  return launch_cfg<128, 64, 2, 2, LA, A_RC, LB, B_RC, AR_FP16X3>(a, b, g, zdim, st);
-                return launch_cfg<64, 64, 2, 2, LA, A_RC, LB, B_RC, AR_FP16X3>(a, b, g, zdim, st);
-            }
-        }
+int launch_any(const typename LA::Op& a, const typename LB::Op& b, const GemmParams& g, int zdim, hipStream_t st, const LaunchPlan& p) {
+    auto tiles_of = [&](auto arith_c) -> int {
+        constexpr int AR = decltype(arith_c)::value;
+        const int tile = p.bm * 1000 + p.bn;
+        if constexpr (AR != AR_BF16X6) if (tile == 128128) return launch_cfg<128, 128, 2, 2, LA, A_RC, LB, B_RC, AR>(a, b, g, zdim, st, p.stat_rows);
+        if (tile == 128064) return launch_cfg<128, 64, 2, 2, LA, A_RC, LB, B_RC, AR>(a, b, g, zdim, st, p.stat_rows);
+        if constexpr (AR == AR_FP32) if (tile == 128032) return launch_cfg<128, 32, 4, 1, LA, A_RC, LB, B_RC, AR>(a, b, g, zdim, st, p.stat_rows);
+        if (tile == 64064) return launch_cfg<64, 64, 2, 2, LA, A_RC, LB, B_RC, AR>(a, b, g, zdim, st, p.stat_rows);
+        bdetr_set_error("igemm: no kernel for the planned tile %dx%d with arithmetic %d", p.bm, p.bn, AR);
+        return -1;
+    };
+    if constexpr (LoaderId<LA>::v != 3 && LoaderId<LB>::v != 3) {       // the split arithmetics need the 16-byte loaders
+        if (p.arith == AR_BF16X3) return tiles_of(std::integral_constant<int, AR_BF16X3>{});
+        if (p.arith == AR_BF16X6) return tiles_of(std::integral_constant<int, AR_BF16X6>{});
+        if constexpr (A_RC && B_RC) if (p.arith == AR_FP16X3) return tiles_of(std::integral_constant<int, AR_FP16X3>{});
     }
-    if (t.bm == 128 && t.bn == 128) return launch_cfg<128, 128, 2, 2, LA, A_RC, LB, B_RC>(a, b, g, zdim, st);
-    if (t.bm == 128 && t.bn == 64)  return launch_cfg<128, 64, 2, 2, LA, A_RC, LB, B_RC>(a, b, g, zdim, st);
-    if (t.bm == 128 && t.bn == 32)  return launch_cfg<128, 32, 4, 1, LA, A_RC, LB, B_RC>(a, b, g, zdim, st);
-    return launch_cfg<64, 64, 2, 2, LA, A_RC, LB, B_RC>(a, b, g, zdim, st);
+    BDETR_CHECK_ARG(p.arith == AR_FP32, "igemm: no kernel with arithmetic %d for these operands", p.arith);
+    return tiles_of(std::integral_constant<int, AR_FP32>{});
 }
 
 // The loaders address an operand with 32-bit byte offsets from its base (raw buffer loads, NUM_RECORDS):
@@ -694,13 +696,6 @@ int launch_any(const typename LA::Op& a, const typename LB::Op& b, GemmParams g,
 constexpr int64_t MAX_OPERAND_ELEMS = (int64_t)(NUM_RECORDS / 4) - 64;
 bool span_ok(int64_t elems) { return elems >= 0 && elems <= MAX_OPERAND_ELEMS; }
 int64_t dense_span(const DenseOp& o) { return (int64_t)(o.rows - 1) * o.ld + o.cols; }
-
-// number of partial-statistics rows the epilogue writes for an (I,J) problem: tiles_i * WM
-int stat_chunks(int I, int J) {
-    TileChoice t = choose_tile(I, J, 1, true, use_split(false) != AR_FP32);
-    const int wm = (t.bm == 128 && t.bn == 32) ? 4 : 2;
-    return (int)cdiv64(I, t.bm) * wm;
-}
 
 // dst[i] += ws[0][i] + ws[1][i] + ... in that order: the fixed-order fold of the deterministic split-K mode
 __global__ __launch_bounds__(256) void splitk_fold_kernel(const float* __restrict__ ws, int zdim, int64_t slab, float* __restrict__ dst, int64_t n) {
@@ -787,6 +782,17 @@ extern "C" int bdetr_prof_read_arith(int arith, double* total_ms, int64_t* launc
     return prof_sum(arith, total_ms, launches, flops);
 }
 
+// One dense product (or group) on V-float loaders: plans the tile for its operand flavour and launches it
+template <int V>
+static int launch_dense(const DenseOp& a, const DenseOp& b, const GemmParams& g, int zdim, hipStream_t st, bool arc, bool brc, int arith) {
+    // the scalar loaders and the [r][i] x [j][r] flavour are instantiated at 64x64 only
+    const LaunchPlan p = plan_tile(FAM_DENSE, g.I, g.J, g.splitk > 1 ? 2 : zdim, arc && brc, arith, V == 1 || (!arc && brc));
+    if (arc && brc)   return launch_any<DenseLoader<V>, true, DenseLoader<V>, true>(a, b, g, zdim, st, p);
+    if (arc && !brc)  return launch_any<DenseLoader<V>, true, DenseLoader<V>, false>(a, b, g, zdim, st, p);
+    if (!arc && !brc) return launch_any<DenseLoader<V>, false, DenseLoader<V>, false>(a, b, g, zdim, st, p);
+    return launch_any<DenseLoader<V>, false, DenseLoader<V>, true>(a, b, g, zdim, st, p);
+}
+
 // Up to 4 independent dense GEMMs with the same J, R, operand flavours and epilogue in ONE launch
 // (gridDim.z = n): the Q/K/V projections of an attention block and their input gradients.
 extern "C" int bdetr_gemm_grouped(const bdetr_gemm_desc* d, int n, void* stream) {
@@ -832,28 +838,10 @@ extern "C" int bdetr_gemm_grouped(const bdetr_gemm_desc* d, int n, void* stream)
     DenseOp a{f.a, f.lda, 0, 0, f.a_rcontig ? maxI : f.R, f.a_rcontig ? f.R : maxI};
     DenseOp b{f.b, f.ldb, 0, 0, f.b_rcontig ? f.J : f.R, f.b_rcontig ? f.R : f.J};
     hipStream_t st = (hipStream_t)stream;
-    const bool arc = f.a_rcontig != 0, brc = f.b_rcontig != 0;
-    const int sp = use_split(f.grad != 0);
-    if (arc && brc)   return launch_any<DenseLoader<4>, true, DenseLoader<4>, true>(a, b, g, zdim, st, sp);
-    if (arc && !brc)  return launch_any<DenseLoader<4>, true, DenseLoader<4>, false>(a, b, g, zdim, st, sp);
-    if (!arc && !brc) return launch_any<DenseLoader<4>, false, DenseLoader<4>, false>(a, b, g, zdim, st, sp);
-    return launch_any<DenseLoader<4>, false, DenseLoader<4>, true>(a, b, g, zdim, st, sp, true);
+    return launch_dense<4>(a, b, g, zdim, st, f.a_rcontig != 0, f.b_rcontig != 0, use_split(f.grad != 0));
 }
 
 extern "C" int bdetr_gemm(const bdetr_gemm_desc* d, void* stream) { return bdetr_gemm_ws(d, nullptr, 0, stream); }
-
-template <class F>
-static int with_splitk_slabs(GemmParams& g, int zdim, float* ws, int64_t ws_elems, hipStream_t st, const char* who, F&& launch) {
-    // deterministic split-K: the slices store into slabs of the caller's workspace, a second launch folds them into C in order
-    float* c = g.c;
-    const int64_t n = (int64_t)g.I * g.J, slab = splitk_slab(n);
-    BDETR_CHECK_ARG(g.ldc == g.J, "%s: the split-K workspace form needs a dense C (ldc == J)", who);
-    BDETR_CHECK_ARG(aligned16(ws) && ws_elems >= (int64_t)zdim * slab, "%s: workspace too small or misaligned (%lld floats, need %lld)", who,
-                    (long long)ws_elems, (long long)((int64_t)zdim * slab));
-    g.c = ws; g.sc0 = slab; g.mode = ST_STORE;
-    if (int e = launch()) return e;
-    return splitk_fold(ws, zdim, slab, c, n, st);
-}
 
 extern "C" int bdetr_gemm_ws(const bdetr_gemm_desc* d, float* ws, int64_t ws_elems, void* stream) {
     BDETR_CHECK_ARG(d && d->a && d->b && d->c, "bdetr_gemm: null pointer");
@@ -871,53 +859,72 @@ extern "C" int bdetr_gemm_ws(const bdetr_gemm_desc* d, float* ws, int64_t ws_ele
     g.I = d->I; g.J = d->J; g.R = d->R; g.nb1 = nb1;
     g.c = d->c; g.ldc = d->ldc; g.sc0 = d->sc0; g.sc1 = d->sc1;
     g.bias = d->bias; g.alpha = d->alpha; g.act = d->act;
-    g.mode = splitk > 1 ? ST_ATOMIC : (d->accumulate ? ST_ACCUM : ST_STORE);
-    int zdim = nb0 * nb1;
-    if (splitk > 1) {
-        g.splitk = splitk;
-        g.r_chunk = (int)(cdiv64(cdiv64(d->R, splitk), BK) * BK);
-        zdim = (int)cdiv64(d->R, g.r_chunk);
-        g.splitk = zdim > 1 ? zdim : 2;   // >1 keeps the split code path (r_begin/r_end)
-    }
+    g.mode = d->accumulate ? ST_ACCUM : ST_STORE;
+    const int zdim = splitk > 1 ? set_splitk(g, d->R, splitk, BK) : nb0 * nb1;
     auto vec_ok = [&](const DenseOp& o) {
         return aligned16(o.p) && o.ld % 4 == 0 && o.s0 % 4 == 0 && o.s1 % 4 == 0 && o.cols % 4 == 0;
     };
-    const bool v4 = vec_ok(a) && vec_ok(b);
     const bool arc = d->a_rcontig != 0, brc = d->b_rcontig != 0;
-    const int sp = use_split(d->grad != 0);
     auto launch = [&]() -> int {
-        if (v4) {
-            if (arc && brc)   return launch_any<DenseLoader<4>, true, DenseLoader<4>, true>(a, b, g, zdim, st, sp);
-            if (arc && !brc)  return launch_any<DenseLoader<4>, true, DenseLoader<4>, false>(a, b, g, zdim, st, sp);
-            if (!arc && !brc) return launch_any<DenseLoader<4>, false, DenseLoader<4>, false>(a, b, g, zdim, st, sp);
-            return launch_any<DenseLoader<4>, false, DenseLoader<4>, true>(a, b, g, zdim, st, sp, true);
-        }
+        if (vec_ok(a) && vec_ok(b)) return launch_dense<4>(a, b, g, zdim, st, arc, brc, use_split(d->grad != 0));
         // unaligned fallback (scalar HBM loads): only tiny problems take it (82-wide heads, T=49 attention)
-        if (arc && brc)   return launch_any<DenseLoader<1>, true, DenseLoader<1>, true>(a, b, g, zdim, st, AR_FP32, true);
-        if (arc && !brc)  return launch_any<DenseLoader<1>, true, DenseLoader<1>, false>(a, b, g, zdim, st, AR_FP32, true);
-        if (!arc && !brc) return launch_any<DenseLoader<1>, false, DenseLoader<1>, false>(a, b, g, zdim, st, AR_FP32, true);
-        return launch_any<DenseLoader<1>, false, DenseLoader<1>, true>(a, b, g, zdim, st, AR_FP32, true);
+        return launch_dense<1>(a, b, g, zdim, st, arc, brc, AR_FP32);
     };
     if (ws != nullptr && splitk > 1) return with_splitk_slabs(g, zdim, ws, ws_elems, st, "bdetr_gemm_ws", launch);
     return launch();
 }
 
 static int check_conv(const bdetr_conv_desc* d, const char* who) {
-    BDETR_CHECK_ARG(d != nullptr, "%s: null desc", who);
-    BDETR_CHECK_ARG(d->N > 0 && d->H > 0 && d->W > 0 && d->C > 0 && d->K > 0 && d->R > 0 && d->S > 0 && d->stride > 0 && d->pad >= 0,
-                    "%s: bad conv geometry", who);
+    if (int e = check_conv_geometry(d, who)) return e;
     BDETR_CHECK_ARG(d->C % 4 == 0, "%s: input channels must be a multiple of 4 (got %d)", who, d->C);
-    BDETR_CHECK_ARG(d->OH == (d->H + 2 * d->pad - d->R) / d->stride + 1 && d->OW == (d->W + 2 * d->pad - d->S) / d->stride + 1,
-                    "%s: OH/OW inconsistent with geometry", who);
     BDETR_CHECK_ARG((int64_t)d->N * d->OH * d->OW < (1LL << 31) && (int64_t)d->R * d->S * d->C < (1LL << 31), "%s: problem too large", who);
     BDETR_CHECK_ARG(span_ok((int64_t)d->N * d->H * d->W * d->C) && span_ok((int64_t)d->N * d->OH * d->OW * d->K) && span_ok((int64_t)d->K * d->R * d->S * d->C),
                     "%s: a tensor spans 4 GB or more (the loaders use 32-bit buffer offsets); use a smaller per-GPU batch", who);
     return 0;
 }
 
+static LaunchPlan fwd_plan(const bdetr_conv_desc* d) {
+    const int M = d->N * d->OH * d->OW;
+    LaunchPlan p = plan_tile(is_1x1_dense(d) ? FAM_DENSE : FAM_PATCH, M, d->K, 1, true, use_split(false));
+    p.stat_rows = (int)cdiv64(M, p.bm) * p.wm;
+    return p;
+}
+
+// FAM_DENSE: 1x1 convolutions of any stride and taps that never overlap (R, S <= stride, pad 0) - dense products whose rows scatter
+static LaunchPlan bwd_data_plan(const bdetr_conv_desc* d) {
+    const bool dense = d->pad == 0 && ((d->R == 1 && d->S == 1) || (d->stride > 1 && d->R <= d->stride && d->S <= d->stride));
+    return plan_tile(dense ? FAM_DENSE : FAM_PATCH, dense ? d->N * d->OH * d->OW : d->N * d->H * d->W, d->C, 1, false, use_split(true));
+}
+
+// splitk <= 0: the factor is the plan's to choose (what bdetr_conv2d_bwd_weight_splitk reports)
+static LaunchPlan bwd_weight_plan(const bdetr_conv_desc* d, int splitk) {
+    const int M = d->N * d->OH * d->OW, Kd = d->R * d->S * d->C;
+    const int family = is_1x1_dense(d) ? FAM_DENSE : FAM_PATCH, arith = use_split(true);
+    LaunchPlan p = plan_tile(family, d->K, Kd, 2, false, arith);
+    if (splitk <= 0) {
+        // (bf16x6 runs a 128x128 wish on 128x64 tiles; its slice count keeps following the wish, as the other split arithmetics' does)
+        const LaunchPlan wish = arith == AR_BF16X6 ? plan_tile(family, d->K, Kd, 2, false, AR_BF16X3) : p;
+        int64_t tiles = cdiv64(d->K, wish.bm) * cdiv64(Kd, wish.bn);
+        int64_t want = 3LL * num_cus();
+        // A handful of output tiles over a very long pixel range - the stem's 64 x 196 gradient over 1.6 M pixels, the LAST kernel of the
+        // backward pass, alone on the chip with the optimizer waiting for it: 16 workgroups per CU instead of 3 (tools/stem_wgrad_probe.py,
+        // round 5: split 192 -> 467 us, 1024 -> 355 us)
+        const bool few_tiles = tiles <= 8 && M >= (1 << 20);      // (the pixel-count bound keeps the stage-2 layers of the igemm backward policies - bf16x6, fp32: 0.4 M pixels, 1-4 tiles - on their 3 workgroups per CU: 1,024 slices of 64-KB atomics each cost value_fp32_grade 22 %)
+        if (few_tiles) want = 16LL * num_cus();
+        int64_t sk = cdiv64(want, tiles);
+        int64_t maxsk = cdiv64(M, 4 * BK);      // keep >= 4 stages per split
+        if (sk > maxsk) sk = maxsk;
+        if (sk < 1) sk = 1;
+        if (sk > (few_tiles ? 1024 : 512)) sk = few_tiles ? 1024 : 512;
+        splitk = (int)sk;
+    }
+    if (splitk == 1) p = plan_tile(family, d->K, Kd, 1, false, arith);      // one slice: the tile of an unsplit launch
+    p.splitk = splitk;
+    return p;
+}
+
 extern "C" int bdetr_conv2d_fwd_stat_chunks(const bdetr_conv_desc* d) {
-    if (check_conv(d, "bdetr_conv2d_fwd_stat_chunks")) return -1;
-    return stat_chunks(d->N * d->OH * d->OW, d->K);
+    return check_conv(d, "bdetr_conv2d_fwd_stat_chunks") ? -1 : fwd_plan(d).stat_rows;
 }
 
 extern "C" int bdetr_conv2d_fwd(const float* x, const float* w, const float* bias, float* y,
@@ -933,12 +940,13 @@ extern "C" int bdetr_conv2d_fwd(const float* x, const float* w, const float* bia
     g.stat_sum = stat_sum; g.stat_sq = stat_sq;
     DenseOp wop{w, Kd, 0, 0, d->K, Kd};
     hipStream_t st = (hipStream_t)stream;
-    if (d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0) {
+    const LaunchPlan p = fwd_plan(d);
+    if (p.family == FAM_DENSE) {
         DenseOp xop{x, d->C, 0, 0, M, d->C};
-        return launch_any<DenseLoader<4>, true, DenseLoader<4>, true>(xop, wop, g, 1, st, use_split(false));
+        return launch_any<DenseLoader<4>, true, DenseLoader<4>, true>(xop, wop, g, 1, st, p);
     }
     PatchOp xop{x, d->N, d->H, d->W, d->C, d->OH, d->OW, d->R, d->S, d->stride, d->pad, M, Kd};
-    return launch_any<PatchLoader, true, DenseLoader<4>, true>(xop, wop, g, 1, st, use_split(false));
+    return launch_any<PatchLoader, true, DenseLoader<4>, true>(xop, wop, g, 1, st, p);
 }
 
 extern "C" int bdetr_conv2d_bwd_data(const float* dy, const float* w, float* dx,
@@ -950,34 +958,22 @@ extern "C" int bdetr_conv2d_bwd_data(const float* dy, const float* w, float* dx,
     const int M = d->N * d->OH * d->OW;
     GemmParams g; init_params(g);
     g.c = dx; g.ldc = d->C; g.mode = accumulate ? ST_ACCUM : ST_STORE;
-    if (d->R == 1 && d->S == 1 && d->pad == 0) {
-        // dx[m][c] = sum_k dy[m][k] * w[k][c]; strided convs scatter their rows into the strided pixels
+    const LaunchPlan p = bwd_data_plan(d);
+    if (p.family == FAM_DENSE) {
+        // dx[m][c] = sum_k dy[m][k] * w[k][c]; strided convs scatter their rows into the strided pixels.  Taps that never overlap (the
+        // panoptic head's 3x3 stride-4 ConvOut): every (output pixel, tap) owns one input pixel, so dx = R*S dense products
+        // dy[M,K] x w[:, r, s, :] scattered to the pixels (oh*stride + r, ow*stride + s); the pixels no window reads (ih % stride >= R,
+        // or beyond the last window) keep the zero fill
         g.I = M; g.J = d->C; g.R = d->K;
         if (d->stride > 1) {
-            if (!accumulate) {
-                if (int e = bdetr_zero_bytes(dx, sizeof(float) * (size_t)d->N * d->H * d->W * d->C, st)) return e;
-            }
-            g.rowmap = 1; g.rm_OW = d->OW; g.rm_OHOW = d->OH * d->OW; g.rm_H = d->H; g.rm_W = d->W; g.rm_stride = d->stride;
+            if (int e = set_rowmap(g, d, dx, accumulate, st)) return e;
         }
-        DenseOp a{dy, d->K, 0, 0, M, d->K};
-        DenseOp b{w, d->C, 0, 0, d->K, d->C};
-        return launch_any<DenseLoader<4>, true, DenseLoader<4>, false>(a, b, g, 1, st, use_split(true));
-    }
-    if (d->stride > 1 && d->pad == 0 && d->R <= d->stride && d->S <= d->stride) {
-        // taps that never overlap (the panoptic head's 3x3 stride-4 ConvOut): every (output pixel, tap) owns one input pixel, so
-        // dx = R*S dense products dy[M,K] x w[:, r, s, :] scattered to the pixels (oh*stride + r, ow*stride + s); the pixels no
-        // window reads (ih % stride >= R, or beyond the last window) keep the zero fill
-        if (!accumulate) {
-            if (int e = bdetr_zero_bytes(dx, sizeof(float) * (size_t)d->N * d->H * d->W * d->C, st)) return e;
-        }
-        g.I = M; g.J = d->C; g.R = d->K;
-        g.rowmap = 1; g.rm_OW = d->OW; g.rm_OHOW = d->OH * d->OW; g.rm_H = d->H; g.rm_W = d->W; g.rm_stride = d->stride;
         DenseOp a{dy, d->K, 0, 0, M, d->K};
         for (int r = 0; r < d->R; ++r)
             for (int s = 0; s < d->S; ++s) {
                 g.rm_off = r * d->W + s;
                 DenseOp b{w + (int64_t)(r * d->S + s) * d->C, (int64_t)d->R * d->S * d->C, 0, 0, d->K, d->C};
-                if (int e = launch_any<DenseLoader<4>, true, DenseLoader<4>, false>(a, b, g, 1, st, use_split(true))) return e;
+                if (int e = launch_any<DenseLoader<4>, true, DenseLoader<4>, false>(a, b, g, 1, st, p)) return e;
             }
         return 0;
     }
@@ -989,26 +985,11 @@ extern "C" int bdetr_conv2d_bwd_data(const float* dy, const float* w, float* dx,
     PatchOp a{dy, d->N, d->OH, d->OW, d->K, d->H, d->W, d->R, d->S, 1, d->R - 1 - d->pad, Mx, d->R * d->S * d->K};
     BDETR_CHECK_ARG(d->R == d->S, "bdetr_conv2d_bwd_data: square kernels only");
     WFlipOp b{w, d->K, d->C, d->R, d->S, d->R * d->S * d->K, d->C};
-    return launch_any<PatchLoader, true, WFlipLoader, false>(a, b, g, 1, st, use_split(true));
+    return launch_any<PatchLoader, true, WFlipLoader, false>(a, b, g, 1, st, p);
 }
 
 extern "C" int bdetr_conv2d_bwd_weight_splitk(const bdetr_conv_desc* d) {
-    if (check_conv(d, "bdetr_conv2d_bwd_weight_splitk")) return -1;
-    const int M = d->N * d->OH * d->OW, Kd = d->R * d->S * d->C;
-    TileChoice t = choose_tile(d->K, Kd, 2, false, use_split(true) != AR_FP32, !(d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0));
-    int64_t tiles = cdiv64(d->K, t.bm) * cdiv64(Kd, t.bn);
-    int64_t want = 3LL * num_cus();
-    // A handful of output tiles over a very long pixel range - the stem's 64 x 196 gradient over 1.6 M pixels, the LAST kernel of the
-    // backward pass, alone on the chip with the optimizer waiting for it: 16 workgroups per CU instead of 3 (tools/stem_wgrad_probe.py,
-    // round 5: split 192 -> 467 us, 1024 -> 355 us)
-    const bool few_tiles = tiles <= 8 && M >= (1 << 20);      // (the pixel-count bound keeps the stage-2 layers of the igemm backward policies - bf16x6, fp32: 0.4 M pixels, 1-4 tiles - on their 3 workgroups per CU: 1,024 slices of 64-KB atomics each cost value_fp32_grade 22 %)
-    if (few_tiles) want = 16LL * num_cus();
-    int64_t sk = cdiv64(want, tiles);
-    int64_t maxsk = cdiv64(M, 4 * BK);      // keep >= 4 stages per split
-    if (sk > maxsk) sk = maxsk;
-    if (sk < 1) sk = 1;
-    if (sk > (few_tiles ? 1024 : 512)) sk = few_tiles ? 1024 : 512;
-    return (int)sk;
+    return check_conv(d, "bdetr_conv2d_bwd_weight_splitk") ? -1 : bwd_weight_plan(d, 0).splitk;
 }
 
 extern "C" int bdetr_conv2d_bwd_weight(const float* x, const float* dy, float* dw,
@@ -1022,26 +1003,20 @@ extern "C" int bdetr_conv2d_bwd_weight_ws(const float* x, const float* dy, float
     BDETR_CHECK_ARG(d->K % 4 == 0, "bdetr_conv2d_bwd_weight: output channels must be a multiple of 4");
     hipStream_t st = (hipStream_t)stream;
     const int M = d->N * d->OH * d->OW, Kd = d->R * d->S * d->C;
-    if (splitk <= 0) splitk = bdetr_conv2d_bwd_weight_splitk(d);
+    const LaunchPlan p = bwd_weight_plan(d, splitk);
     GemmParams g; init_params(g);
     g.I = d->K; g.J = Kd; g.R = M;
     g.c = dw; g.ldc = Kd;
-    int zdim = 1;
-    if (splitk > 1) {
-        g.r_chunk = (int)(cdiv64(cdiv64(M, splitk), BK) * BK);
-        zdim = (int)cdiv64(M, g.r_chunk);
-        g.splitk = zdim > 1 ? zdim : 2;
-        g.mode = ST_ATOMIC;
-    }
+    const int zdim = p.splitk > 1 ? set_splitk(g, M, p.splitk, BK) : 1;
     DenseOp a{dy, d->K, 0, 0, M, d->K};           // rows = r (pixels), cols = i (k)
     auto launch = [&]() -> int {
-        if (d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0) {
+        if (p.family == FAM_DENSE) {
             DenseOp b{x, d->C, 0, 0, M, d->C};
-            return launch_any<DenseLoader<4>, false, DenseLoader<4>, false>(a, b, g, zdim, st, use_split(true));
+            return launch_any<DenseLoader<4>, false, DenseLoader<4>, false>(a, b, g, zdim, st, p);
         }
         PatchOp b{x, d->N, d->H, d->W, d->C, d->OH, d->OW, d->R, d->S, d->stride, d->pad, M, Kd};
-        return launch_any<DenseLoader<4>, false, PatchLoader, false>(a, b, g, zdim, st, use_split(true));
+        return launch_any<DenseLoader<4>, false, PatchLoader, false>(a, b, g, zdim, st, p);
     };
-    if (ws != nullptr && splitk > 1) return with_splitk_slabs(g, zdim, ws, ws_elems, st, "bdetr_conv2d_bwd_weight_ws", launch);
+    if (ws != nullptr && p.splitk > 1) return with_splitk_slabs(g, zdim, ws, ws_elems, st, "bdetr_conv2d_bwd_weight_ws", launch);
     return launch();
 }

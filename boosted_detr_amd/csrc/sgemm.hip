@@ -691,24 +691,39 @@ void sgemm_kernel(typename LA::Op opa, typename LB::Op opb, GemmParams g)
 enum { T_128x128 = 0, T_128x64 = 1, T_64x64 = 2, T_COUNT = 3 };
 const int TILE_BM[T_COUNT] = {128, 128, 64};
 const int TILE_BN[T_COUNT] = {128, 64, 64};
-const int TILE_WM[T_COUNT] = {2, 2, 2};
+constexpr int TILE_WM = 2, TILE_WN = 2;                    // every instantiated tile runs 2 x 2 waves
 
-int forced_tile() {
-    static int forced = -2;
-    if (forced == -2) {
-        forced = -1;
-        if (const char* e = getenv("BDETR_STILE")) {
-            const char* names[T_COUNT] = {"128x128", "128x64", "64x64"};
-            for (int t = 0; t < T_COUNT; ++t) if (!strcmp(e, names[t])) forced = t;
-        }
+struct Switches {                                          // every environment switch of this file, read once
+    int forced_tile = -1;                                  // BDETR_STILE: T_*, or -1
+    bool wgrad_wide;                                       // BDETR_WGRAD_1X1_TILE=128x128 (A/B switch)
+    int want_x, want_3x3, want_64, min_stages;             // split-K occupancy targets of the weight gradients (bwd_weight_plan), each >= 1
+    bool want_3x3_set;                                     // BDETR_WGRAD_WANT_3X3 was given: it then rules the 64x64 im2col layers too
+    int dbg = 0;                                           // BDETR_SGEMM_DBG (diagnostic builds only)
+    Switches() {
+        const char* names[T_COUNT] = {"128x128", "128x64", "64x64"};
+        if (const char* e = getenv("BDETR_STILE")) for (int t = 0; t < T_COUNT; ++t) if (!strcmp(e, names[t])) forced_tile = t;
+        const char* w = getenv("BDETR_WGRAD_1X1_TILE");
+        wgrad_wide = w && !strcmp(w, "128x128");
+        auto num = [](const char* e, int dflt) { const int v = e ? atoi(e) : dflt; return v < 1 ? 1 : v; };
+        want_x = num(getenv("BDETR_WGRAD_WANT"), 2);       // measured: 2 workgroups per CU (5.9 ms over the ResNet-50 layers) beats 1 (6.5), 3 (6.4), 4 (6.9): atomic bytes grow with the split
+        const char* e3 = getenv("BDETR_WGRAD_WANT_3X3");   // (the same for the im2col layers alone: A/B switch)
+        want_3x3_set = e3 != nullptr;
+        want_3x3 = num(e3, want_x);
+        want_64 = num(getenv("BDETR_WGRAD_WANT_64"), 3);
+        min_stages = num(getenv("BDETR_WGRAD_MINSTAGES"), 8);
+#ifdef BDETR_SGEMM_DIAG
+        if (const char* d = getenv("BDETR_SGEMM_DBG")) dbg = atoi(d);
+#endif
     }
-    return forced;
-}
+};
+const Switches& switches() { static const Switches s; return s; }
+
+LaunchPlan tile_plan(int family, int t) { return LaunchPlan{family, TILE_BM[t], TILE_BN[t], TILE_WM, 0, 0, 0}; }
 
 // Bigger tiles stage fewer bytes per FLOP (128x128: 32 FLOP per staged byte, 64x64: 16) but need enough
 // workgroups to fill 256 CUs x 2 resident workgroups.
 int choose_tile(int64_t I, int64_t J, int64_t z) {
-    const int forced = forced_tile();
+    const int forced = switches().forced_tile;
     if (forced >= 0) return (J < 64 || (TILE_BN[forced] == 128 && J < 128)) ? T_64x64 : forced;
     const int64_t cus = num_cus();
     auto tiles = [&](int bm, int bn) { return cdiv64(I, bm) * cdiv64(J, bn) * z; };
@@ -718,16 +733,15 @@ int choose_tile(int64_t I, int64_t J, int64_t z) {
 }
 
 template <int BM, int BN, int WM, int WN, int NS, class LA, class LB, bool XX, bool F16, int OCC = default_occ(BM, BN, WM, WN, NS)>
-int launch_cfg(const typename LA::Op& a, const typename LB::Op& b, GemmParams g, int zdim, hipStream_t st, int kind) {
+int launch_cfg(const typename LA::Op& a, const typename LB::Op& b, GemmParams g, int zdim, hipStream_t st, int kind, int stat_rows) {
     g.tiles_i = (int)cdiv64(g.I, BM);
     g.tiles_j = (int)cdiv64(g.J, BN);
     dim3 grid(g.tiles_i * g.tiles_j, 1, zdim);
     g.vec_store = (g.J % 4 == 0) && (g.ldc % 4 == 0) && aligned16(g.c);
+    if (int e = check_stat_rows(g, WM, stat_rows, "sgemm")) return e;
 #ifdef BDETR_SGEMM_DIAG
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = getenv("BDETR_SGEMM_DBG"); dbg = e ? atoi(e) : 0; }
-    g.dbg = dbg;
-    if (dbg & 4) g.vec_store = 0;
+    g.dbg = switches().dbg;
+    if (g.dbg & 4) g.vec_store = 0;
 #endif
     const bool prof = g_prof_on;
     if (prof) prof_begin(st, 2.0 * (double)g.I * (double)g.J * (double)g.R, g.I, g.J, g.R, zdim, BM, BN * 10 + NS,
@@ -773,11 +787,12 @@ int launch_cfg(const typename LA::Op& a, const typename LB::Op& b, GemmParams g,
 }
 
 template <class LA, class LB, bool XX, bool F16>
-int launch_any(const typename LA::Op& a, const typename LB::Op& b, const GemmParams& g, int zdim, hipStream_t st, int kind, int tile) {
-    switch (tile) {
-        case T_128x128:    return launch_cfg<128, 128, 2, 2, 2, LA, LB, XX, F16>(a, b, g, zdim, st, kind);
-        case T_128x64:     return launch_cfg<128, 64, 2, 2, 2, LA, LB, XX, F16>(a, b, g, zdim, st, kind);
-        default:           return launch_cfg<64, 64, 2, 2, 2, LA, LB, XX, F16>(a, b, g, zdim, st, kind);
+int launch_any(const typename LA::Op& a, const typename LB::Op& b, const GemmParams& g, int zdim, hipStream_t st, int kind, const LaunchPlan& p) {
+    switch (p.bm * 1000 + p.bn) {
+        case 128128:       return launch_cfg<128, 128, TILE_WM, TILE_WN, 2, LA, LB, XX, F16>(a, b, g, zdim, st, kind, p.stat_rows);
+        case 128064:       return launch_cfg<128, 64, TILE_WM, TILE_WN, 2, LA, LB, XX, F16>(a, b, g, zdim, st, kind, p.stat_rows);
+        case 64064:        return launch_cfg<64, 64, TILE_WM, TILE_WN, 2, LA, LB, XX, F16>(a, b, g, zdim, st, kind, p.stat_rows);
+        default:           bdetr_set_error("sgemm: no kernel for the planned tile %dx%d", p.bm, p.bn); return -1;
     }
 }
 
@@ -787,11 +802,7 @@ constexpr int64_t MAX_OPERAND_ELEMS = (int64_t)(NUM_RECORDS / 4) - (4 << 20);
 bool span_ok(int64_t elems) { return elems >= 0 && elems <= MAX_OPERAND_ELEMS; }
 
 int check_conv(const bdetr_conv_desc* d, const char* who) {
-    BDETR_CHECK_ARG(d != nullptr, "%s: null desc", who);
-    BDETR_CHECK_ARG(d->N > 0 && d->H > 0 && d->W > 0 && d->C > 0 && d->K > 0 && d->R > 0 && d->S > 0 && d->stride > 0 && d->pad >= 0,
-                    "%s: bad conv geometry", who);
-    BDETR_CHECK_ARG(d->OH == (d->H + 2 * d->pad - d->R) / d->stride + 1 && d->OW == (d->W + 2 * d->pad - d->S) / d->stride + 1,
-                    "%s: OH/OW inconsistent with geometry", who);
+    if (int e = check_conv_geometry(d, who)) return e;
     BDETR_CHECK_ARG(d->C % 8 == 0 && d->K % 8 == 0, "%s: the P16 layout needs channel counts that are multiples of 8 (C=%d K=%d)", who, d->C, d->K);
     BDETR_CHECK_ARG((d->R == 1 && d->S == 1) || d->C % BK == 0, "%s: kernels larger than 1x1 need C %% %d == 0 (C=%d)", who, BK, d->C);
     BDETR_CHECK_ARG(d->R * d->S <= 32 && (int64_t)d->R * d->S * d->C <= 16384 && d->C <= 16384 && d->K <= 16384, "%s: at most 32 taps and rows of at most 16,384 elements", who);
@@ -811,7 +822,61 @@ PPatch make_patch(const void* p, int N, int H, int W, int C, int OH, int OW, int
     o.single_wrap = o.d_oh < OH;
     return o;
 }
-bool is_1x1_dense(const bdetr_conv_desc* d) { return d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0; }
+bool is_3x3_same(const bdetr_conv_desc* d) { return d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1; }      // what hconv.hip's halo kernel computes
+
+LaunchPlan fwd_plan(const bdetr_conv_desc* d) {
+    const int64_t M = (int64_t)d->N * d->OH * d->OW;
+    LaunchPlan p;
+    if (is_3x3_same(d) && hconv_plan(M, d->W, d->C, d->K, true, &p)) return p;
+    p = tile_plan(is_1x1_dense(d) ? FAM_DENSE : FAM_PATCH, choose_tile(M, d->K, 1));
+    p.stat_rows = (int)cdiv64(M, p.bm) * p.wm;
+    return p;
+}
+
+// vec: the launch accumulates or carries fused BatchNorm-backward sums (the float4 epilogue EPI_VEC of the dense stride-1 kernels)
+LaunchPlan bwd_data_plan(const bdetr_conv_desc* d, bool vec) {
+    const bool dense = d->R == 1 && d->S == 1 && d->pad == 0;        // any stride: strided 1x1 convolutions scatter their rows
+    const int64_t rows = dense ? (int64_t)d->N * d->OH * d->OW : (int64_t)d->N * d->H * d->W;
+    LaunchPlan p;
+    if (is_3x3_same(d) && hconv_plan(rows, d->W, d->K, d->C, false, &p)) return p;      // dy plays the input's role
+    int t = choose_tile(rows, d->C, 1);
+    // 1x1 stride-1 backward-data with accumulate / fused sums (EPI_VEC: one workgroup per tile, float4 epilogue with up to three tile-sized
+    // loads): short reductions (K <= 512) run 128x64 tiles - half the epilogue registers (no second half-pass), twice the workgroups to hide its
+    // round trips (masked accumulate + sums at 160x160: 0.373 -> 0.335 ms, 80x80: 0.213 -> 0.183); long ones keep the operand reuse of 128x128
+    if (dense && d->stride == 1 && vec && t == T_128x128 && d->K <= 512) t = T_128x64;
+    p = tile_plan(dense ? FAM_DENSE : FAM_PATCH, t);
+    p.stat_rows = (int)cdiv64(rows, p.bm);          // one partial row per tile_i (the LDS-transposed epilogue folds the tile's rows)
+    return p;
+}
+
+LaunchPlan bwd_weight_plan(const bdetr_conv_desc* d) {
+    const Switches& sw = switches();
+    const int M = d->N * d->OH * d->OW;
+    const int64_t Kd = (int64_t)d->R * d->S * d->C;
+    // (Round 4 measured 256x128 ping-pong tiles here - BDETR_WGRAD_PP: 586 / 574 images/s for the 3x3 layers / every layer against 592;
+    // one eight-wave workgroup per CU loses more to its serial prologue / atomic epilogue and to the halved slice count than the fill
+    // saves.  Removed in round 5 together with its instantiations.)
+    int t = T_128x128;
+    if (sw.forced_tile >= 0 && d->K % TILE_BM[sw.forced_tile] == 0 && Kd % TILE_BN[sw.forced_tile] == 0) t = sw.forced_tile;
+    else if (!(d->K % 128 == 0 && Kd % 128 == 0)) t = T_64x64;
+    // 1x1 layers: 128x64 (twice the workgroups per split-K slice, half the x-operand fragments per wave) measured 5-25 % faster than
+    // 128x128 on 13 of the 16 layer shapes of ResNet-50 at batch 16 (tools/tile_sweep.py, round 3); the stride-2 projections (K = 2 C) not
+    else if (d->R == 1 && d->S == 1 && !(d->stride > 1 && d->K > d->C) && !sw.wgrad_wide) t = T_128x64;
+    LaunchPlan p = tile_plan(is_1x1_dense(d) ? FAM_DENSE : FAM_PATCH, t);
+    const int64_t tiles = cdiv64(d->K, p.bm) * cdiv64(Kd, p.bn);
+    // floor, not ceil: all tiles x slices must fit the want_x * CUs resident slots at once - one workgroup more than
+    // that runs alone in a second round and doubles the launch's duration
+    // (3x3 layers on 64x64 tiles - the 64-channel layers of stage 2 - take three workgroups per CU: four fit, and the per-lane patch
+    // addressing of their loads wants more waves to hide behind; 0.156 -> 0.130 ms at 160x160x64, round 5, profiles/r05_wgrad_tile_sweep.txt)
+    const int want = (d->R == 1 && d->S == 1) ? sw.want_x : (t == T_64x64 && !sw.want_3x3_set ? sw.want_64 : sw.want_3x3);
+    int64_t sk = ((int64_t)want * num_cus()) / tiles;
+    const int64_t maxsk = cdiv64(M, (int64_t)sw.min_stages * BK);       // keep >= min_stages K-steps per split
+    if (sk > maxsk) sk = maxsk;
+    if (sk < 1) sk = 1;
+    if (sk > 512) sk = 512;
+    p.splitk = (int)sk;
+    return p;
+}
 
 }  // namespace
 
@@ -837,19 +902,8 @@ extern "C" int bdetr_p16_supported(const bdetr_conv_desc* d) {
     return 1;
 }
 
-static int fwd_tile(const bdetr_conv_desc* d) { return choose_tile((int64_t)d->N * d->OH * d->OW, d->K, 1); }
-
-// 3x3 / stride 1 / pad 1: the halo-resident kernel of hconv.hip (its tile as BM * 1000 + BN), else 0
-static int fwd_hconv(const bdetr_conv_desc* d) {
-    if (!(d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1)) return 0;
-    return hconv_tile((int64_t)d->N * d->H * d->W, d->W, d->C, d->K, true);
-}
-
 extern "C" int bdetr_p16_conv2d_fwd_stat_chunks(const bdetr_conv_desc* d) {
-    if (check_conv(d, "bdetr_p16_conv2d_fwd_stat_chunks")) return -1;
-    if (const int ht = fwd_hconv(d)) return (int)cdiv64((int64_t)d->N * d->OH * d->OW, ht / 1000) * 4;      // tiles_i * WM (4 wave rows)
-    const int t = fwd_tile(d);
-    return (int)cdiv64((int64_t)d->N * d->OH * d->OW, TILE_BM[t]) * TILE_WM[t];          // tiles_i * WM
+    return check_conv(d, "bdetr_p16_conv2d_fwd_stat_chunks") ? -1 : fwd_plan(d).stat_rows;
 }
 
 extern "C" int bdetr_p16_conv2d_fwd(const void* x_f16, const void* w_f16, const float* bias, float* y,
@@ -865,43 +919,19 @@ extern "C" int bdetr_p16_conv2d_fwd(const void* x_f16, const void* w_f16, const 
     g.stat_sum = stat_sum; g.stat_sq = stat_sq;
     PDense wop{w_f16, (unsigned)Kd, d->K, Kd};
     hipStream_t st = (hipStream_t)stream;
-    const int tile = fwd_tile(d);
-    if (is_1x1_dense(d)) {
+    const LaunchPlan p = fwd_plan(d);
+    if (p.family == FAM_DENSE) {
         PDense xop{x_f16, (unsigned)d->C, M, d->C};
-        return launch_any<RRDense, RRDense, false, true>(xop, wop, g, 1, st, 0, tile);
+        return launch_any<RRDense, RRDense, false, true>(xop, wop, g, 1, st, 0, p);
     }
-    if (const int ht = fwd_hconv(d)) return hconv_launch(ht, true, x_f16, d->N, d->H, d->W, d->C, w_f16, d->K, g, st);
+    if (p.family == FAM_HALO) return hconv_launch(p, true, x_f16, d->N, d->H, d->W, d->C, w_f16, d->K, g, st);
     PPatch xop = make_patch(x_f16, d->N, d->H, d->W, d->C, d->OH, d->OW, d->R, d->S, d->stride, d->pad, M, Kd);
-    return launch_any<RRPatch, RRDense, false, true>(xop, wop, g, 1, st, 1000, tile);
-}
-
-static int bwd_data_tile(const bdetr_conv_desc* d) {
-    const bool dense = d->R == 1 && d->S == 1 && d->pad == 0;
-    return choose_tile(dense ? (int64_t)d->N * d->OH * d->OW : (int64_t)d->N * d->H * d->W, d->C, 1);
-}
-
-// 1x1 stride-1 backward-data with accumulate / fused sums (EPI_VEC: one workgroup per tile, float4 epilogue with up to three tile-sized
-// loads): short reductions (K <= 512) run 128x64 tiles - half the epilogue registers (no second half-pass), twice the workgroups to hide its
-// round trips (masked accumulate + sums at 160x160: 0.373 -> 0.335 ms, 80x80: 0.213 -> 0.183); long ones keep the operand reuse of 128x128
-static int dense_vec_tile(const bdetr_conv_desc* d) {
-    const int t = bwd_data_tile(d);
-    return (t == T_128x128 && d->K <= 512) ? T_128x64 : t;
-}
-
-// 3x3 / stride 1 / pad 1: the halo-resident kernel of hconv.hip (its tile as BM * 1000 + BN), else 0
-static int bwd_data_hconv(const bdetr_conv_desc* d) {
-    if (!(d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1)) return 0;
-    return hconv_tile((int64_t)d->N * d->H * d->W, d->W, d->K, d->C, false);
+    return launch_any<RRPatch, RRDense, false, true>(xop, wop, g, 1, st, 1000, p);
 }
 
 // number of partial rows bdetr_p16_conv2d_bwd_data writes per statistic when the BatchNorm-backward reduction is fused
 extern "C" int bdetr_p16_conv2d_bwd_data_stat_chunks(const bdetr_conv_desc* d) {
-    if (check_conv(d, "bdetr_p16_conv2d_bwd_data_stat_chunks")) return -1;
-    const bool dense = d->R == 1 && d->S == 1 && d->pad == 0;
-    if (const int ht = bwd_data_hconv(d)) return (int)cdiv64((int64_t)d->N * d->H * d->W, ht / 1000);      // one partial row per tile_i
-    const int t = (dense && d->stride == 1) ? dense_vec_tile(d) : bwd_data_tile(d);
-    // one partial row per tile_i (the LDS-transposed epilogue folds the tile's rows)
-    return (int)cdiv64(dense ? (int64_t)d->N * d->OH * d->OW : (int64_t)d->N * d->H * d->W, TILE_BM[t]);
+    return check_conv(d, "bdetr_p16_conv2d_bwd_data_stat_chunks") ? -1 : bwd_data_plan(d, true).stat_rows;
 }
 
 // dy_bf16: P16-bf16 [N,OH,OW,K]; wt_bf16: the transposed / tap-flipped P16-bf16 weight copy [C][R*S][K]
@@ -932,29 +962,26 @@ static int p16_bwd_data(const void* dy_bf16, const void* wt_bf16, float* dx, con
             g.bnb2_y = bn->y2; g.bnb2_mean = bn->mean2; g.bnb2_rstd = bn->rstd2; g.bnb2_sum_gx = bn->part_gx2;
         }
     }
-    if (d->R == 1 && d->S == 1 && d->pad == 0) {
+    const LaunchPlan p = bwd_data_plan(d, accumulate || bn != nullptr);
+    if (p.family == FAM_DENSE) {
         g.I = M; g.J = d->C; g.R = d->K;
         if (d->stride > 1) {
-            if (!accumulate) {
-                if (int e = bdetr_zero_bytes(dx, sizeof(float) * (size_t)d->N * d->H * d->W * d->C, st)) return e;
-            }
-            g.rowmap = 1; g.rm_OW = d->OW; g.rm_OHOW = d->OH * d->OW; g.rm_H = d->H; g.rm_W = d->W; g.rm_stride = d->stride;
+            if (int e = set_rowmap(g, d, dx, accumulate, st)) return e;
         }
         PDense a{dy_bf16, (unsigned)d->K, M, d->K};
         PDense b{wt_bf16, (unsigned)d->K, d->C, d->K};
-        const bool vec = !g.rowmap && (g.mode == ST_ACCUM || g.bnb_y != nullptr);
-        return launch_any<RRDense, RRDense, false, false>(a, b, g, 1, st, 0, vec ? dense_vec_tile(d) : bwd_data_tile(d));
+        return launch_any<RRDense, RRDense, false, false>(a, b, g, 1, st, 0, p);
     }
     BDETR_CHECK_ARG(d->stride == 1 && d->R == d->S, "bdetr_p16_conv2d_bwd_data: stride>1 only for 1x1 convs; square kernels only");
     BDETR_CHECK_ARG(d->K % BK == 0, "bdetr_p16_conv2d_bwd_data: K %% %d == 0 required for kernels larger than 1x1", BK);
     // dx[n,ih,iw,c] = sum_{r',s',k} dy[n, ih - pad' + r', iw - pad' + s', k] * wt[c][r'][s'][k],  pad' = R-1-pad, wt pre-flipped
     const int Mx = d->N * d->H * d->W, Kd = d->R * d->S * d->K;
     g.I = Mx; g.J = d->C; g.R = Kd;
-    if (const int ht = bwd_data_hconv(d))                 // dy plays the input's role: same spatial size, K channels; wt rows = input channels
-        return hconv_launch(ht, false, dy_bf16, d->N, d->H, d->W, d->K, wt_bf16, d->C, g, st);
+    if (p.family == FAM_HALO)                              // dy plays the input's role: same spatial size, K channels; wt rows = input channels
+        return hconv_launch(p, false, dy_bf16, d->N, d->H, d->W, d->K, wt_bf16, d->C, g, st);
     PPatch a = make_patch(dy_bf16, d->N, d->OH, d->OW, d->K, d->H, d->W, d->R, d->S, 1, d->R - 1 - d->pad, Mx, Kd);
     PDense b{wt_bf16, (unsigned)Kd, d->C, Kd};
-    return launch_any<RRPatch, RRDense, false, false>(a, b, g, 1, st, 1000, bwd_data_tile(d));
+    return launch_any<RRPatch, RRDense, false, false>(a, b, g, 1, st, 1000, p);
 }
 
 extern "C" int bdetr_p16_conv2d_bwd_data(const void* dy_bf16, const void* wt_bf16, float* dx,
@@ -982,50 +1009,8 @@ extern "C" int bdetr_p16_conv2d_bwd_data_bnstats(const void* dy_bf16, const void
     return p16_bwd_data(dy_bf16, wt_bf16, dx, d, 0, bn, nullptr, stream);
 }
 
-static int wgrad_tile(const bdetr_conv_desc* d) {
-    const int64_t Kd = (int64_t)d->R * d->S * d->C;
-    // (Round 4 measured 256x128 ping-pong tiles here - BDETR_WGRAD_PP: 586 / 574 images/s for the 3x3 layers / every layer against 592;
-    // one eight-wave workgroup per CU loses more to its serial prologue / atomic epilogue and to the halved slice count than the fill
-    // saves.  Removed in round 5 together with its instantiations.)
-    const int forced = forced_tile();
-    if (forced >= 0 && d->K % TILE_BM[forced] == 0 && Kd % TILE_BN[forced] == 0) return forced;
-    if (!(d->K % 128 == 0 && Kd % 128 == 0)) return T_64x64;
-    // 1x1 layers: 128x64 (twice the workgroups per split-K slice, half the x-operand fragments per wave) measured 5-25 % faster than
-    // 128x128 on 13 of the 16 layer shapes of ResNet-50 at batch 16 (tools/tile_sweep.py, round 3); the stride-2 projections (K = 2 C) not
-    static int wide = -1;
-    if (wide < 0) { const char* e = getenv("BDETR_WGRAD_1X1_TILE"); wide = (e && !strcmp(e, "128x128")) ? 1 : 0; }     // (A/B switch)
-    if (d->R == 1 && d->S == 1 && !(d->stride > 1 && d->K > d->C) && !wide) return T_128x64;
-    return T_128x128;
-}
-
 extern "C" int bdetr_p16_conv2d_bwd_weight_splitk(const bdetr_conv_desc* d) {
-    if (check_conv(d, "bdetr_p16_conv2d_bwd_weight_splitk")) return -1;
-    const int M = d->N * d->OH * d->OW;
-    const int64_t Kd = (int64_t)d->R * d->S * d->C;
-    const int t = wgrad_tile(d);
-    const int64_t tiles = cdiv64(d->K, TILE_BM[t]) * cdiv64(Kd, TILE_BN[t]);
-    static int want_x = 0, want_3x3 = 0, min_stages = 0;
-    if (want_x == 0) {
-        const char* e = getenv("BDETR_WGRAD_WANT"); want_x = e ? atoi(e) : 2;      // measured: 2 workgroups per CU (5.9 ms over the ResNet-50 layers) beats 1 (6.5), 3 (6.4), 4 (6.9): atomic bytes grow with the split
-        const char* e3 = getenv("BDETR_WGRAD_WANT_3X3"); want_3x3 = e3 ? atoi(e3) : want_x;      // (the same for the im2col layers alone: A/B switch)
-        if (want_3x3 < 1) want_3x3 = 1;
-        const char* f = getenv("BDETR_WGRAD_MINSTAGES"); min_stages = f ? atoi(f) : 8;
-        if (want_x < 1) want_x = 1;
-        if (min_stages < 1) min_stages = 1;
-    }
-    // floor, not ceil: all tiles x slices must fit the want_x * CUs resident slots at once - one workgroup more than
-    // that runs alone in a second round and doubles the launch's duration
-    // (3x3 layers on 64x64 tiles - the 64-channel layers of stage 2 - take three workgroups per CU: four fit, and the per-lane patch
-    // addressing of their loads wants more waves to hide behind; 0.156 -> 0.130 ms at 160x160x64, round 5, profiles/r05_wgrad_tile_sweep.txt)
-    static int want_64 = 0;
-    if (want_64 == 0) { const char* e64 = getenv("BDETR_WGRAD_WANT_64"); want_64 = e64 ? atoi(e64) : 3; if (want_64 < 1) want_64 = 1; }
-    const int want = (d->R == 1 && d->S == 1) ? want_x : (t == T_64x64 && getenv("BDETR_WGRAD_WANT_3X3") == nullptr ? want_64 : want_3x3);
-    int64_t sk = ((int64_t)want * num_cus()) / tiles;
-    const int64_t maxsk = cdiv64(M, (int64_t)min_stages * BK);       // keep >= min_stages K-steps per split
-    if (sk > maxsk) sk = maxsk;
-    if (sk < 1) sk = 1;
-    if (sk > 512) sk = 512;
-    return (int)sk;
+    return check_conv(d, "bdetr_p16_conv2d_bwd_weight_splitk") ? -1 : bwd_weight_plan(d).splitk;
 }
 
 // x_bf16: P16-bf16 [N,H,W,C]; dy_bf16: P16-bf16 [N,OH,OW,K]; dw: fp32 [K][R][S][C], must hold zeros (or the
@@ -1036,37 +1021,25 @@ static int p16_bwd_weight(const void* x_bf16, int x_is_f16, const void* dy_bf16,
     BDETR_CHECK_ARG(x_bf16 && dy_bf16 && dw, "bdetr_p16_conv2d_bwd_weight: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const int M = d->N * d->OH * d->OW, Kd = d->R * d->S * d->C;
-    if (splitk <= 0) splitk = bdetr_p16_conv2d_bwd_weight_splitk(d);
+    const LaunchPlan p = bwd_weight_plan(d);
+    if (splitk <= 0) splitk = p.splitk;
     GemmParams g; init_params(g);
     g.b_f16 = x_is_f16;
     g.I = d->K; g.J = Kd; g.R = M;
     g.c = dw; g.ldc = Kd;
-    int zdim = 1;
-    if (splitk > 1) {
-        g.r_chunk = (int)(cdiv64(cdiv64(M, splitk), BK) * BK);
-        zdim = (int)cdiv64(M, g.r_chunk);
-        g.splitk = zdim > 1 ? zdim : 2;
-        g.mode = ST_ATOMIC;
-    }
+    const int zdim = splitk > 1 ? set_splitk(g, M, splitk, BK) : 1;
     PDense a{dy_bf16, (unsigned)d->K, M, d->K};          // rows = r (pixels), cols = i (output channels)
-    const int tile = wgrad_tile(d);
-    const bool slabs = ws != nullptr && splitk > 1;      // deterministic mode: partial tiles to the caller's workspace, fixed-order fold
-    const int64_t n = (int64_t)d->K * Kd, slab = splitk_slab(n);
-    if (slabs) {
-        BDETR_CHECK_ARG(aligned16(ws) && ws_elems >= (int64_t)zdim * slab, "bdetr_p16_conv2d_bwd_weight_ws: workspace too small or misaligned (%lld floats, need %lld)",
-                        (long long)ws_elems, (long long)((int64_t)zdim * slab));
-        g.c = ws; g.sc0 = slab; g.mode = ST_STORE;
-    }
-    int e;
-    if (is_1x1_dense(d)) {
-        PDense b{x_bf16, (unsigned)d->C, M, d->C};
-        e = launch_any<XXDense, XXDense, true, false>(a, b, g, zdim, st, 2000, tile);
-    } else {
+    auto launch = [&]() -> int {
+        if (p.family == FAM_DENSE) {
+            PDense b{x_bf16, (unsigned)d->C, M, d->C};
+            return launch_any<XXDense, XXDense, true, false>(a, b, g, zdim, st, 2000, p);
+        }
         PPatch b = make_patch(x_bf16, d->N, d->H, d->W, d->C, d->OH, d->OW, d->R, d->S, d->stride, d->pad, M, Kd);
-        e = launch_any<XXDense, XXPatch, true, false>(a, b, g, zdim, st, 3000, tile);
-    }
-    if (e || !slabs) return e;
-    return splitk_fold(ws, zdim, slab, dw, n, st);
+        return launch_any<XXDense, XXPatch, true, false>(a, b, g, zdim, st, 3000, p);
+    };
+    // deterministic mode: partial tiles to the caller's workspace, fixed-order fold
+    if (ws != nullptr && splitk > 1) return with_splitk_slabs(g, zdim, ws, ws_elems, st, "bdetr_p16_conv2d_bwd_weight_ws", launch);
+    return launch();
 }
 extern "C" int bdetr_p16_conv2d_bwd_weight_ws(const void* x, int x_is_f16, const void* dy_bf16, float* dw,
                                               const bdetr_conv_desc* d, int splitk, float* ws, int64_t ws_elems, void* stream) {
@@ -1102,14 +1075,8 @@ extern "C" int bdetr_p16_stem_bwd_weight(const void* x2_bf16, const void* dy_bf1
     if (sk > maxsk) sk = maxsk;
     if (sk < 1) sk = 1;
     if (sk > 1024) sk = 1024;
-    int zdim = 1;
-    if (sk > 1) {
-        g.r_chunk = (int)(cdiv64(cdiv64(M, sk), BK) * BK);
-        zdim = (int)cdiv64(M, g.r_chunk);
-        g.splitk = zdim > 1 ? zdim : 2;
-        g.mode = ST_ATOMIC;
-    }
+    const int zdim = sk > 1 ? set_splitk(g, M, (int)sk, BK) : 1;
     PDense a{dy_bf16, (unsigned)K, M, K};
     PPatch b = make_patch(x2_bf16, N, H2, W2, 16, H2, W2, 4, 4, 1, 2, M, Kd);
-    return launch_any<XXDense, XXPatch, true, false>(a, b, g, zdim, (hipStream_t)stream, 3000, T_64x64);
+    return launch_any<XXDense, XXPatch, true, false>(a, b, g, zdim, (hipStream_t)stream, 3000, tile_plan(FAM_PATCH, T_64x64));
 }

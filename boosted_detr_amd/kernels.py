@@ -221,8 +221,9 @@ class ConvGeom:
         return ConvDesc(self.N, self.H, self.W, self.C, self.K, self.R, self.S, self.stride, self.pad, self.OH, self.OW)
 
 
-def conv2d_fwd(x, w, bias, g: ConvGeom, act: int = ACT_NONE, want_stats: bool = False):
-    """x [N,H,W,C], w [K,R,S,C] (OHWI), bias [K] -> y [N,OH,OW,K] (+ partial column stats)."""
+# The fp32 path (csrc/igemm.hip, symbols bdetr_conv2d_*) and the pre-split path (csrc/sgemm.hip, bdetr_p16_conv2d_*) take the same
+# arguments pass by pass; `family` is the symbol stem ("conv2d" / "p16_conv2d"), which the error texts carry too.
+def _conv2d_fwd(family: str, x, w, bias, g: ConvGeom, act: int, want_stats: bool):
     _chk(x, w, bias)
     L = _lib.lib()
     d = g.desc()
@@ -230,40 +231,54 @@ def conv2d_fwd(x, w, bias, g: ConvGeom, act: int = ACT_NONE, want_stats: bool = 
     psum = psq = None
     nparts = 0
     if want_stats:
-        nparts = L.bdetr_conv2d_fwd_stat_chunks(C.byref(d))
+        nparts = getattr(L, f"bdetr_{family}_fwd_stat_chunks")(C.byref(d))
         if nparts <= 0:
-            check(-1, "conv2d_fwd_stat_chunks")
+            check(-1, f"{family}_fwd_stat_chunks")
         psum = empty(nparts, g.K, like=x)
         psq = empty(nparts, g.K, like=x)
-    check(L.bdetr_conv2d_fwd(_p(x), _p(w), _p(bias), _p(y), C.byref(d), act, _p(psum), _p(psq), _stream()), "conv2d_fwd")
+    check(getattr(L, f"bdetr_{family}_fwd")(_p(x), _p(w), _p(bias), _p(y), C.byref(d), act, _p(psum), _p(psq), _stream()), f"{family}_fwd")
     return y, (psum, psq, nparts)
 
 
-def conv2d_bwd_data(dy, w, g: ConvGeom, dx: Optional[torch.Tensor] = None, accumulate: bool = False):
+def _conv2d_bwd_data(family: str, dy, w, g: ConvGeom, dx: Optional[torch.Tensor], accumulate: bool):
     _chk(dy, w, dx)
     d = g.desc()
     if dx is None:
         assert not accumulate
         dx = empty(g.N, g.H, g.W, g.C, like=dy)
-    check(_lib.lib().bdetr_conv2d_bwd_data(_p(dy), _p(w), _p(dx), C.byref(d), int(accumulate), _stream()), "conv2d_bwd_data")
+    check(getattr(_lib.lib(), f"bdetr_{family}_bwd_data")(_p(dy), _p(w), _p(dx), C.byref(d), int(accumulate), _stream()), f"{family}_bwd_data")
     return dx
 
 
-def conv2d_bwd_weight(x, dy, g: ConvGeom, dw: Optional[torch.Tensor] = None, prezeroed: bool = False):
-    """prezeroed: dw already holds zeros (the optimizer's flat gradient buffer is cleared once per step),
-    so the split-K atomics need no per-tensor memset."""
+def _conv2d_bwd_weight(family: str, x, x_flags: tuple, dy, g: ConvGeom, dw: Optional[torch.Tensor], prezeroed: bool):
+    """x_flags: what the family's entry point takes between x and dy (the pre-split one: whether x is the f16 pair)."""
     _chk(x, dy, dw)
     L = _lib.lib()
     d = g.desc()
     if dw is None:
         dw = empty(g.K, g.R, g.S, g.C, like=x)
         prezeroed = False
-    sk = L.bdetr_conv2d_bwd_weight_splitk(C.byref(d))
+    sk = getattr(L, f"bdetr_{family}_bwd_weight_splitk")(C.byref(d))
     if sk > 1 and not prezeroed:
         check(L.bdetr_zero(_p(dw), dw.numel(), _stream()), "zero")
     ws, n = _splitk_ws(g.K, g.R * g.S * g.C, sk, x)
-    check(L.bdetr_conv2d_bwd_weight_ws(_p(x), _p(dy), _p(dw), C.byref(d), sk, _p(ws), n, _stream()), "conv2d_bwd_weight")
+    check(getattr(L, f"bdetr_{family}_bwd_weight_ws")(_p(x), *x_flags, _p(dy), _p(dw), C.byref(d), sk, _p(ws), n, _stream()), f"{family}_bwd_weight")
     return dw
+
+
+def conv2d_fwd(x, w, bias, g: ConvGeom, act: int = ACT_NONE, want_stats: bool = False):
+    """x [N,H,W,C], w [K,R,S,C] (OHWI), bias [K] -> y [N,OH,OW,K] (+ partial column stats)."""
+    return _conv2d_fwd("conv2d", x, w, bias, g, act, want_stats)
+
+
+def conv2d_bwd_data(dy, w, g: ConvGeom, dx: Optional[torch.Tensor] = None, accumulate: bool = False):
+    return _conv2d_bwd_data("conv2d", dy, w, g, dx, accumulate)
+
+
+def conv2d_bwd_weight(x, dy, g: ConvGeom, dw: Optional[torch.Tensor] = None, prezeroed: bool = False):
+    """prezeroed: dw already holds zeros (the optimizer's flat gradient buffer is cleared once per step),
+    so the split-K atomics need no per-tensor memset."""
+    return _conv2d_bwd_weight("conv2d", x, (), dy, g, dw, prezeroed)
 
 
 # --------------------------------------------------------------------------------------
@@ -422,30 +437,11 @@ def p16_pack_conv_weights_multi(table: torch.Tensor) -> None:
 
 
 def p16_conv2d_fwd(x_f16, w_f16, bias, g: ConvGeom, act: int = ACT_NONE, want_stats: bool = False):
-    _chk(x_f16, w_f16, bias)
-    L = _lib.lib()
-    d = g.desc()
-    y = empty(g.N, g.OH, g.OW, g.K, like=x_f16)
-    psum = psq = None
-    nparts = 0
-    if want_stats:
-        nparts = L.bdetr_p16_conv2d_fwd_stat_chunks(C.byref(d))
-        if nparts <= 0:
-            check(-1, "p16_conv2d_fwd_stat_chunks")
-        psum = empty(nparts, g.K, like=x_f16)
-        psq = empty(nparts, g.K, like=x_f16)
-    check(L.bdetr_p16_conv2d_fwd(_p(x_f16), _p(w_f16), _p(bias), _p(y), C.byref(d), act, _p(psum), _p(psq), _stream()), "p16_conv2d_fwd")
-    return y, (psum, psq, nparts)
+    return _conv2d_fwd("p16_conv2d", x_f16, w_f16, bias, g, act, want_stats)
 
 
 def p16_conv2d_bwd_data(dy_bf16, wt_bf16, g: ConvGeom, dx: Optional[torch.Tensor] = None, accumulate: bool = False):
-    _chk(dy_bf16, wt_bf16, dx)
-    d = g.desc()
-    if dx is None:
-        assert not accumulate
-        dx = empty(g.N, g.H, g.W, g.C, like=dy_bf16)
-    check(_lib.lib().bdetr_p16_conv2d_bwd_data(_p(dy_bf16), _p(wt_bf16), _p(dx), C.byref(d), int(accumulate), _stream()), "p16_conv2d_bwd_data")
-    return dx
+    return _conv2d_bwd_data("p16_conv2d", dy_bf16, wt_bf16, g, dx, accumulate)
 
 
 def relu_mask_apply_(x: torch.Tensor, relu_mask: torch.Tensor) -> torch.Tensor:
@@ -520,18 +516,7 @@ def p16_conv2d_bwd_data_bnstats(dy_bf16, wt_bf16, g: ConvGeom, y_prev, mean, rst
 
 def p16_conv2d_bwd_weight(x_bf16, dy_bf16, g: ConvGeom, dw: Optional[torch.Tensor] = None, prezeroed: bool = False, x_f16: bool = False):
     """x_f16: `x_bf16` is the P16-f16 tensor the forward read (converted to bf16 pairs inside the kernel)."""
-    _chk(x_bf16, dy_bf16, dw)
-    L = _lib.lib()
-    d = g.desc()
-    if dw is None:
-        dw = empty(g.K, g.R, g.S, g.C, like=x_bf16)
-        prezeroed = False
-    sk = L.bdetr_p16_conv2d_bwd_weight_splitk(C.byref(d))
-    if sk > 1 and not prezeroed:
-        check(L.bdetr_zero(_p(dw), dw.numel(), _stream()), "zero")
-    ws, n = _splitk_ws(g.K, g.R * g.S * g.C, sk, x_bf16)
-    check(L.bdetr_p16_conv2d_bwd_weight_ws(_p(x_bf16), int(x_f16), _p(dy_bf16), _p(dw), C.byref(d), sk, _p(ws), n, _stream()), "p16_conv2d_bwd_weight")
-    return dw
+    return _conv2d_bwd_weight("p16_conv2d", x_bf16, (int(x_f16),), dy_bf16, g, dw, prezeroed)
 
 
 # --------------------------------------------------------------------------------------

@@ -68,7 +68,7 @@ def hconv_cases(tile):
 
 def stile_cases(tile):
     """Fused backward-data epilogues on one forced sgemm tile (BDETR_HCONV=0): rows = 297, C % BN != 0; K = 520 keeps the
-    forced 128x128 tile on the dense float4 epilogue (dense_vec_tile() halves it for K <= 512)."""
+    forced 128x128 tile on the dense float4 epilogue (bwd_data_plan() halves it for K <= 512)."""
     return [("bnstats", (3, 9, 11, 160, 64, 3), "3x3 fused sums"), ("bnstats", (3, 9, 11, 136, 520, 1), "1x1 fused sums"),
             ("masked", (3, 9, 11, 136, 520, False), "masked accumulate"), ("masked", (3, 9, 11, 136, 520, True), "masked accumulate + fused sums")]
 

@@ -2,7 +2,7 @@
 covered by test_default_policy_is_mixed) against fp64 products.  Tolerances: exact-fp32 MFMA and split-fp16 forward
 products 2e-5 x max|ref| (fp32-grade round-off over the sum), split-bf16 6e-5 x max|ref| (2^-18 per product).
 
-Which kernel variant a shape reaches depends on the tile chooser (csrc/igemm.hip choose_tile): the 128x128 split
+Which kernel variant a shape reaches depends on the tile chooser (csrc/igemm.hip plan_tile): the 128x128 split
 tiles are only picked when the grid still fills the chip, i.e. at the benchmark's batch-16 shapes.  BIG_CONVS /
 BIG_LINEARS below are sized to cross that threshold, and test_bench_step_variants_are_all_oracle_tested asserts
 that EVERY (arithmetic, loaders, layouts, tile) tuple a config-2 batch-16 training step launches is also launched -

@@ -1,6 +1,6 @@
 """Every selectable variant of the conv/GEMM kernel family, forced by its environment switch and compared with fp64.
 
-The choosers (hconv_tile, choose_tile / wgrad_tile / dense_vec_tile, igemm's choose_tile, attn_split_enabled) pick a compiled
+The choosers (hconv_plan, sgemm.hip's choose_tile / bwd_data_plan / bwd_weight_plan, igemm.hip's plan_tile, attn_split_enabled) pick a compiled
 variant from the problem size and the CU count; the other kernel tests check whatever they pick for the listed shapes.  Here
 each variant is FORCED (the switches are read once per process, so every variant runs in a child process,
 tests/_variant_child.py) on the geometries where tiled kernels go wrong, and the parent asserts
