@@ -232,6 +232,7 @@ SIGNATURES = {
     "bdetr_attr_pack": (I, [P, L, I, P, P, P]),
     "bdetr_det_match_attr": (I, [P] * 16 + [C.c_double] + [I] * 9 + [P] * 7),
     "bdetr_mask_match_attr": (I, [P] * 18 + [C.c_double] + [I] * 10 + [P] * 7),
+    "bdetr_token_key_mask": (I, [P, I, I, I, I, I, P, P]),
 }
 
 

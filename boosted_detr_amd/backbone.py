@@ -126,6 +126,19 @@ class EncoderBackbone(Layer):
         c.update({"image_input_shape": self.image_input_shape})
         return c
 
+    def feature_hw(self):
+        """(r, c) of the feature grid this backbone leaves for its image_input_shape, from the layers' own geometry (the stem,
+        the max pool, every unit's first 1x1), without running anything."""
+        net = self.ImageFeaturesExtractor
+        out = []
+        for s in self.image_input_shape[:2]:
+            s = (int(s) + 2 * net.stem.pad - 7) // net.stem.stride + 1
+            s = (s + 2 - 3) // 2 + 1                       # ZeroPad1 + maxpool3x3/2
+            for blk in net.blocks:
+                s = (s - 1) // blk["c1"].stride + 1
+            out.append(s)
+        return tuple(out)
+
     def call(self, inputs, training=False):
         image = inputs[0]                                  # [B,h,w,3] in [0,1]
         height, width = self.image_input_shape[:2]

@@ -8,7 +8,7 @@ the matcher + loss run on the cumulative predictions of every learner (232-243).
 from __future__ import annotations
 
 from . import backbone, losses_and_metrics, ops, prediction_heads, tokenizers, transformers
-from .model import DETR, _image, _inference_outputs, _prepare_targets
+from .model import DETR, _image, _inference_outputs, _prepare_targets, _token_key_mask, _valid_region
 from .training import Model
 
 
@@ -64,20 +64,23 @@ class BoostedDETR(Model):
 
     def call(self, inputs, training=False, raw=False):
         focused_training_layer = None          # hard-coded in the reference (boosted_model.py:171)
+        valid_region = _valid_region(self, inputs)             # optional, as in DETR.call: refused before anything is launched
         image = _image(inputs)
         if training:
             y_true = _prepare_targets(self, inputs)
         encoder_features = self.EncoderBackbone([image], training=training)
         encoder_features = self.BackboneNeck([encoder_features], training=training)
+        key_mask = _token_key_mask(valid_region, encoder_features)       # one mask for every learner; None without the key
 
         loss_terms, metrics_i = [], None
         cat_preds = attribute_preds = box_coord_preds = None
         for i in range(self.num_decoder_blocks):
             # (the reference reshapes the carried features back to [B,r,c,D]; they already are)
-            encoder_features, positional_encoding = self.EncoderTransformerBlocks[i]([encoder_features], training=training)
+            encoder_features, positional_encoding = self.EncoderTransformerBlocks[i]([encoder_features], training=training, attention_mask=key_mask)
             enc_value, decoder_features, encoder_key, decoder_positional = \
                 self.DecoderPrep([encoder_features, positional_encoding], training=training)
-            decoder_features = self.DecoderBlocks[i]([enc_value, decoder_features, encoder_key, decoder_positional], training=training)
+            decoder_features = self.DecoderBlocks[i]([enc_value, decoder_features, encoder_key, decoder_positional], training=training,
+                                                     joint_attention_mask=key_mask)
             cat_preds_i = self.CategoryBlocks[i]([decoder_features], training=training)
             attribute_preds_i = self.AttributeBlocks[i]([decoder_features], training=training)
             box_coord_preds_i = self.BoxBlocks[i]([decoder_features], training=training)

@@ -900,6 +900,31 @@ def attention_mask_apply(x, mask, fill=False, out=None):
     return out
 
 
+def token_keep_host(region, h, w, r, c) -> np.ndarray:
+    """The rule of token_key_mask (include/bdetr.h K35) on the host, NumPy int64: region [B,4] rows (top, left, height, width) in
+    pixels of an h x w image -> bool [B, r*c], token (i, j) at i*c + j kept iff its centre lies in the region."""
+    g = np.asarray(region).astype(np.int64).reshape(-1, 4)
+    top, left, height, width = (g[:, k, None] for k in range(4))
+    ci = (2 * np.arange(r, dtype=np.int64) + 1)[None, :] * np.int64(h)
+    cj = (2 * np.arange(c, dtype=np.int64) + 1)[None, :] * np.int64(w)
+    rows = (2 * r * top <= ci) & (ci < 2 * r * (top + height))
+    cols = (2 * c * left <= cj) & (cj < 2 * c * (left + width))
+    return (rows[:, :, None] & cols[:, None, :]).reshape(g.shape[0], r * c)
+
+
+def token_key_mask(region, h, w, r, c):
+    """region int32 [B,4] in HBM, rows (top, left, height, width) in pixels of an h x w image -> bool [B,1,1,r*c], the key mask of
+    attention_fwd's exclusion rule over the tokens of an r x c feature grid: True where the token's centre lies in the region
+    (include/bdetr.h K35).  One launch that reads `region` on the device; nothing is read back."""
+    _chk(region, dtype=torch.int32)
+    if region.dim() != 2 or region.shape[1] != 4:
+        raise ValueError(f"region must be int32 [B,4], got shape {tuple(region.shape)}")
+    B = region.shape[0]
+    mask = torch.empty((B, int(r) * int(c)), dtype=torch.uint8, device=region.device)
+    check(_lib.lib().bdetr_token_key_mask(_p(region), B, int(h), int(w), int(r), int(c), _p(mask), _stream()), "token_key_mask")
+    return mask.view(torch.bool).view(B, 1, 1, int(r) * int(c))
+
+
 def softmax_rows_fwd(s2d, scale=1.0, out=None):
     _chk(s2d, out)
     rows, cols = s2d.shape

@@ -13,7 +13,8 @@ import numpy as np
 import torch
 
 from . import backbone, losses_and_metrics, ops, prediction_heads, tokenizers, transformers
-from .engine import to_device
+from . import kernels as K
+from .engine import device, to_device
 from .training import Model
 
 
@@ -48,6 +49,64 @@ def _inference_outputs(model, cat_preds, attribute_preds, box_coord_preds, raw: 
 def _image(inputs):
     img = inputs["image"]
     return to_device(img if isinstance(img, torch.Tensor) else np.asarray(img, np.float32))
+
+
+VALID_REGION_KEY = "valid_region"
+
+
+def check_valid_region(region, B: int, h: int, w: int, r: int, c: int, device=None):
+    """inputs["valid_region"] against its contract, on the host and before anything is launched: int32 [B,4], rows (top, left,
+    height, width) in pixels of the batch's h x w image as given.  Every failure is a ValueError.
+    Every form: shape, dtype, and a device tensor on another device than `device` (None: not compared).
+    A host array (a device tensor is never read back): top >= 0, left >= 0, height >= 1, width >= 1, the region inside the image,
+    and at least one kept token per image on the r x c feature grid (kernels.token_keep_host, the kernel's integer rule).
+    Returns the entry ready for to_device: the device tensor itself, or the host array as a contiguous int32 ndarray."""
+    on_device = isinstance(region, torch.Tensor) and region.is_cuda
+    if not on_device:
+        region = region.numpy() if isinstance(region, torch.Tensor) else np.asarray(region)
+    dtype_ok = region.dtype == (torch.int32 if on_device else np.int32)
+    if not dtype_ok:
+        raise ValueError(f"valid_region must be int32, got {region.dtype}")
+    if tuple(region.shape) != (B, 4):
+        raise ValueError(f"valid_region must be [B,4] = [{B},4] rows (top, left, height, width), got shape {tuple(region.shape)}")
+    if on_device:
+        if device is not None and region.device != device:
+            raise ValueError(f"valid_region lives on {region.device}, the model on {device}")
+        return region
+    g = region.astype(np.int64)
+    top, left, height, width = g[:, 0], g[:, 1], g[:, 2], g[:, 3]
+    for name, bad in (("top < 0", top < 0), ("left < 0", left < 0), ("height < 1", height < 1), ("width < 1", width < 1),
+                      (f"top + height > {h}", top + height > h), (f"left + width > {w}", left + width > w)):
+        if bad.any():
+            b = int(np.argmax(bad))
+            raise ValueError(f"valid_region[{b}] = {g[b].tolist()} of a {h} x {w} image: {name}")
+    empty = ~K.token_keep_host(g, h, w, r, c).any(axis=1)
+    if empty.any():
+        b = int(np.argmax(empty))
+        raise ValueError(f"valid_region[{b}] = {g[b].tolist()} of a {h} x {w} image holds no token centre of the {r} x {c} feature grid")
+    return np.ascontiguousarray(region)
+
+
+def _valid_region(model, inputs):
+    """inputs["valid_region"] checked (check_valid_region; nothing launched yet) and in HBM with the image's (h, w), or None without the key."""
+    region = inputs.get(VALID_REGION_KEY)
+    if region is None:
+        return None
+    shape = tuple(np.shape(inputs["image"]))
+    if len(shape) != 4:
+        raise ValueError(f"valid_region needs an image [B,h,w,3], got shape {shape}")
+    B, h, w = (int(s) for s in shape[:3])
+    r, c = model.EncoderBackbone.feature_hw()
+    return to_device(check_valid_region(region, B, h, w, r, c, device()), torch.int32), h, w
+
+
+def _token_key_mask(valid_region, features):
+    """The key mask [B,1,1,r*c] (bool, True attends) of the neck's output [B,r,c,D] for _valid_region's answer: one launch per call,
+    on the device (include/bdetr.h K35), so a captured step follows the regions in its static input buffer.  None without the key."""
+    if valid_region is None:
+        return None
+    region, h, w = valid_region
+    return K.token_key_mask(region, h, w, int(features.shape[1]), int(features.shape[2]))
 
 
 class DETR(Model):
@@ -152,6 +211,9 @@ class DETR(Model):
         return c
 
     def call(self, inputs, training=False, raw=False):
+        """inputs["valid_region"] (optional; check_valid_region): the padding tokens are excluded as KEYS from the encoder's
+        self-attention and from every decoder block's attention over the image (K33 / K35).  Without the key: the unmasked kernels."""
+        valid_region = _valid_region(self, inputs)                # every refusal of the entry before anything is launched
         image = _image(inputs)
         if training:
             y_true = _prepare_targets(self, inputs)
@@ -160,7 +222,8 @@ class DETR(Model):
 
         encoder_features = self.EncoderBackbone([image], training=training)
         encoder_features = self.BackboneNeck([encoder_features], training=training)
-        encoder_features, positional_encoding = self.ImageEncoderAttention([encoder_features], training=training)
+        key_mask = _token_key_mask(valid_region, encoder_features)       # None without the key
+        encoder_features, positional_encoding = self.ImageEncoderAttention([encoder_features], training=training, attention_mask=key_mask)
         image_encoding = encoder_features                         # [B, r, c, D]
         encoder_features, decoder_features, encoder_key, decoder_positional = \
             self.DecoderPrep([encoder_features, positional_encoding], training=training)
@@ -170,7 +233,8 @@ class DETR(Model):
         loss_terms, metrics_i, y_pred_i = [], None, None
         layer_outputs, aux_preds, aux_logits, aux_matches = [], [], [], []
         for i in range(self.num_decoder_blocks):
-            decoder_features = self.DecoderBlocks[i]([encoder_features, decoder_features, encoder_key, decoder_positional], training=training)
+            decoder_features = self.DecoderBlocks[i]([encoder_features, decoder_features, encoder_key, decoder_positional], training=training,
+                                                     joint_attention_mask=key_mask)
             if stacked:
                 layer_outputs.append(decoder_features)
             elif training and (use_intermediate_losses or i >= self.num_decoder_blocks - 1):

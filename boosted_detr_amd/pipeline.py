@@ -234,14 +234,21 @@ class Augmentations:
 
     A batch that carries 'segments' (pad_annotations(with_masks=True)) also gets 'masks' and 'mask_area' (mask_targets), placed
     by the SAME draw that moved the image: (H, W, new_h, new_w, off_h, off_w).  The masks follow the image's true geometry - the
-    source stretched to new_h x new_w at (off_h, off_w) - while the boxes keep the reference's quirky arithmetic (adjust_boxes)."""
+    source stretched to new_h x new_w at (off_h, off_w) - while the boxes keep the reference's quirky arithmetic (adjust_boxes).
+
+    with_valid_region=True: the output also carries 'valid_region', int32 [B,4] on the host, rows (off_h, off_w, new_h, new_w) of that
+    same draw - the picture's place on the canvas, which DETR.call / BoostedDETR.call turn into a key mask over the padding tokens
+    (include/bdetr.h K35).  With the default False the output has the keys it always had."""
 
     image_key, bbox_key, segments_key = "image", "bbox", "segments"
     mask_grid = MASK_GRID
 
-    def __init__(self, seed: int = 0, jpeg_quality: bool = True):
+    valid_region_key = "valid_region"
+
+    def __init__(self, seed: int = 0, jpeg_quality: bool = True, with_valid_region: bool = False):
         self.rng = np.random.Generator(np.random.PCG64(seed))
         self.jpeg_quality = jpeg_quality
+        self.with_valid_region = bool(with_valid_region)
 
     def draw(self, B: int, H: int, W: int) -> Dict[str, np.ndarray]:
         # rand_val = max(1, truncated_normal(mean .5, std .7)): mostly 1 (no down-size), up to ~1.9
@@ -288,6 +295,8 @@ class Augmentations:
         if self.segments_key in batch:
             place = np.stack([np.full(B, H), np.full(B, W), p["new_h"], p["new_w"], p["off_h"], p["off_w"]], axis=-1).astype(np.int32)
             out.update(mask_targets(batch[self.segments_key], self.mask_grid, place))
+        if self.with_valid_region:
+            out[self.valid_region_key] = np.stack([p["off_h"], p["off_w"], p["new_h"], p["new_w"]], axis=-1).astype(np.int32)
         return out
 
     def apply_image_augmentations(self, dataset: Iterable[dict]) -> Iterator[dict]:

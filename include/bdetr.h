@@ -1092,6 +1092,28 @@ int bdetr_attention_masked_bwd(const float* q, const float* k, const float* v, c
 int bdetr_attention_mask_apply(const float* x, float* out, int B, int h, int nq, int nk,
                                const void* mask, int64_t mask_sb, int64_t mask_sh, int64_t mask_sq, int mask_mode, int fill, void* stream);
 
+/* ------------------------------------------------------------------------
+ * K35  bdetr_token_key_mask (csrc/tokenmask.hip; kernels.token_key_mask; the batch key `valid_region` of DETR.call /
+ *   BoostedDETR.call).  An addition to ABI 8.  Valid image regions -> the key mask of K33 over the tokens of an r x c feature grid.
+ *
+ *   region: int32 [B,4] in HBM, rows (top, left, height, width) in pixels of an h x w image: rows [top, top + height) and columns
+ *   [left, left + width) hold picture, the rest is padding.  mask: uint8 [B, r*c], token (i, j) at index i*c + j; 1 = attends.
+ *
+ *   The rule is this project's own and is stated in integers (int64, no floats, nothing rounded).  Token (i, j) is kept iff its
+ *   centre, taken in image pixels, lies in the region:
+ *       2 r top  <= (2 i + 1) h < 2 r (top + height)     and     2 c left <= (2 j + 1) w < 2 c (left + width)
+ *   i.e. (i + 1/2) h / r in [top, top + height): top and left inclusive, bottom and right exclusive.  This is "nearest" sampling with
+ *   half-pixel centres, the convention of K19.  DETR proper interpolates its pixel mask to the feature size with mode="nearest";
+ *   equality with that is NOT claimed (its index rule floors i h / r, without the half pixel).
+ *
+ *   The kernel reads `region` from HBM - one thread per token, one plain byte store each, no atomics, no memset or memcpy - so a
+ *   captured step replayed after the region buffer changed makes the mask of the new regions.  Nothing in `region` is validated on
+ *   the device: a row with no picture (height or width < 1), or one that covers no token centre, gives an all-zero mask row, which
+ *   K33 answers with O = 0, lse = -inf and no NaN.  Returns -1 before the launch (bdetr_last_error says why) on a null pointer,
+ *   B outside [1, 65535], h, w, r or c outside [1, 2^20] (every product of the rule then stays below 2^54), or r*c above 2^31 - 257.
+ * ---------------------------------------------------------------------- */
+int bdetr_token_key_mask(const int32_t* region, int B, int h, int w, int r, int c, uint8_t* mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
